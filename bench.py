@@ -11,7 +11,10 @@ One step = ONE CALL of avk_compare_batch: the reference's rayon loop over solve_
 boundary SURVEY.md 8d and BASELINE.md section 2 define — the region batch in HOST memory (pinned arrays from avk_host_alloc, which is where the Rust side
 would build its FlatBatch) -> H2D of the caller's arrays as they are -> packing kernels -> solver kernels -> unpacking kernel -> D2H -> per-region
 records, per-variant decisions and the 288-counter tally in the caller's HOST arrays.  `value` = regions/s of the timed steps on that boundary.
-In the same JSON line:
+
+A plain run sets up, warms up, times the --steps calls, writes the outputs of the last timed call when --dump-outputs DIR is given, and prints the
+headline (metric, value, unit, ms_per_step, steps, config, ...).  With --full the same JSON line also carries everything below, each measured in
+runs of its own after the timed steps, and the outputs are checked bit for bit against the oracle:
   resident_value  regions/s of avk_compare_resident on the same batch already packed in HBM (no copies in the timed region): the kernels by themselves;
   roofline        algorithmic bytes of the batch / duration of all solver launches of a step (HIP events on the launch stream);
   cpu_baseline    the CPU restatement of the reference algorithm (oracle/) on the usable host cores, same outputs, >= 6 s of wall time;
@@ -66,6 +69,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed avk_compare_batch calls (host arrays -> host arrays)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the side legs, the resident leg and roofline, the parity gate against the oracle, the CPU "
+                                                         "baseline and the secondary workloads (a plain run reports the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed call as DIR/<name>.npy (float32 / float64; a fixed, seeded sample of the regions and calls)")
     ap.add_argument("--resident-steps", type=int, default=300, help="timed avk_compare_resident steps of the resident leg (0 = skip)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrinks the contigs (and the call counts with them); 1.0 = the named workload")
     ap.add_argument("--scaling", choices=["auto", "weak", "strong"], default="auto", help="auto = strong for N > 1 (one call set sharded over the ranks)")
@@ -90,7 +97,10 @@ def parse():
     ap.add_argument("--traffic-json", default=None,
                     help="PMC-derived HBM bytes per step collected with rocprofv3 --pmc in a builder-side run (default: the newest profiles/rNN_pmc_traffic.json); it is "
                          "reported only when the file names the build (avk_source_hash) of the library this process has loaded")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def supervise(args):
@@ -337,8 +347,10 @@ def main():
         hb = cmp_b
     wide = batch
     if not args.pageable:
-        hb, wide = (ctx.pinned_packed(hb) if form == "packed" else ctx.pinned_compact(hb)), ctx.pinned_batch(batch)
-        cmp_b = ctx.pinned_compact(cmp_b) if form == "packed" else hb
+        hb = ctx.pinned_packed(hb) if form == "packed" else ctx.pinned_compact(hb)
+        if args.full:  # the forms of the side legs
+            wide = ctx.pinned_batch(batch)
+            cmp_b = ctx.pinned_compact(cmp_b) if form == "packed" else hb
     # the results in the packed form (avk_result_batch::region_packed / var_packed: 8 B per region + 1 B per call, everything the wide arrays say) unless --wide-results
     res_form = False if args.wide_results else "only"
     # `value` is measured on the reference's WHOLE return value: solve_compare_region gives a CompareBenchmark with the region's GroupTypeMetrics
@@ -386,6 +398,58 @@ def main():
     call_stats = {"min": round(float(call_ms.min()), 3), "median": round(float(np.median(call_ms)), 3), "p95": round(float(np.percentile(call_ms, 95)), 3),
                   "max": round(float(call_ms.max()), 3)} if args.steps else None
     log("timed region: %d %s calls in %.3f s (%.2f ms per call; single calls %s)" % (args.steps, entry_name, elapsed, elapsed / max(args.steps, 1) * 1e3, call_stats))
+    ms_per_step = elapsed / args.steps * 1e3
+    value = total_regions * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, ctx, batch, res)
+        log("outputs of the last timed call: %.1f MB in %s" % (nbytes / 1e6, args.dump_outputs))
+
+    def emit(out):
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+
+    in_bytes = hb.nbytes()
+    out_bytes = int(sum(getattr(res, f).nbytes for f in ("status", "ed_h1", "ed_h2", "n_optima", "type_present", "var_expected", "var_observed", "var_class", "var_zyg",
+                                                         "region_packed", "var_packed") if getattr(res, f) is not None))
+    out = {
+        "metric": "compared regions/sec (whole node)",
+        "value": value,
+        "unit": "regions/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2] stand-in: HG002-scale SNV+indel compare, 24 contigs of GRCh38 primary lengths x %.3g (%d bases), "
+                               "%d regions in the job (%d on rank 0), %d calls on rank 0; seeds 20250103/4; one step = one %s call, region batch (%s flat form) and "
+                               "results in %s host memory (the reference loop's boundary, src/main.rs:251-268), H2D and D2H inside the timed region"
+                               % (args.scale, sum(c.size for c in contigs), n_job_regions if scaling == "strong" else total_regions, n_regions, batch.n_variants, entry_name, form,
+                                  "pageable" if args.pageable else "pinned (avk_host_alloc)"),
+                   "regions_per_gpu": n_regions, "max_branch_factor": cfg.max_branch_factor, "min_variant_gap": 50,
+                   "host_bytes_in_per_step": in_bytes, "host_bytes_out_per_step": out_bytes,
+                   "outputs_per_step": ("the reference's full return value (CompareBenchmark, compare_benchmark.rs:9-33): " if full_result else "") +
+                                       "per-region record (status, ed_h1, ed_h2, optima, types), per-variant decision (EA, OA, class, resolved zygosity), 288-counter tally" +
+                                       ("; per-region BASEPAIR groups, packed: one word per region, the groups of multi-type regions spilled (with the per-call decisions: the "
+                                        "region's whole 13 x 22 GroupTypeMetrics block, avk_group_metrics_from_compact)" if full_result else "; NO per-region groups (--records-only)") +
+                                       ("" if args.wide_results else "; regions and calls in the packed form of avk_result_batch (8 B + 1 B; avk_results_expand gives the wide arrays)"),
+                   "parallelism": ("regions of ONE call set sharded by hash(region_id) over %d GPU(s)" % world if scaling == "strong" else
+                                   "one call set per GPU on %d GPU(s)" % world) +
+                                  ", no data-path collective; one RCCL all-reduce of the job tally (288 x int64) inside the timed region"},
+        "call_ms": call_stats,  # this rank's single calls inside the timed region (value = all of them, barrier to barrier)
+        "process": ("PyTorch loaded: the process runs on the HIP runtime the wheel bundles (torch/lib/libamdhip64.so)" if use_torch else
+                    "one rank, PyTorch not loaded: the process runs on the system's HIP runtime, the one libaardvark_amd.so is linked with (--torch loads it as N > 1 ranks do)"),
+    }
+    if not args.full:  # the headline only: the side legs, the resident leg, the parity gate and the baselines are --full's
+        if rank == 0:
+            emit(out)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     job_tally = tally.cpu().numpy().copy() if use_torch else job_tally_host.astype(np.int64)
     res_ref_rp, res_ref_vp, res_ref_tally = (res.region_packed.copy(), res.var_packed.copy(), res.tally.copy()) if res_form else (None, None, None)
     got_boundary = res if args.wide_results else res.expanded(ctx.lib, batch)  # the outputs of the last timed call (the packed form: expanded on the host, outside the timed region)
@@ -664,8 +728,6 @@ def main():
         ctx.upload_reference(contigs)
 
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = total_regions * args.steps / elapsed
         alg_bytes = ctx.algorithmic_bytes(batch, with_groups=bool(full_result))  # per-region records, per-call decisions, the tally — and the per-region groups when the steps write them
         s_ms = float(np.mean(solver_ms))
         k_ms = float(np.mean(kernel_ms))
@@ -690,49 +752,16 @@ def main():
                                    % (loaded_hash, os.path.relpath(tj, ROOT)))
             except Exception as e:
                 traffic_src = "null: %s unreadable (%s)" % (os.path.relpath(tj, ROOT), e)
-        in_bytes = hb.nbytes()
         wide_bytes = sum(getattr(wide, f).nbytes for f in ("contig_idx", "start", "end", "t_off", "t_cnt", "q_off", "q_cnt", "var_pos", "var_type", "var_zyg", "var_raw_space",
                                                             "a0_off", "a0_len", "a1_off", "a1_len", "allele_bytes"))
-        out_bytes = int(sum(getattr(res, f).nbytes for f in ("status", "ed_h1", "ed_h2", "n_optima", "type_present", "var_expected", "var_observed", "var_class", "var_zyg",
-                                                             "region_packed", "var_packed") if getattr(res, f) is not None))
-        out = {
-            "metric": "compared regions/sec (whole node)",
-            "value": value,
-            "unit": "regions/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2] stand-in: HG002-scale SNV+indel compare, 24 contigs of GRCh38 primary lengths x %.3g (%d bases), "
-                                   "%d regions in the job (%d on rank 0), %d calls on rank 0; seeds 20250103/4; one step = one %s call, region batch (%s flat form) and "
-                                   "results in %s host memory (the reference loop's boundary, src/main.rs:251-268), H2D and D2H inside the timed region"
-                                   % (args.scale, sum(c.size for c in contigs), n_job_regions if scaling == "strong" else total_regions, n_regions, batch.n_variants, entry_name, form,
-                                      "pageable" if args.pageable else "pinned (avk_host_alloc)"),
-                       "regions_per_gpu": n_regions, "max_branch_factor": cfg.max_branch_factor, "min_variant_gap": 50,
-                       "host_bytes_in_per_step": in_bytes, "host_bytes_out_per_step": out_bytes,
-                       "outputs_per_step": ("the reference's full return value (CompareBenchmark, compare_benchmark.rs:9-33): " if full_result else "") +
-                                           "per-region record (status, ed_h1, ed_h2, optima, types), per-variant decision (EA, OA, class, resolved zygosity), 288-counter tally" +
-                                           ("; per-region BASEPAIR groups, packed: one word per region, the groups of multi-type regions spilled (with the per-call decisions: the "
-                                            "region's whole 13 x 22 GroupTypeMetrics block, avk_group_metrics_from_compact)" if full_result else "; NO per-region groups (--records-only)") +
-                                           ("" if args.wide_results else "; regions and calls in the packed form of avk_result_batch (8 B + 1 B; avk_results_expand gives the wide arrays)"),
-                       "parallelism": ("regions of ONE call set sharded by hash(region_id) over %d GPU(s)" % world if scaling == "strong" else
-                                       "one call set per GPU on %d GPU(s)" % world) +
-                                      ", no data-path collective; one RCCL all-reduce of the job tally (288 x int64) inside the timed region",
-                       "parity": parity, "workspace_tiers": tiers, "lane_kernel_regions": lane_regions, "wide_kernel_regions": wide_regions},
-            "call_ms": call_stats,  # this rank's single calls inside the timed region (value = all of them, barrier to barrier)
+        out["config"].update({"parity": parity, "workspace_tiers": tiers, "lane_kernel_regions": lane_regions, "wide_kernel_regions": wide_regions})
+        out.update({
             "resident_value": resident["value"] if resident else None,
             "resident": resident,
             "wide_results": wide_results_entry,
             "pipelined": pipelined_entry,
             "with_bp_groups": bp_entry,
             "records_only": records_entry,
-            "process": ("PyTorch loaded: the process runs on the HIP runtime the wheel bundles (torch/lib/libamdhip64.so)" if use_torch else
-                        "one rank, PyTorch not loaded: the process runs on the system's HIP runtime, the one libaardvark_amd.so is linked with (--torch loads it as N > 1 ranks do)"),
             "compact_soa": compact_entry,
             "wide_soa": {"value": total_regions * n_wide / wide_elapsed, "unit": "regions/s", "ms_per_step": wide_elapsed / n_wide * 1e3, "steps": n_wide, "host_bytes_in_per_step": wide_bytes,
                          "what": "the same boundary with the batch in the wide structure-of-arrays form (avk_region_batch through avk_compare_batch)"},
@@ -743,7 +772,7 @@ def main():
                          "bytes_per_region": alg_bytes / max(n_regions, 1),
                          "pcie": {"bytes_per_step": in_bytes + out_bytes, "achieved_GBs": (in_bytes + out_bytes) * (total_regions / max(n_regions, 1)) / world / (ms_per_step * 1e-3) / 1e9,
                                   "note": "the host boundary moves the caller's arrays over PCIe (57 GB/s each way measured on this pool, profiles/r03_pcie_probe.txt): its floor per step is bytes / 57 GB/s"}},
-        }
+        })
         if byte_compares:  # base comparisons the reference algorithm makes on this batch (counted by the oracle), at the rates above
             out["dwfa_byte_compares_per_region"] = byte_compares / max(n_regions, 1)
             out["dwfa_byte_compares_per_s"] = out["dwfa_byte_compares_per_region"] * value
@@ -784,11 +813,61 @@ def main():
             out["secondary"] = {"merge_3_callers": merge_sharded}
         if world == 1 and not args.no_secondary:
             out["secondary"] = secondary_legs(ctx, cfg, args, cpus, log, contigs, job_batch, ms_per_step, resident["ms_per_step"] if resident else None)
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
+        emit(out)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20250110
+DUMP_REGIONS = 1 << 17
+DUMP_CALLS = 1 << 19
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, ctx, batch, res):
+    """What the last timed call handed back, as DIR/<name>.npy in float32 (float64 for indices and the tally): the 288-counter tally whole, the per-region record,
+    the region's BASEPAIR groups and the per-call decisions on a fixed, seeded sample of regions and calls (region_index / call_index).  The packed words are read
+    through avk_results_expand, and a region's groups are listed as avk_group_metrics_from_compact reads them — joint group first, then one per call type in type
+    order — so that the spilled groups' order in bp_groups, which the kernels leave unspecified, does not show.  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    exp = res.expanded(ctx.lib, batch) if res.status is None else res
+    rng = np.random.default_rng(DUMP_SEED)
+    ri = np.sort(rng.choice(batch.n_regions, size=min(batch.n_regions, DUMP_REGIONS), replace=False))
+    vi = np.sort(rng.choice(batch.n_variants, size=min(batch.n_variants, DUMP_CALLS), replace=False))
+    arrays = {"tally": res.tally.astype(np.float64), "region_index": ri.astype(np.float64), "call_index": vi.astype(np.float64)}
+    for f, _ in res.WIDE_REGION:
+        arrays[f] = getattr(exp, f)[ri].astype(np.float32)
+    for f in res.WIDE_CALL:
+        arrays[f] = getattr(exp, f)[vi].astype(np.float32)
+    if getattr(res, "bp_packed", None) is not None:
+        types = np.zeros(ri.size, np.uint32)  # the call types of each sampled region, as a bit mask
+        for off, cnt in ((batch.t_off, batch.t_cnt), (batch.q_off, batch.q_cnt)):
+            o, c = off[ri].astype(np.int64), cnt[ri].astype(np.int64)
+            first = np.cumsum(c) - c
+            if c.sum() == 0:
+                continue
+            pos = np.repeat(o - first, c) + np.arange(int(c.sum()))
+            bits = np.left_shift(np.uint32(1), batch.var_type[pos].astype(np.uint32))
+            types[c > 0] |= np.bitwise_or.reduceat(bits, first[c > 0])
+        n_groups = 1 + np.bitwise_count(types).astype(np.int64)
+        word = res.bp_packed[ri]
+        owner = np.repeat(np.arange(ri.size), n_groups)
+        groups = np.stack([(word >> np.uint32(7 * i)) & np.uint32(0x7F) for i in range(4)], axis=1)[owner]  # a word stands for every group of its region
+        spilled = (word[owner] & np.uint32(0x80000000)) != 0
+        rows = (word[owner][spilled] & np.uint32(0x7FFFFFFF)).astype(np.int64) + (np.arange(owner.size) - np.repeat(np.cumsum(n_groups) - n_groups, n_groups))[spilled]
+        if rows.size and rows.max() >= int(res.bp_spilled[0]):
+            raise RuntimeError("a region's spilled BASEPAIR groups reach past bp_spilled")
+        groups[spilled] = res.bp_groups[rows]
+        arrays["bp_group_count"] = n_groups.astype(np.float32)
+        arrays["bp_groups"] = groups.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return total
 
 
 def secondary_legs(ctx, cfg, args, cpus, log, job_contigs=None, job_batch=None, headline_ms=None, headline_resident_ms=None):

@@ -4,7 +4,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/pmc_pass
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --pmc "$@" -d "$OUT" -o p -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-secondary --resident-steps 3 --no-supervisor > "$OUT/log.txt" 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc "$@" -d "$OUT" -o p -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-secondary --resident-steps 3 --no-supervisor > "$OUT/log.txt" 2>&1
 echo "rc $?"
 python3 - "$OUT" <<'PY'
 import glob, sqlite3, sys
