@@ -110,6 +110,25 @@ class AvkPackedBatch(C.Structure):
     ]
 
 
+class AvkPackedEscapes(C.Structure):
+    _fields_ = [
+        ("first_region", C.c_uint64),
+        ("first_call", C.c_uint64),
+        ("first_slot", C.c_uint64),
+        ("n_esc_regions", C.c_uint64),
+        ("esc_region", _p(C.c_uint64)),
+        ("esc_len", _p(C.c_uint32)),
+        ("n_esc_slots", C.c_uint64),
+        ("esc_slot", _p(C.c_uint64)),
+        ("esc_cnt", _p(C.c_uint32)),
+        ("n_esc_calls", C.c_uint64),
+        ("esc_call", _p(C.c_uint64)),
+        ("esc_rel_pos", _p(C.c_uint32)),
+        ("esc_a0_len", _p(C.c_uint32)),
+        ("esc_a1_len", _p(C.c_uint32)),
+    ]
+
+
 class AvkCompareConfig(C.Structure):
     _fields_ = [
         ("max_branch_factor", C.c_uint32),
@@ -312,6 +331,83 @@ class CompactBatch:
         return b
 
 
+class PackedEscapes:
+    """The escapes of a packed batch (avk_packed_escapes): three sorted lists of overrides for the regions, count slots and calls whose values do not fit the
+    narrow fields.  The listed indices carry the bases first_region / first_slot / first_call, so a slice of a batch is a slice of the lists plus new bases."""
+
+    FIELDS = ("esc_region", "esc_len", "esc_slot", "esc_cnt", "esc_call", "esc_rel_pos", "esc_a0_len", "esc_a1_len")
+    DTYPES = (np.uint64, np.uint32, np.uint64, np.uint32, np.uint64, np.uint32, np.uint32, np.uint32)
+
+    def __init__(self, first_region=0, first_call=0, first_slot=0, **arrays):
+        self.first_region, self.first_call, self.first_slot = int(first_region), int(first_call), int(first_slot)
+        for name, dt in zip(self.FIELDS, self.DTYPES):
+            a = arrays.get(name)
+            setattr(self, name, np.zeros(0, dt) if a is None else np.ascontiguousarray(a, dtype=dt))
+        assert self.esc_region.size == self.esc_len.size and self.esc_slot.size == self.esc_cnt.size
+        assert self.esc_call.size == self.esc_rel_pos.size == self.esc_a0_len.size == self.esc_a1_len.size
+
+    @classmethod
+    def build(cls, length, counts, rel, a0_len, a1_len):
+        """the lists for wide per-region lengths, per-slot counts and per-call (relative position, allele lengths): whatever does not fit 16 / 8 / 16, 8, 8 bits"""
+        er = np.flatnonzero(length >= 65536)
+        es = np.flatnonzero(counts >= 256)
+        ec = np.flatnonzero((rel >= 65536) | (a0_len >= 256) | (a1_len >= 256))
+        return cls(esc_region=er, esc_len=length[er], esc_slot=es, esc_cnt=counts[es], esc_call=ec, esc_rel_pos=rel[ec], esc_a0_len=a0_len[ec], esc_a1_len=a1_len[ec])
+
+    def empty(self):
+        return self.esc_region.size == 0 and self.esc_slot.size == 0 and self.esc_call.size == 0
+
+    def nbytes(self):
+        return sum(getattr(self, f).nbytes for f in self.FIELDS)
+
+    def apply(self, length, counts, rel, a0_len, a1_len):
+        """the lists written over wide (int64) copies of the narrow arrays, in place"""
+        length[(self.esc_region - np.uint64(self.first_region)).astype(np.int64)] = self.esc_len
+        counts[(self.esc_slot - np.uint64(self.first_slot)).astype(np.int64)] = self.esc_cnt
+        v = (self.esc_call - np.uint64(self.first_call)).astype(np.int64)
+        rel[v], a0_len[v], a1_len[v] = self.esc_rel_pos, self.esc_a0_len, self.esc_a1_len
+
+    def slice(self, r0, r1, s0, s1, v0, v1):
+        """the escapes of regions [r0, r1), count slots [s0, s1) and calls [v0, v1) of the batch these belong to: ranges of the same arrays, new bases"""
+        cut = lambda idx, first, lo, hi: (int(np.searchsorted(idx, np.uint64(first + lo))), int(np.searchsorted(idx, np.uint64(first + hi))))
+        a, b = cut(self.esc_region, self.first_region, r0, r1)
+        c, d = cut(self.esc_slot, self.first_slot, s0, s1)
+        e, f = cut(self.esc_call, self.first_call, v0, v1)
+        return PackedEscapes(self.first_region + r0, self.first_call + v0, self.first_slot + s0, esc_region=self.esc_region[a:b], esc_len=self.esc_len[a:b],
+                             esc_slot=self.esc_slot[c:d], esc_cnt=self.esc_cnt[c:d], esc_call=self.esc_call[e:f], esc_rel_pos=self.esc_rel_pos[e:f],
+                             esc_a0_len=self.esc_a0_len[e:f], esc_a1_len=self.esc_a1_len[e:f])
+
+    def pinned(self, host_array):
+        """a copy whose lists live in memory handed out by `host_array(shape, dtype)` (Context.host_array)"""
+        out = PackedEscapes(self.first_region, self.first_call, self.first_slot)
+        for f in self.FIELDS:
+            a = getattr(self, f)
+            b = host_array((max(a.size, 1),), a.dtype)[:a.size]
+            b[...] = a
+            setattr(out, f, b)
+        return out
+
+    def c_struct(self):
+        e = AvkPackedEscapes()
+        e.first_region, e.first_call, e.first_slot = self.first_region, self.first_call, self.first_slot
+        e.n_esc_regions, e.n_esc_slots, e.n_esc_calls = int(self.esc_region.size), int(self.esc_slot.size), int(self.esc_call.size)
+        for name, ct in (("esc_region", C.c_uint64), ("esc_len", C.c_uint32), ("esc_slot", C.c_uint64), ("esc_cnt", C.c_uint32), ("esc_call", C.c_uint64),
+                         ("esc_rel_pos", C.c_uint32), ("esc_a0_len", C.c_uint32), ("esc_a1_len", C.c_uint32)):
+            a = getattr(self, name)
+            if a.size:
+                setattr(e, name, _ptr(a, ct))
+        return e
+
+    @classmethod
+    def from_c(cls, e):
+        """a copy of the lists of an avk_packed_escapes (a shard's)"""
+        take = lambda ptr, m, dt: np.ctypeslib.as_array(ptr, shape=(max(m, 1),))[:m].astype(dt).copy() if ptr and m else np.zeros(0, dt)
+        nr, ns, nc = int(e.n_esc_regions), int(e.n_esc_slots), int(e.n_esc_calls)
+        return cls(int(e.first_region), int(e.first_call), int(e.first_slot), esc_region=take(e.esc_region, nr, np.uint64), esc_len=take(e.esc_len, nr, np.uint32),
+                   esc_slot=take(e.esc_slot, ns, np.uint64), esc_cnt=take(e.esc_cnt, ns, np.uint32), esc_call=take(e.esc_call, nc, np.uint64),
+                   esc_rel_pos=take(e.esc_rel_pos, nc, np.uint32), esc_a0_len=take(e.esc_a0_len, nc, np.uint32), esc_a1_len=take(e.esc_a1_len, nc, np.uint32))
+
+
 class PackedBatch:
     """The same batch in the library's packed form (avk_packed_batch): 10 bytes per region, 5 per call plus the allele bytes; every offset is implied by
     order.  `from_compact` checks the constraints (calls and alleles back to back in region / call order, narrow fields wide enough)."""
@@ -319,15 +415,20 @@ class PackedBatch:
     FIELDS = ("contig_idx", "start", "len", "t_cnt", "q_cnt", "var_rel_pos", "var_type_zyg", "a0_len", "a1_len", "var_raw_space", "allele_bytes")
     DTYPES = (np.uint16, np.uint32, np.uint16, np.uint8, np.uint8, np.uint16, np.uint8, np.uint8, np.uint8, np.uint32, np.uint8)
 
-    def __init__(self, **arrays):
+    def __init__(self, escapes=None, **arrays):
         for name, dt in zip(self.FIELDS, self.DTYPES):
             a = arrays.get(name)
             setattr(self, name, None if a is None else np.ascontiguousarray(a, dtype=dt))
         self.n_regions = int(self.start.size)
         self.n_variants = int(self.var_rel_pos.size)
+        self.escapes = escapes  # a PackedEscapes (possibly empty), or None: the batch as it was before escapes existed
 
     @classmethod
-    def from_compact(cls, cb):
+    def from_compact(cls, cb, escapes=False):
+        """escapes=True: values that do not fit the narrow fields go to the batch's PackedEscapes instead of raising (what is left to raise for: calls or
+        alleles that are not back to back, a call in front of its region's start, more than 65,535 contigs)"""
+        if escapes:
+            return cls._from_compact_escaped(cb)
         n, nv = cb.n_regions, cb.n_variants
         cnt = cb.t_cnt.astype(np.int64) + cb.q_cnt
         voff = np.concatenate([[0], np.cumsum(cnt)])
@@ -346,8 +447,57 @@ class PackedBatch:
         return cls(contig_idx=cb.contig_idx, start=cb.start, len=cb.len, t_cnt=cb.t_cnt, q_cnt=cb.q_cnt, var_rel_pos=rel, var_type_zyg=cb.var_type_zyg, a0_len=cb.a0_len,
                    a1_len=cb.a1_len, var_raw_space=cb.var_raw_space, allele_bytes=cb.allele_bytes)
 
+    @classmethod
+    def _from_compact_escaped(cls, cb):
+        n, nv = cb.n_regions, cb.n_variants
+        cnt = cb.t_cnt.astype(np.int64) + cb.q_cnt
+        voff = np.concatenate([[0], np.cumsum(cnt)])
+        a0, a1 = cb.a0_len.astype(np.int64), cb.a1_len.astype(np.int64)
+        aoff = np.concatenate([[0], np.cumsum(a0 + a1)])
+        ok = (np.array_equal(cb.v_off, voff[:-1]) and int(voff[-1]) == nv and np.array_equal(cb.a_off, aoff[:-1]) and (nv == 0 or int(aoff[-1]) == cb.allele_bytes.size) and
+              (cb.contig_idx is None or n == 0 or int(cb.contig_idx.max()) < 65536))
+        rel = None
+        if ok:
+            rel = cb.var_pos.astype(np.int64) - cb.start.astype(np.int64)[np.repeat(np.arange(n), cnt)]
+            ok = nv == 0 or int(rel.min()) >= 0
+        if not ok:
+            raise ValueError("the batch does not satisfy the constraints of the packed form with escapes (include/aardvark_amd.h: avk_packed_escapes)")
+        length = cb.len.astype(np.int64)
+        slots = np.stack([cb.t_cnt.astype(np.int64), cb.q_cnt.astype(np.int64)], axis=1).reshape(-1) if n else np.zeros(0, np.int64)
+        esc = PackedEscapes.build(length, slots, rel, a0, a1)
+        # a listed entry's narrow fields are written as 0
+        length[esc.esc_region.astype(np.int64)] = 0
+        slots[esc.esc_slot.astype(np.int64)] = 0
+        v = esc.esc_call.astype(np.int64)
+        rel[v], a0[v], a1[v] = 0, 0, 0
+        return cls(escapes=esc, contig_idx=cb.contig_idx, start=cb.start, len=length, t_cnt=slots[0::2], q_cnt=slots[1::2], var_rel_pos=rel, var_type_zyg=cb.var_type_zyg,
+                   a0_len=a0, a1_len=a1, var_raw_space=cb.var_raw_space, allele_bytes=cb.allele_bytes)
+
+    def _wide_fields(self):
+        """(len, count slots, relative positions, a0_len, a1_len) as int64 with the escapes applied"""
+        length, rel, a0, a1 = self.len.astype(np.int64), self.var_rel_pos.astype(np.int64), self.a0_len.astype(np.int64), self.a1_len.astype(np.int64)
+        slots = np.stack([self.t_cnt.astype(np.int64), self.q_cnt.astype(np.int64)], axis=1).reshape(-1) if self.n_regions else np.zeros(0, np.int64)
+        if self.escapes is not None:
+            self.escapes.apply(length, slots, rel, a0, a1)
+        return length, slots, rel, a0, a1
+
+    def to_compact(self):
+        """undoes the packing: the CompactBatch this batch (with its escapes) stands for"""
+        length, slots, rel, a0, a1 = self._wide_fields()
+        tc, qc = slots[0::2], slots[1::2]
+        cnt = tc + qc
+        voff = np.concatenate([[0], np.cumsum(cnt)])[:-1]
+        aoff = np.concatenate([[0], np.cumsum(a0 + a1)])[:-1]
+        pos = self.start.astype(np.int64)[np.repeat(np.arange(self.n_regions), cnt)] + rel
+        return CompactBatch(contig_idx=self.contig_idx, start=self.start, len=length, v_off=voff, t_cnt=tc, q_cnt=qc, var_pos=pos, var_type_zyg=self.var_type_zyg, a_off=aoff,
+                            a0_len=a0, a1_len=a1, var_raw_space=self.var_raw_space, allele_bytes=self.allele_bytes)
+
     def nbytes(self):
-        return sum(getattr(self, f).nbytes for f in self.FIELDS if getattr(self, f) is not None)
+        return sum(getattr(self, f).nbytes for f in self.FIELDS if getattr(self, f) is not None) + (self.escapes.nbytes() if self.escapes is not None else 0)
+
+    def c_escapes(self):
+        """the avk_packed_escapes to hand in with c_struct(), or None when the batch lists nothing (the entry points without escapes then serve)"""
+        return None if self.escapes is None or self.escapes.empty() else self.escapes.c_struct()
 
     def split(self, n_parts):
         """the batch as `n_parts` batches of consecutive regions (cut at contig boundaries where there are enough contigs): a job handed over piece by piece"""
@@ -359,15 +509,21 @@ class PackedBatch:
                 for i in range(1, n_parts):
                     cuts[i] = int(starts[np.argmin(np.abs(starts - cuts[i]))])
         cuts = sorted(set(cuts))
-        voff = np.concatenate([[0], np.cumsum(self.t_cnt.astype(np.int64) + self.q_cnt)])
-        aoff = np.concatenate([[0], np.cumsum(self.a0_len.astype(np.int64) + self.a1_len)])
+        if self.escapes is not None:
+            _, slots, _, a0, a1 = self._wide_fields()
+            voff = np.concatenate([[0], np.cumsum(slots[0::2] + slots[1::2])])
+            aoff = np.concatenate([[0], np.cumsum(a0 + a1)])
+        else:
+            voff = np.concatenate([[0], np.cumsum(self.t_cnt.astype(np.int64) + self.q_cnt)])
+            aoff = np.concatenate([[0], np.cumsum(self.a0_len.astype(np.int64) + self.a1_len)])
         parts = []
         for r0, r1 in zip(cuts[:-1], cuts[1:]):
             v0, v1 = int(voff[r0]), int(voff[r1])
             a0, a1 = int(aoff[v0]), int(aoff[v1])
             cut = {"contig_idx": (r0, r1), "start": (r0, r1), "len": (r0, r1), "t_cnt": (r0, r1), "q_cnt": (r0, r1), "var_rel_pos": (v0, v1), "var_type_zyg": (v0, v1),
                    "a0_len": (v0, v1), "a1_len": (v0, v1), "var_raw_space": (v0, v1), "allele_bytes": (a0, a1)}
-            parts.append(PackedBatch(**{f: (None if getattr(self, f) is None else getattr(self, f)[cut[f][0]:cut[f][1]]) for f in self.FIELDS}))
+            esc = None if self.escapes is None else self.escapes.slice(r0, r1, 2 * r0, 2 * r1, v0, v1)
+            parts.append(PackedBatch(escapes=esc, **{f: (None if getattr(self, f) is None else getattr(self, f)[cut[f][0]:cut[f][1]]) for f in self.FIELDS}))
         return parts
 
     def c_struct(self):

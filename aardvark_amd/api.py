@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkRegionBatch, AvkResultBatch, CompactBatch, PackedBatch, RegionBatch,
-                   ResultBatch)
+from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkResultBatch, CompactBatch, PackedBatch,
+                   RegionBatch, ResultBatch)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -64,6 +64,10 @@ def load_library():
         lib.avk_compare_packed_submit.argtypes = [vp, C.POINTER(AvkPackedBatch), C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), C.POINTER(vp)]
         lib.avk_wait.argtypes = [vp, vp]
     lib.avk_batch_upload_packed.argtypes = [vp, C.POINTER(AvkPackedBatch), C.POINTER(vp)]
+    esc = C.POINTER(AvkPackedEscapes)  # packed batches with escapes (avk_packed_escapes)
+    lib.avk_compare_packed_esc.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch)]
+    lib.avk_compare_packed_submit_esc.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), C.POINTER(vp)]
+    lib.avk_batch_upload_packed_esc.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, C.POINTER(vp)]
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
     lib.avk_results_download.argtypes = [vp, vp, C.POINTER(AvkResultBatch)]
     lib.avk_batch_free.argtypes = [vp, vp]
@@ -112,6 +116,13 @@ class ResidentBatch:
         self.ctx, self.batch = ctx, batch
         self.handle = C.c_void_p()
         cb = batch.c_struct()
+        if isinstance(batch, PackedBatch):  # (with its escapes when it has any)
+            esc = batch.c_escapes()
+            if esc is None:
+                ctx._check(ctx.lib.avk_batch_upload_packed(ctx.handle, C.byref(cb), C.byref(self.handle)))
+            else:
+                ctx._check(ctx.lib.avk_batch_upload_packed_esc(ctx.handle, C.byref(cb), C.byref(esc), C.byref(self.handle)))
+            return
         ctx._check(ctx.lib.avk_batch_upload(ctx.handle, C.byref(cb), C.byref(self.handle)))
 
     def free(self):
@@ -223,14 +234,18 @@ class Context:
             out = self.host_array(a.shape, a.dtype)
             out[...] = a
             return out
-        return PackedBatch(**{f: pin(getattr(pbatch, f)) for f in PackedBatch.FIELDS})
+        esc = None if pbatch.escapes is None else pbatch.escapes.pinned(self.host_array)
+        return PackedBatch(escapes=esc, **{f: pin(getattr(pbatch, f)) for f in PackedBatch.FIELDS})
 
     def solve_packed(self, pbatch, config=None, res=None):
         """avk_compare_packed: solve_compare_region for every region of a batch in the packed form -> ResultBatch (indexed like the packed arrays)"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
-        pb, cfg, ro = pbatch.c_struct(), config.c_struct(), res.c_struct()
-        self._check(self.lib.avk_compare_packed(self.handle, C.byref(pb), C.byref(cfg), C.byref(ro)))
+        pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
+        if esc is None:
+            self._check(self.lib.avk_compare_packed(self.handle, C.byref(pb), C.byref(cfg), C.byref(ro)))
+        else:
+            self._check(self.lib.avk_compare_packed_esc(self.handle, C.byref(pb), C.byref(esc), C.byref(cfg), C.byref(ro)))
         return res
 
     def submit_packed(self, pbatch, config=None, res=None):
@@ -238,10 +253,13 @@ class Context:
         `pbatch` and `res` must live in pinned memory (pinned_packed / pinned_results) for the copies to overlap anything; at most four tickets are in flight."""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
-        pb, cfg, ro = pbatch.c_struct(), config.c_struct(), res.c_struct()
+        pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
         handle = C.c_void_p()
-        self._check(self.lib.avk_compare_packed_submit(self.handle, C.byref(pb), C.byref(cfg), C.byref(ro), C.byref(handle)))
-        return Ticket(self, handle, res, (pbatch, pb, ro))
+        if esc is None:
+            self._check(self.lib.avk_compare_packed_submit(self.handle, C.byref(pb), C.byref(cfg), C.byref(ro), C.byref(handle)))
+        else:
+            self._check(self.lib.avk_compare_packed_submit_esc(self.handle, C.byref(pb), C.byref(esc), C.byref(cfg), C.byref(ro), C.byref(handle)))
+        return Ticket(self, handle, res, (pbatch, pb, ro, esc))
 
     def solve_compact(self, cbatch, config=None, res=None):
         """avk_compare_compact: solve_compare_region for every region of a batch in the compact form -> ResultBatch (indexed like the compact arrays)"""
@@ -304,6 +322,7 @@ class Context:
 
     # --- resident form (benchmarks, pipelines that keep batches in HBM)
     def upload(self, batch):
+        """a RegionBatch, or a PackedBatch (with its escapes) -> ResidentBatch"""
         return ResidentBatch(self, batch)
 
     def compare_resident(self, rb, config=None, tally_dev_ptr=None):

@@ -283,6 +283,103 @@ AVK_DEV void dp_widen_packed_multi(const DpPackedMulti &c, u64 i) { /* one lane:
     }
 }
 
+/* ---- packed batches with ESCAPES (avk_packed_escapes): the few regions, counts and calls whose values do not fit the narrow fields come from three sorted
+ * lists.  A listed entry's narrow field is 0, so the two prefix sums over the narrow arrays (avk_ps_*) run unchanged and lack exactly the listed values in front of
+ * an entry: a lane finds the number p of listed entries before its own by a binary search of the sorted list (a few thousand words at most, shared by every lane:
+ * it stays in L2), adds the list's own exclusive sum before[p], and learns from list[p] whether its own entry is listed — one search answers both questions, no
+ * bitmap to clear and scatter into, no device copy of the narrow arrays.  Only the widening route reads these: a batch without escapes never comes here. */
+struct DpEsc {
+    const u64 *region, *slot, *call;        /* ascending; indices carry the bases below */
+    const u32 *len, *cnt, *rel, *a0, *a1;
+    const u64 *cnt_before, *bytes_before;   /* [n_slots + 1], [n_calls + 1]: exclusive sums of cnt, of a0 + a1 */
+    u64 n_regions, n_slots, n_calls, first_region, first_slot, first_call;
+};
+AVK_DEV u64 dp_esc_lower(const u64 *list, u64 n, u64 key) { /* the first p with list[p] >= key */
+    u64 lo = 0, hi = n;
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (list[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+/* the positions of calls [vo, vo + calls): one walk along the call list from the first listed call at or behind vo */
+AVK_DEV void dp_esc_positions(const DpEsc &e, const uint16_t *rel_pos, u64 *w_pos, u64 st, u64 vo, u64 calls, u64 n_variants) {
+    u64 pc = dp_esc_lower(e.call, e.n_calls, e.first_call + vo);
+    for (u64 q = 0; q < calls && vo + q < n_variants; ++q) {
+        const u64 v = vo + q;
+        u64 rel = rel_pos[v];
+        if (pc < e.n_calls && e.call[pc] == e.first_call + v) rel = e.rel[pc++];
+        w_pos[v] = st + rel;
+    }
+}
+AVK_DEV void dp_esc_call(const DpEsc &e, const u8 *a0_len, const u8 *a1_len, const u64 *a_off, u64 i, u32 &l0, u32 &l1, u64 &ao) {
+    const u64 pc = dp_esc_lower(e.call, e.n_calls, e.first_call + i);
+    const bool hit = pc < e.n_calls && e.call[pc] == e.first_call + i;
+    l0 = hit ? e.a0[pc] : (u32)a0_len[i];
+    l1 = hit ? e.a1[pc] : (u32)a1_len[i];
+    ao = a_off[i] + e.bytes_before[pc];
+}
+/* call i of a packed form (compare or multi) with escapes into the wide call arrays */
+template <class Form>
+AVK_DEV void dp_esc_widen_call(const Form &c, const DpEsc &e, u64 i) {
+    u32 l0, l1;
+    u64 ao;
+    dp_esc_call(e, c.a0_len, c.a1_len, c.a_off, i, l0, l1, ao);
+    const u32 tz = c.var_type_zyg[i];
+    c.w_a0_off[i] = ao;
+    c.w_a1_off[i] = ao + l0;
+    c.w_a0_len[i] = l0;
+    c.w_a1_len[i] = l1;
+    if (c.w_raw) c.w_raw[i] = c.var_raw ? c.var_raw[i] : (l0 > l1 ? l0 : l1);
+    c.w_type[i] = (u8)(tz & 15u);
+    c.w_zyg[i] = (u8)(tz >> 4);
+}
+AVK_DEV void dp_widen_packed_esc(const DpPacked &c, const DpEsc &e, u64 i) { /* dp_widen_packed with the lists: one lane, region i and call i */
+    if (i < c.n_regions) {
+        const u64 st = c.start[i], key = e.first_slot + 2 * i;
+        u64 ps = dp_esc_lower(e.slot, e.n_slots, key);
+        const u64 vo = c.v_off[i] + e.cnt_before[ps];
+        u32 tc = c.t_cnt[i], qc = c.q_cnt[i];
+        if (ps < e.n_slots && e.slot[ps] == key) tc = e.cnt[ps++];
+        if (ps < e.n_slots && e.slot[ps] == key + 1) qc = e.cnt[ps];
+        const u64 pr = dp_esc_lower(e.region, e.n_regions, e.first_region + i);
+        const u64 len = pr < e.n_regions && e.region[pr] == e.first_region + i ? (u64)e.len[pr] : (u64)c.len[i];
+        if (c.w_contig) c.w_contig[i] = c.contig_idx[i];
+        c.w_start[i] = st;
+        c.w_end[i] = st + len;
+        c.w_t_off[i] = vo;
+        c.w_q_off[i] = vo + tc;
+        c.w_t_cnt[i] = tc;
+        c.w_q_cnt[i] = qc;
+        dp_esc_positions(e, c.rel_pos, c.w_pos, st, vo, (u64)tc + qc, c.n_variants);
+    }
+    if (i < c.n_variants) dp_esc_widen_call(c, e, i);
+}
+/* the multi form: c.in_off holds the running sum over the NARROW counts; the true offsets of a region's inputs are written to w_in_off */
+AVK_DEV void dp_widen_packed_multi_esc(const DpPackedMulti &c, const DpEsc &e, u64 *w_in_off, u64 i) {
+    if (i < c.n_multi) {
+        const u64 st = c.start[i], key = e.first_slot + i * c.k;
+        u64 ps = dp_esc_lower(e.slot, e.n_slots, key);
+        const u64 vo = c.in_off[i * c.k] + e.cnt_before[ps];
+        const u64 pr = dp_esc_lower(e.region, e.n_regions, e.first_region + i);
+        const u64 len = pr < e.n_regions && e.region[pr] == e.first_region + i ? (u64)e.len[pr] : (u64)c.len[i];
+        if (c.w_contig) c.w_contig[i] = c.contig_idx[i];
+        c.w_start[i] = st;
+        c.w_end[i] = st + len;
+        u64 run = vo;
+        for (u32 j = 0; j < c.k; ++j) {
+            u32 cnt = c.in_cnt[i * c.k + j];
+            if (ps < e.n_slots && e.slot[ps] == key + j) cnt = e.cnt[ps++];
+            w_in_off[i * c.k + j] = run;
+            c.w_in_cnt[i * c.k + j] = cnt;
+            run += cnt;
+        }
+        dp_esc_positions(e, c.rel_pos, c.w_pos, st, vo, run - vo, c.n_variants);
+    }
+    if (i < c.n_variants) dp_esc_widen_call(c, e, i);
+}
+
 /* ---- the merge path on the device (solve_merge_region, src/merge_solver.rs:110-200) ------------------------------------------------------------------- */
 /* a batch of MultiRegions (avk_multi_batch) as one CompareRegion-shaped item per input pair (i < j, lexicographic): input i plays the truth side */
 struct DpPairs {

@@ -16,6 +16,41 @@ __global__ void __launch_bounds__(256) avk_dp_merge_classify_kernel(dpk::DpMerge
 __global__ void __launch_bounds__(256) avk_dp_widen_kernel(dpk::DpCompact c) { dpk::dp_widen(c, (uint64_t)blockIdx.x * 256u + threadIdx.x); }
 __global__ void __launch_bounds__(256) avk_dp_widen_packed_kernel(dpk::DpPacked c) { dpk::dp_widen_packed(c, (uint64_t)blockIdx.x * 256u + threadIdx.x); }
 __global__ void __launch_bounds__(256) avk_dp_widen_packed_multi_kernel(dpk::DpPackedMulti c) { dpk::dp_widen_packed_multi(c, (uint64_t)blockIdx.x * 256u + threadIdx.x); }
+__global__ void __launch_bounds__(256) avk_dp_widen_packed_esc_kernel(dpk::DpPacked c, dpk::DpEsc e) { dpk::dp_widen_packed_esc(c, e, (uint64_t)blockIdx.x * 256u + threadIdx.x); }
+__global__ void __launch_bounds__(256) avk_dp_widen_packed_multi_esc_kernel(dpk::DpPackedMulti c, dpk::DpEsc e, uint64_t *w_in_off) {
+    dpk::dp_widen_packed_multi_esc(c, e, w_in_off, (uint64_t)blockIdx.x * 256u + threadIdx.x);
+}
+/* One escape list of a packed batch (avk_packed_escapes), one workgroup: checks that idx[] is strictly ascending inside [lo, hi) — *err is set otherwise —, writes
+ * the exclusive sums of a[i] + b[i] to before[0 .. n] (b may be NULL; a NULL: a list without values to sum) and adds their total to *total: the sums over the narrow
+ * arrays count a listed entry as 0, this is what they lack.  The lists are sparse (a genome's long alleles: thousands), so one workgroup's chunks of 1024 do. */
+__global__ void __launch_bounds__(1024) avk_esc_scan_kernel(const uint64_t *idx, const uint32_t *a, const uint32_t *b, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *before,
+                                                            uint64_t *total, uint64_t *err) {
+    __shared__ uint64_t part[1024];
+    __shared__ uint64_t carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (uint64_t base = 0; base < n; base += 1024u) {
+        const uint64_t i = base + threadIdx.x;
+        if (i < n && (idx[i] < lo || idx[i] >= hi || (i && idx[i - 1] >= idx[i]))) *err = 1; /* (every writer stores the same word) */
+        const uint64_t x = i < n && a ? (uint64_t)a[i] + (b ? (uint64_t)b[i] : 0ull) : 0ull;
+        part[threadIdx.x] = x;
+        __syncthreads();
+        for (uint32_t st = 1; st < 1024u; st <<= 1) { /* Hillis-Steele inclusive scan */
+            const uint64_t y = threadIdx.x >= st ? part[threadIdx.x - st] : 0ull;
+            __syncthreads();
+            part[threadIdx.x] += y;
+            __syncthreads();
+        }
+        if (i < n && before) before[i] = carry + part[threadIdx.x] - x;
+        __syncthreads();
+        if (threadIdx.x == 1023u) carry += part[1023];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (before) before[n] = carry;
+        if (total) *total += carry;
+    }
+}
 /* Exclusive prefix sum of a[i] + b[i] over n byte pairs (the packed form's offsets: calls per region, allele bytes per call): per-workgroup sums of 4096
  * elements, a one-workgroup scan of those sums, then every workgroup scans its own 4096 again from its base.  16 elements per thread, waves and workgroup
  * combined through LDS. */
@@ -832,13 +867,73 @@ struct PackedOnDevice {
     uint32_t *start, *raw;
     uint16_t *len, *contig, *rel_pos;
     hipEvent_t ready;
+    /* the escape lists of the batch (avk_packed_escapes), copied with the rest; NULL without escapes */
+    uint64_t *esc_region, *esc_slot, *esc_call;
+    uint32_t *esc_len, *esc_cnt, *esc_rel, *esc_a0, *esc_a1;
 };
+/* an avk_packed_escapes that lists something, with every array it needs */
+static inline bool esc_present(const avk_packed_escapes *e) { return e && (e->n_esc_regions || e->n_esc_slots || e->n_esc_calls); }
+static inline bool esc_arrays_ok(const avk_packed_escapes *e) {
+    if (!esc_present(e)) return true;
+    return (!e->n_esc_regions || (e->esc_region && e->esc_len)) && (!e->n_esc_slots || (e->esc_slot && e->esc_cnt)) &&
+           (!e->n_esc_calls || (e->esc_call && e->esc_rel_pos && e->esc_a0_len && e->esc_a1_len));
+}
+/* host: the narrow per-entry fields of a packed batch with its escapes applied — for the host-side utilities (shards, merge counts, the merge path's host
+ * fallback).  cnt[] has one entry per count slot: 2r / 2r + 1 = t_cnt / q_cnt of region r (compare form, cnt_b given), or in_cnt as it is (multi form, cnt_b NULL).
+ * false: a list is not ascending or names an entry outside the batch. */
+struct PackedWideHost {
+    std::vector<uint32_t> len, cnt, rel, a0, a1;
+};
+static bool packed_widen_host(const uint16_t *len, uint64_t n, const uint8_t *cnt_a, const uint8_t *cnt_b, uint64_t n_slots, const uint16_t *rel, const uint8_t *a0, const uint8_t *a1,
+                              uint64_t nv, const avk_packed_escapes *esc, PackedWideHost &w) {
+    w.len.resize(n + 1), w.cnt.resize(n_slots + 1), w.rel.resize(nv + 1), w.a0.resize(nv + 1), w.a1.resize(nv + 1);
+    for (uint64_t r = 0; r < n; ++r) w.len[r] = len[r];
+    if (cnt_b)
+        for (uint64_t r = 0; r < n; ++r) w.cnt[2 * r] = cnt_a[r], w.cnt[2 * r + 1] = cnt_b[r];
+    else
+        for (uint64_t i = 0; i < n_slots; ++i) w.cnt[i] = cnt_a[i];
+    for (uint64_t v = 0; v < nv; ++v) w.rel[v] = rel[v], w.a0[v] = a0[v], w.a1[v] = a1[v];
+    if (!esc_present(esc)) return true;
+    if (!esc_arrays_ok(esc)) return false;
+    auto listed = [](const uint64_t *idx, uint64_t p, uint64_t first, uint64_t count) { return idx[p] >= first && idx[p] - first < count && (p == 0 || idx[p - 1] < idx[p]); };
+    for (uint64_t p = 0; p < esc->n_esc_regions; ++p) {
+        if (!listed(esc->esc_region, p, esc->first_region, n)) return false;
+        w.len[esc->esc_region[p] - esc->first_region] = esc->esc_len[p];
+    }
+    for (uint64_t p = 0; p < esc->n_esc_slots; ++p) {
+        if (!listed(esc->esc_slot, p, esc->first_slot, n_slots)) return false;
+        w.cnt[esc->esc_slot[p] - esc->first_slot] = esc->esc_cnt[p];
+    }
+    for (uint64_t p = 0; p < esc->n_esc_calls; ++p) {
+        if (!listed(esc->esc_call, p, esc->first_call, nv)) return false;
+        const uint64_t v = esc->esc_call[p] - esc->first_call;
+        w.rel[v] = esc->esc_rel_pos[p], w.a0[v] = esc->esc_a0_len[p], w.a1[v] = esc->esc_a1_len[p];
+    }
+    return true;
+}
+/* allele offsets and lengths of a packed batch's calls on the host, escapes honoured (only made for the few calls whose edit distance is left to the host) */
+static void packed_host_alleles(const uint8_t *l0, const uint8_t *l1, uint64_t nv, const avk_packed_escapes *esc, std::vector<uint64_t> &aoff, std::vector<uint32_t> &w0,
+                                std::vector<uint32_t> &w1) {
+    aoff.resize(nv + 1), w0.resize(nv + 1), w1.resize(nv + 1);
+    for (uint64_t v = 0; v < nv; ++v) w0[v] = l0[v], w1[v] = l1[v];
+    if (esc_present(esc))
+        for (uint64_t p = 0; p < esc->n_esc_calls; ++p) {
+            const uint64_t v = esc->esc_call[p] - esc->first_call;
+            if (v < nv) w0[v] = esc->esc_a0_len[p], w1[v] = esc->esc_a1_len[p];
+        }
+    uint64_t run = 0;
+    for (uint64_t v = 0; v < nv; ++v) aoff[v] = run, run += (uint64_t)w0[v] + w1[v];
+    aoff[nv] = run;
+}
 
 /* b: the batch in the wide form, or NULL and cb: the batch in the compact form (avk_compact_batch: half the bytes over PCIe, widened on the device) */
 /* mb: a batch of MultiRegions (the merge path): one region per input pair is made on the device (dp_expand_pairs) */
 /* (pm: the packed form of a multi batch; `mb` then only carries n_regions, n_inputs, n_variants, allele_bytes and allele_bytes_len) */
 static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const avk_compact_batch *cb, bool pairs_mode, avk_dev_batch **out, const avk_multi_batch *mb = nullptr,
-                                const avk_packed_batch *pk = nullptr, const avk_packed_multi_batch *pm = nullptr, const PackedOnDevice *pre = nullptr) {
+                                const avk_packed_batch *pk = nullptr, const avk_packed_multi_batch *pm = nullptr, const PackedOnDevice *pre = nullptr,
+                                const avk_packed_escapes *esc = nullptr) {
+    const bool has_esc = (pk || pm) && esc_present(esc);
+    if (has_esc && !esc_arrays_ok(esc)) return fail(ctx, AVK_E_ARG, "escape arrays missing");
     const uint32_t mk = mb ? mb->n_inputs : 0, mppr = mk * (mk - (mk ? 1u : 0u)) / 2;
     const uint64_t n = pk ? pk->n_regions : (b ? b->n_regions : (cb ? cb->n_regions : mb->n_regions * mppr)), nv = pk ? pk->n_variants : (b ? b->n_variants : (cb ? cb->n_variants : mb->n_variants)),
                    alen = pk ? pk->allele_bytes_len : (b ? b->allele_bytes_len : (cb ? cb->allele_bytes_len : mb->allele_bytes_len));
@@ -894,7 +989,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     memset(&a, 0, sizeof(a));
     /* (the inputs and the packer's intermediates stay with the batch: region records of lane regions are written when a launch needs them) */
     /* a compare batch in the packed form is read from the packed arrays themselves (DpIn::pk_*, round 6): no wide arrays, no widening pass */
-    const bool packed_src = pk != nullptr && ctx->packed_source;
+    const bool packed_src = pk != nullptr && ctx->packed_source && !has_esc; /* (a batch with escapes is widened first: dp_widen_packed_esc) */
     bool early_variant = false, variant_done = false; /* dp_variant queued on the side stream of a packed upload, under its copies */
     auto tmp_or_kept = [&](size_t bytes) -> void * { return kept(bytes); };
     auto wide = [&](size_t bytes) -> void * { return packed_src ? nullptr : kept(bytes); };
@@ -925,7 +1020,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     a.big_list = (uint32_t *)kept((n + 1) * 4);
     uint64_t *d_block_sums = (uint64_t *)tmp(((size_t)n_blocks + 1) * AVK_DP_BS * 8);
     if (!ctx->h_dpstate && !rc) {
-        hipError_t e = hipHostMalloc((void **)&ctx->h_dpstate, sizeof(dpk::DpState) + 16, hipHostMallocDefault);
+        hipError_t e = hipHostMalloc((void **)&ctx->h_dpstate, sizeof(dpk::DpState) + 32, hipHostMallocDefault);
         if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "pinned state block: %s", hipGetErrorString(e));
     }
     if (!ctx->d_contig_tab && !rc) rc = fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
@@ -941,6 +1036,33 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
         (void)hipEventRecord(ctx->ev_tl[k], s);
     };
     mark(0);
+    /* the escape lists of a packed batch in HBM (a staging slot's, or copied with the batch's arrays), and the two exclusive sums over their values */
+    dpk::DpEsc de;
+    memset(&de, 0, sizeof(de));
+    std::vector<CopySeg> esc_segs;
+    if (has_esc) {
+        const uint64_t er = esc->n_esc_regions, es = esc->n_esc_slots, ec = esc->n_esc_calls;
+        uint64_t *x_region = pre ? pre->esc_region : (uint64_t *)tmp((er + 1) * 8), *x_slot = pre ? pre->esc_slot : (uint64_t *)tmp((es + 1) * 8),
+                 *x_call = pre ? pre->esc_call : (uint64_t *)tmp((ec + 1) * 8);
+        uint32_t *x_len = pre ? pre->esc_len : (uint32_t *)tmp((er + 1) * 4), *x_cnt = pre ? pre->esc_cnt : (uint32_t *)tmp((es + 1) * 4), *x_rel = pre ? pre->esc_rel : (uint32_t *)tmp((ec + 1) * 4),
+                 *x_a0 = pre ? pre->esc_a0 : (uint32_t *)tmp((ec + 1) * 4), *x_a1 = pre ? pre->esc_a1 : (uint32_t *)tmp((ec + 1) * 4);
+        de.region = x_region, de.slot = x_slot, de.call = x_call, de.len = x_len, de.cnt = x_cnt, de.rel = x_rel, de.a0 = x_a0, de.a1 = x_a1;
+        de.cnt_before = (uint64_t *)tmp((es + 1) * 8), de.bytes_before = (uint64_t *)tmp((ec + 1) * 8);
+        de.n_regions = er, de.n_slots = es, de.n_calls = ec, de.first_region = esc->first_region, de.first_slot = esc->first_slot, de.first_call = esc->first_call;
+        if (rc) return bail(rc);
+        if (!pre)
+            esc_segs = {{esc->esc_region, x_region, er * 8}, {esc->esc_len, x_len, er * 4}, {esc->esc_slot, x_slot, es * 8}, {esc->esc_cnt, x_cnt, es * 4}, {esc->esc_call, x_call, ec * 8},
+                        {esc->esc_rel_pos, x_rel, ec * 4}, {esc->esc_a0_len, x_a0, ec * 4}, {esc->esc_a1_len, x_a1, ec * 4}};
+    }
+    /* (side stream, behind the sums over the narrow arrays and the lists' copies) the lists are checked and summed; totals[0..1] gain what the narrow sums lack, totals[2] is the error word */
+    auto esc_scans = [&](hipStream_t side, uint64_t *totals, uint64_t n_slots_all, uint64_t n_calls_all, uint64_t n_regions_all) {
+        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.slot, de.cnt, (const uint32_t *)nullptr, de.n_slots, de.first_slot, de.first_slot + n_slots_all,
+                           (uint64_t *)de.cnt_before, totals, totals + 2);
+        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.call, de.a0, de.a1, de.n_calls, de.first_call, de.first_call + n_calls_all, (uint64_t *)de.bytes_before,
+                           totals + 1, totals + 2);
+        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.region, (const uint32_t *)nullptr, (const uint32_t *)nullptr, de.n_regions, de.first_region,
+                           de.first_region + n_regions_all, (uint64_t *)nullptr, (uint64_t *)nullptr, totals + 2);
+    };
     if (pk) { /* the packed arrays as they are, two prefix sums for the offsets they leave out, one kernel that writes the wide arrays */
         /* (the packed arrays stay with the batch when they are what the packer and the later record writers read; a staging slot's stay with its ticket) */
         auto src = [&](size_t bytes) -> void * { return packed_src ? kept(bytes) : tmp(bytes); };
@@ -969,15 +1091,21 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             if (ep != hipSuccess) rc = fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ep));
         } else
         /* (round 6: the allele bytes cross right behind the lengths — dp_variant needs nothing else, and runs on the side stream under the copies that follow) */
-        rc = copy_in(ctx, {{pk->t_cnt, p_tc, n}, {pk->q_cnt, p_qc, n}, {pk->a0_len, p_a0, nv}, {pk->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork},
-                           {pk->allele_bytes, d_alleles, alen, nullptr, ctx->ev_copy_alleles}, {pk->start, p_start, n * 4},
-                           {pk->len, p_len, n * 2}, {pk->contig_idx, p_contig, has_contig ? n * 2 : 0}, {pk->var_rel_pos, p_rel, nv * 2}, {pk->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid},
-                           {pk->var_raw_space, d_raw, has_raw ? nv * 4 : 0}});
+        { /* (the escape lists, when there are any, in front of the array whose event releases the widening; none: the order of the copies is what it was) */
+            std::vector<CopySeg> segs = {{pk->t_cnt, p_tc, n}, {pk->q_cnt, p_qc, n}, {pk->a0_len, p_a0, nv}, {pk->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork},
+                                         {pk->allele_bytes, d_alleles, alen, nullptr, ctx->ev_copy_alleles}, {pk->start, p_start, n * 4}, {pk->len, p_len, n * 2},
+                                         {pk->contig_idx, p_contig, has_contig ? n * 2 : 0}, {pk->var_rel_pos, p_rel, nv * 2}};
+            segs.insert(segs.end(), esc_segs.begin(), esc_segs.end());
+            segs.push_back({pk->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid});
+            segs.push_back({pk->var_raw_space, d_raw, has_raw ? nv * 4 : 0});
+            rc = copy_in(ctx, segs);
+        }
         early_variant = packed_src && nv != 0;
         mark(1);
         if (rc) return bail(rc);
         hipError_t ec = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0); /* (also orders the side stream behind everything queued on the context's stream before) */
         if (ec != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ec)));
+        if (has_esc && hipMemsetAsync(p_sums + nb_r + nb_v, 0, 32, side) != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(hipGetLastError())));
         if (n) {
             hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_tc, (const uint8_t *)p_qc, n, p_sums);
             hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums, nb_r, p_sums + nb_r + nb_v);
@@ -1016,6 +1144,10 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             a.in.pk_start = p_start, a.in.pk_len = p_len, a.in.pk_contig = p_contig, a.in.pk_rel = p_rel, a.in.pk_tc = p_tc, a.in.pk_qc = p_qc, a.in.pk_tz = p_tz, a.in.pk_a0 = p_a0,
             a.in.pk_a1 = p_a1, a.in.pk_voff = p_voff, a.in.pk_aoff = p_aoff;
             db->d_pk_voff = p_voff, db->d_pk_tc = p_tc, db->d_pk_qc = p_qc;
+        } else if (has_esc && ew == hipSuccess) {
+            esc_scans(side, pk_totals, 2 * n, nv, n);
+            if (m) hipLaunchKernelGGL(avk_dp_widen_packed_esc_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, side, c, de);
+            ew = hipGetLastError();
         } else if (m && ew == hipSuccess) {
             hipLaunchKernelGGL(avk_dp_widen_packed_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, side, c);
             ew = hipGetLastError();
@@ -1047,22 +1179,30 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             uint8_t *p_ic = (uint8_t *)tmp(ni + 16), *p_tz = (uint8_t *)tmp(nv + 16), *p_a0 = (uint8_t *)tmp(nv + 16), *p_a1 = (uint8_t *)tmp(nv + 16);
             const uint32_t nb_r = (uint32_t)((ni + AVK_PS_BLOCK - 1) / AVK_PS_BLOCK), nb_v = (uint32_t)((nv + AVK_PS_BLOCK - 1) / AVK_PS_BLOCK);
             uint64_t *p_aoff = (uint64_t *)tmp((nv + 1) * 8), *p_sums = (uint64_t *)tmp(((size_t)nb_r + nb_v + 4) * 8);
+            uint64_t *p_ioff = has_esc ? (uint64_t *)tmp((ni + 1) * 8) : db->d_m_in_off; /* (with escapes: the sums over the narrow counts; the widening writes the true offsets) */
             if (rc) return bail(rc);
             hipStream_t side = (ctx->up_side ? ctx->up_side : ctx->lane_stream4); /* as for avk_packed_batch: copies on the context's stream, counts first; prefix sums and widening beside them */
             auto side_fail = [&](int code) {
                 (void)hipStreamSynchronize(side);
                 return bail(code);
             };
-            rc = copy_in(ctx, {{pm->in_cnt, p_ic, ni}, {pm->a0_len, p_a0, nv}, {pm->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork}, {pm->start, p_start, nm * 4}, {pm->len, p_len, nm * 2},
-                               {pm->contig_idx, p_contig, has_contig ? nm * 2 : 0}, {pm->var_rel_pos, p_rel, nv * 2}, {pm->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid},
-                               {pm->var_raw_space, d_raw, has_raw ? nv * 4 : 0}, {pm->allele_bytes, d_alleles, alen}});
+            {
+                std::vector<CopySeg> segs = {{pm->in_cnt, p_ic, ni}, {pm->a0_len, p_a0, nv}, {pm->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork}, {pm->start, p_start, nm * 4}, {pm->len, p_len, nm * 2},
+                                             {pm->contig_idx, p_contig, has_contig ? nm * 2 : 0}, {pm->var_rel_pos, p_rel, nv * 2}};
+                segs.insert(segs.end(), esc_segs.begin(), esc_segs.end()); /* (none without escapes: the order of the copies is what it was) */
+                segs.push_back({pm->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid});
+                segs.push_back({pm->var_raw_space, d_raw, has_raw ? nv * 4 : 0});
+                segs.push_back({pm->allele_bytes, d_alleles, alen});
+                rc = copy_in(ctx, segs);
+            }
             if (rc) return bail(rc);
             hipError_t ec = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0);
             if (ec != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ec)));
+            if (has_esc && hipMemsetAsync(p_sums + nb_r + nb_v, 0, 32, side) != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(hipGetLastError())));
             if (ni) {
                 hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_ic, (const uint8_t *)nullptr, ni, p_sums);
                 hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums, nb_r, p_sums + nb_r + nb_v);
-                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_ic, (const uint8_t *)nullptr, ni, (const uint64_t *)p_sums, db->d_m_in_off);
+                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_ic, (const uint8_t *)nullptr, ni, (const uint64_t *)p_sums, p_ioff);
             }
             if (nv) {
                 hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, p_sums + nb_r);
@@ -1073,12 +1213,16 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             dpk::DpPackedMulti w;
             memset(&w, 0, sizeof(w));
             w.contig_idx = p_contig, w.len = p_len, w.rel_pos = p_rel, w.start = p_start, w.var_raw = d_raw, w.in_cnt = p_ic, w.var_type_zyg = p_tz, w.a0_len = p_a0, w.a1_len = p_a1,
-            w.in_off = db->d_m_in_off, w.a_off = p_aoff, w.n_multi = nm, w.n_variants = nv, w.k = mk;
+            w.in_off = p_ioff, w.a_off = p_aoff, w.n_multi = nm, w.n_variants = nv, w.k = mk;
             w.w_contig = m_contig, w.w_in_cnt = db->d_m_in_cnt, w.w_a0_len = d_a0l, w.w_a1_len = d_a1l, w.w_raw = nullptr, w.w_start = m_start, w.w_end = m_end, w.w_pos = d_pos,
             w.w_a0_off = d_a0o, w.w_a1_off = d_a1o, w.w_type = d_type, w.w_zyg = d_zyg;
             const uint64_t mx = nm > nv ? nm : nv;
             hipError_t ew = hipStreamWaitEvent(side, ctx->ev_copy_mid, 0);
-            if (mx && ew == hipSuccess) {
+            if (has_esc && ew == hipSuccess) {
+                esc_scans(side, pk_totals, ni, nv, nm);
+                if (mx) hipLaunchKernelGGL(avk_dp_widen_packed_multi_esc_kernel, dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, side, w, de, db->d_m_in_off);
+                ew = hipGetLastError();
+            } else if (mx && ew == hipSuccess) {
                 hipLaunchKernelGGL(avk_dp_widen_packed_multi_kernel, dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, side, w);
                 ew = hipGetLastError();
             }
@@ -1188,22 +1332,25 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
         }
         mark(2);
         if (x == hipSuccess) x = hipMemcpyAsync(hs, a.st, sizeof(dpk::DpState), hipMemcpyDeviceToHost, s);
-        if (x == hipSuccess && pk_totals) x = hipMemcpyAsync(hs + 1, pk_totals, 16, hipMemcpyDeviceToHost, s); /* (the packed forms' two sums ride along: 16 bytes behind the state block) */
+        if (x == hipSuccess && pk_totals) x = hipMemcpyAsync(hs + 1, pk_totals, has_esc ? 24 : 16, hipMemcpyDeviceToHost, s); /* (the packed forms' two sums ride along: 16 bytes behind the state block) */
         if (x == hipSuccess) x = hipStreamSynchronize(s);
         if (x == hipSuccess) engine_rate_check(ctx);
         return x;
     };
     if (e == hipSuccess) e = region_passes();
     if (e == hipSuccess && (pk || pm)) { /* the two sums the packed form implies must be what the caller says they are */
-        uint64_t tot[2] = {0, 0};
-        memcpy(tot, hs + 1, sizeof(tot));
+        uint64_t tot[3] = {0, 0, 0};
+        memcpy(tot, hs + 1, has_esc ? 24 : 16);
+        if (has_esc && tot[2]) return bail(fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending or names an entry outside the batch"));
         if ((((pm ? pm->n_regions : n) && tot[0] != nv) || (nv && tot[1] != alen)))
             return bail(fail(ctx, AVK_E_ARG, "packed batch: the call counts sum to %llu (n_variants %llu), the allele lengths to %llu (allele_bytes_len %llu)",
                              (unsigned long long)tot[0], (unsigned long long)nv, (unsigned long long)tot[1], (unsigned long long)alen));
     }
     std::vector<uint64_t> pk_aoff; /* packed form: allele offsets on the host, made only when a call needs the host's edit distance */
+    std::vector<uint32_t> pk_w0, pk_w1; /* ... and the lengths, escapes honoured */
     const uint8_t *pk_l0 = pk ? pk->a0_len : (pm ? pm->a0_len : nullptr), *pk_l1 = pk ? pk->a1_len : (pm ? pm->a1_len : nullptr);
-    if (e == hipSuccess && hs->n_pending && pk_l0) {
+    if (e == hipSuccess && hs->n_pending && pk_l0 && has_esc) packed_host_alleles(pk_l0, pk_l1, nv, esc, pk_aoff, pk_w0, pk_w1);
+    else if (e == hipSuccess && hs->n_pending && pk_l0) {
         pk_aoff.resize(nv + 1);
         uint64_t run = 0;
         for (uint64_t v = 0; v < nv; ++v) pk_aoff[v] = run, run += (uint64_t)pk_l0[v] + pk_l1[v];
@@ -1218,8 +1365,8 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             avk_parallel_for(np, avk_host_threads(), [&](unsigned, uint64_t lo, uint64_t hi) {
                 for (uint64_t k = lo; k < hi; ++k) {
                     const uint64_t v = idx[k];
-                    const uint64_t o0 = pk_l0 ? pk_aoff[v] : (b ? b->a0_off[v] : (cb ? cb->a_off[v] : mb->a0_off[v])), l0 = pk_l0 ? pk_l0[v] : (b ? b->a0_len[v] : (cb ? cb->a0_len[v] : mb->a0_len[v])),
-                                   o1 = pk_l0 ? o0 + l0 : (b ? b->a1_off[v] : (cb ? o0 + l0 : mb->a1_off[v])), l1 = pk_l0 ? pk_l1[v] : (b ? b->a1_len[v] : (cb ? cb->a1_len[v] : mb->a1_len[v]));
+                    const uint64_t o0 = pk_l0 ? pk_aoff[v] : (b ? b->a0_off[v] : (cb ? cb->a_off[v] : mb->a0_off[v])), l0 = pk_l0 ? (has_esc ? pk_w0[v] : (uint32_t)pk_l0[v]) : (b ? b->a0_len[v] : (cb ? cb->a0_len[v] : mb->a0_len[v])),
+                                   o1 = pk_l0 ? o0 + l0 : (b ? b->a1_off[v] : (cb ? o0 + l0 : mb->a1_off[v])), l1 = pk_l0 ? (has_esc ? pk_w1[v] : (uint32_t)pk_l1[v]) : (b ? b->a1_len[v] : (cb ? cb->a1_len[v] : mb->a1_len[v]));
                     ed[k] = (uint32_t)avk::host_edit_distance(host_alleles + o0, l0, host_alleles + o1, l1);
                 }
             });
@@ -1410,7 +1557,7 @@ static int download_device_packed(avk_ctx *ctx, avk_dev_batch *db, avk_result_ba
     }
     if (rc) return done(rc);
     if (!ctx->h_dpstate) {
-        hipError_t e = hipHostMalloc((void **)&ctx->h_dpstate, sizeof(dpk::DpState) + 16, hipHostMallocDefault);
+        hipError_t e = hipHostMalloc((void **)&ctx->h_dpstate, sizeof(dpk::DpState) + 32, hipHostMallocDefault);
         if (e != hipSuccess) return done(fail(ctx, AVK_E_HIP, "pinned state block: %s", hipGetErrorString(e)));
     }
     static_assert(sizeof(dpk::DpState) >= AVK_TALLY_STRIDE * 8, "the pinned state block also receives the tally");

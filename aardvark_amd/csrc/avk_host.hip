@@ -2626,11 +2626,13 @@ static int stage_slot_prepare(avk_ctx *ctx, avk_ctx::StageSlot &sl, size_t bytes
 
 /* the eleven arrays of `batch` into a staging slot: the slot is (re)sized and the copies are queued on the copy-in stream, counts and lengths first as in
  * avk_compare_packed — nothing of this context reads or writes the slot */
-static int stage_layout(avk_ctx *ctx, avk_ctx::StageSlot &sl, const avk_packed_batch *batch, PackedOnDevice *pre) {
+static int stage_layout(avk_ctx *ctx, avk_ctx::StageSlot &sl, const avk_packed_batch *batch, const avk_packed_escapes *esc, PackedOnDevice *pre) {
     const uint64_t n = batch->n_regions, nv = batch->n_variants, alen = batch->allele_bytes_len;
     const bool has_contig = batch->contig_idx != nullptr, has_raw = batch->var_raw_space != nullptr;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t need = 2 * up(n + 16) + 3 * up(nv + 16) + up(n * 4 + 16) + 2 * up(n * 2 + 16) + up(nv * 2 + 16) + up(nv * 4 + 16) + up(alen + 16);
+    const uint64_t er = esc ? esc->n_esc_regions : 0, es = esc ? esc->n_esc_slots : 0, ec = esc ? esc->n_esc_calls : 0; /* (esc: NULL unless it lists something) */
+    const size_t need = 2 * up(n + 16) + 3 * up(nv + 16) + up(n * 4 + 16) + 2 * up(n * 2 + 16) + up(nv * 2 + 16) + up(nv * 4 + 16) + up(alen + 16) +
+                        (esc ? up(er * 8 + 16) + up(er * 4 + 16) + up(es * 8 + 16) + up(es * 4 + 16) + up(ec * 8 + 16) + 3 * up(ec * 4 + 16) : 0);
     {
         const int rc = stage_slot_prepare(ctx, sl, need);
         if (rc) return rc;
@@ -2645,6 +2647,18 @@ static int stage_layout(avk_ctx *ctx, avk_ctx::StageSlot &sl, const avk_packed_b
     pre->t_cnt = take(n), pre->q_cnt = take(n), pre->a0_len = take(nv), pre->a1_len = take(nv), pre->start = (uint32_t *)take(n * 4), pre->len = (uint16_t *)take(n * 2);
     pre->contig = (uint16_t *)take(n * 2), pre->rel_pos = (uint16_t *)take(nv * 2), pre->var_type_zyg = take(nv), pre->raw = (uint32_t *)take(nv * 4), pre->alleles = take(alen);
     pre->ready = sl.ev_in;
+    if (esc) { /* the escape lists ride on the copy stream with the rest */
+        pre->esc_region = (uint64_t *)take(er * 8), pre->esc_len = (uint32_t *)take(er * 4), pre->esc_slot = (uint64_t *)take(es * 8), pre->esc_cnt = (uint32_t *)take(es * 4);
+        pre->esc_call = (uint64_t *)take(ec * 8), pre->esc_rel = (uint32_t *)take(ec * 4), pre->esc_a0 = (uint32_t *)take(ec * 4), pre->esc_a1 = (uint32_t *)take(ec * 4);
+        const struct { const void *src; void *dst; size_t bytes; } ce[] = {
+            {esc->esc_region, pre->esc_region, er * 8}, {esc->esc_len, pre->esc_len, er * 4}, {esc->esc_slot, pre->esc_slot, es * 8}, {esc->esc_cnt, pre->esc_cnt, es * 4},
+            {esc->esc_call, pre->esc_call, ec * 8}, {esc->esc_rel_pos, pre->esc_rel, ec * 4}, {esc->esc_a0_len, pre->esc_a0, ec * 4}, {esc->esc_a1_len, pre->esc_a1, ec * 4}};
+        for (const auto &c : ce)
+            if (c.bytes && c.src && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, ctx->copy_in_stream) != hipSuccess) {
+                (void)hipStreamSynchronize(ctx->copy_in_stream);
+                return fail(ctx, AVK_E_HIP, "queueing the batch's copies failed: %s", hipGetErrorString(hipGetLastError()));
+            }
+    }
     const struct { const void *src; void *dst; size_t bytes; } cp[] = {
         {batch->t_cnt, pre->t_cnt, n}, {batch->q_cnt, pre->q_cnt, n}, {batch->a0_len, pre->a0_len, nv}, {batch->a1_len, pre->a1_len, nv}, {batch->start, pre->start, n * 4},
         {batch->len, pre->len, n * 2}, {batch->contig_idx, pre->contig, has_contig ? n * 2 : 0}, {batch->var_rel_pos, pre->rel_pos, nv * 2}, {batch->var_type_zyg, pre->var_type_zyg, nv},
@@ -2659,24 +2673,34 @@ static int stage_layout(avk_ctx *ctx, avk_ctx::StageSlot &sl, const avk_packed_b
     }
     return 0;
 }
-static bool packed_inputs_pinned(const avk_packed_batch *batch) {
+static bool packed_inputs_pinned(const avk_packed_batch *batch, const avk_packed_escapes *esc = nullptr) {
     const uint64_t n = batch->n_regions, nv = batch->n_variants, alen = batch->allele_bytes_len;
+    if (esc && !(is_pinned(esc->esc_region, esc->n_esc_regions * 8) && is_pinned(esc->esc_len, esc->n_esc_regions * 4) && is_pinned(esc->esc_slot, esc->n_esc_slots * 8) &&
+                 is_pinned(esc->esc_cnt, esc->n_esc_slots * 4) && is_pinned(esc->esc_call, esc->n_esc_calls * 8) && is_pinned(esc->esc_rel_pos, esc->n_esc_calls * 4) &&
+                 is_pinned(esc->esc_a0_len, esc->n_esc_calls * 4) && is_pinned(esc->esc_a1_len, esc->n_esc_calls * 4)))
+        return false;
     return is_pinned(batch->t_cnt, n) && is_pinned(batch->q_cnt, n) && is_pinned(batch->a0_len, nv) && is_pinned(batch->a1_len, nv) && is_pinned(batch->start, n * 4) &&
            is_pinned(batch->len, n * 2) && is_pinned(batch->contig_idx, n * 2) && is_pinned(batch->var_rel_pos, nv * 2) && is_pinned(batch->var_type_zyg, nv) &&
            is_pinned(batch->var_raw_space, nv * 4) && is_pinned(batch->allele_bytes, alen);
 }
 
 static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket, uint32_t *shared_spill,
-                       uint32_t *shared_spill_count);
+                       uint32_t *shared_spill_count, const avk_packed_escapes *esc = nullptr);
 int avk_compare_packed_submit(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket) {
     return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr);
+}
+int avk_compare_packed_submit_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_compare_config *cfg, avk_result_batch *out,
+                                  avk_ticket **ticket) {
+    return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr, esc);
 }
 /* shared_spill / shared_spill_count: the device list and counter the parts of one split call spill their BASEPAIR groups into (compare_packed_split); with them a
  * batch that returns the packed groups can be queued like any other */
 static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket, uint32_t *shared_spill,
-                       uint32_t *shared_spill_count) {
+                       uint32_t *shared_spill_count, const avk_packed_escapes *esc) {
     if (!ctx || !batch || !cfg || !out || !ticket || !(out->status || out->region_packed)) return AVK_E_ARG;
     *ticket = nullptr;
+    if (!esc_present(esc)) esc = nullptr;
+    if (!esc_arrays_ok(esc)) return fail(ctx, AVK_E_ARG, "escape arrays missing");
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = batch->n_regions, nv = batch->n_variants;
@@ -2689,7 +2713,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     avk_ticket *t = new avk_ticket();
     t->out = *out;
     /* arrays that are not pinned cannot be copied behind the caller's back: such a batch is solved here and now, its ticket is complete */
-    bool pinned = packed_inputs_pinned(batch);
+    bool pinned = packed_inputs_pinned(batch, esc);
     pinned = pinned && is_pinned(out->status, n * 4) && is_pinned(out->region_packed, n * 8) && is_pinned(out->ed_h1, n * 4) && is_pinned(out->ed_h2, n * 4) && is_pinned(out->n_optima, n * 4) &&
              is_pinned(out->type_present, n * 2) && is_pinned(out->var_expected, nv) && is_pinned(out->var_observed, nv) && is_pinned(out->var_class, nv) && is_pinned(out->var_zyg, nv) &&
              is_pinned(out->var_packed, nv) && is_pinned(out->group_metrics, n * AVK_N_GROUPS * AVK_N_FIELDS * 4);
@@ -2708,7 +2732,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
         return fail(ctx, AVK_E_STATE, "four batches are in flight: avk_wait for one of them first");
     }
     if (slot < 0) { /* solved here and now (it uses no staging slot): a complete ticket on success, no ticket on failure — the caller owns what it is handed */
-        const int rc_now = avk_compare_packed(ctx, batch, cfg, out);
+        const int rc_now = avk_compare_packed_esc(ctx, batch, esc, cfg, out);
         if (rc_now) {
             delete t;
             return rc_now;
@@ -2719,7 +2743,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     }
     avk_ctx::StageSlot &sl = ctx->stage[slot];
     PackedOnDevice pre;
-    int rc = stage_layout(ctx, sl, batch, &pre);
+    int rc = stage_layout(ctx, sl, batch, esc, &pre);
     if (rc) {
         delete t;
         return rc;
@@ -2742,7 +2766,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
             ctx->pool_fence_pending = false;
         }
     }
-    rc = upload_device_packed(ctx, nullptr, nullptr, false, &t->db, nullptr, batch, nullptr, &pre);
+    rc = upload_device_packed(ctx, nullptr, nullptr, false, &t->db, nullptr, batch, nullptr, &pre, esc);
     if (!rc && ctx->up_stream) {
         hipError_t e = hipEventRecord(ctx->ev_packed, ctx->up_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ev_packed, 0);
@@ -3000,13 +3024,14 @@ int avk_batch_upload_compact(avk_ctx *ctx, const avk_compact_batch *batch, avk_d
     return upload_device_packed(ctx, nullptr, batch, false, out);
 }
 
-int avk_batch_upload_packed(avk_ctx *ctx, const avk_packed_batch *batch, avk_dev_batch **out) {
+int avk_batch_upload_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, avk_dev_batch **out) {
     if (!ctx || !batch || !out) return AVK_E_ARG;
     *out = nullptr;
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    return upload_device_packed(ctx, nullptr, nullptr, false, out, nullptr, batch);
+    return upload_device_packed(ctx, nullptr, nullptr, false, out, nullptr, batch, nullptr, nullptr, esc);
 }
+int avk_batch_upload_packed(avk_ctx *ctx, const avk_packed_batch *batch, avk_dev_batch **out) { return avk_batch_upload_packed_esc(ctx, batch, nullptr, out); }
 
 /* One large call as `parts` batches in flight (context option split_parts; avk_compare_packed below): the regions are independent (src/main.rs:251-268 maps over
  * them), so the batch is cut into ranges of regions — the packed form has no explicit offsets, a range of regions with its calls and allele bytes is a packed batch of
@@ -3128,9 +3153,13 @@ static int compare_packed_split(avk_ctx *ctx, const avk_packed_batch *batch, con
 }
 
 int avk_compare_packed(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out) {
+    return avk_compare_packed_esc(ctx, batch, nullptr, cfg, out);
+}
+int avk_compare_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_compare_config *cfg, avk_result_batch *out) {
     if (!ctx || !batch || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
     ctx->last_one_shot = 0;
-    if (ctx->split_parts > 1 && ctx->d_ref) {
+    if (!esc_present(esc)) esc = nullptr;
+    if (ctx->split_parts > 1 && ctx->d_ref && !esc) { /* (the split cuts the narrow arrays by their own running sums: a batch with escapes runs whole) */
         const int rs = compare_packed_split(ctx, batch, cfg, out);
         if (rs >= 0) return rs;
     }
@@ -3139,7 +3168,7 @@ int avk_compare_packed(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     if (!out->group_metrics) ctx->emit_group_metrics = 0;
     if ((out->bp_off || (out->bp_packed && out->bp_spilled)) && out->bp_groups) ctx->emit_bp_groups = 1;
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = avk_batch_upload_packed(ctx, batch, &db);
+    int rc = avk_batch_upload_packed_esc(ctx, batch, esc, &db);
     const auto t1 = std::chrono::steady_clock::now();
     if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
     const auto t2 = std::chrono::steady_clock::now();
@@ -3392,10 +3421,15 @@ static bool merge_on_device(const avk_ctx *ctx, uint64_t n_regions, uint32_t k) 
     return ctx->device_pack && k >= 2 && k <= (uint32_t)avk::dp::DP_MERGE_KMAX && n_regions && n_regions * (uint64_t)(k * (k - 1) / 2) <= 0x7FFFFFFFull;
 }
 static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                uint64_t *members);
+                                uint64_t *members, const avk_packed_escapes *esc = nullptr);
 
 int avk_merge_packed(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification, uint64_t *members) {
+    return avk_merge_packed_esc(ctx, pm, nullptr, cfg, status, classification, members);
+}
+int avk_merge_packed_esc(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
+                         uint64_t *members) {
     if (!ctx || !pm || !cfg || !status || !classification || !members) return AVK_E_ARG;
+    if (!esc_present(esc)) esc = nullptr;
     const uint32_t k = pm->n_inputs;
     if (k < 1 || k > 64) return fail(ctx, AVK_E_ARG, "n_inputs must be in [1, 64]");
     const uint64_t n = pm->n_regions, nv = pm->n_variants;
@@ -3404,25 +3438,28 @@ int avk_merge_packed(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_m
     avk_multi_batch mb;
     memset(&mb, 0, sizeof(mb));
     mb.n_regions = n, mb.n_inputs = k, mb.n_variants = nv, mb.allele_bytes = pm->allele_bytes, mb.allele_bytes_len = pm->allele_bytes_len;
-    if (merge_on_device(ctx, n, k)) return merge_batch_internal(ctx, &mb, pm, cfg, status, classification, members);
+    if (merge_on_device(ctx, n, k)) return merge_batch_internal(ctx, &mb, pm, cfg, status, classification, members, esc);
+    PackedWideHost wh;
+    if (!packed_widen_host(pm->len, n, pm->in_cnt, nullptr, n * k, pm->var_rel_pos, pm->a0_len, pm->a1_len, nv, esc, wh))
+        return fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending or names an entry outside the batch");
     /* no device path for this batch (more than DP_MERGE_KMAX inputs, an empty batch, device_pack = 0): the wide form, made here, through avk_merge_batch */
     std::vector<uint64_t> start(n), end(n), in_off(n * k), pos(nv), a0_off(nv), a1_off(nv);
     std::vector<uint32_t> contig(n), in_cnt(n * k), a0_len(nv), a1_len(nv), raw(nv);
     std::vector<uint8_t> type(nv + 1), zyg(nv + 1);
     uint64_t v = 0, ab = 0;
     for (uint64_t m = 0; m < n; ++m) {
-        contig[m] = pm->contig_idx ? pm->contig_idx[m] : 0u, start[m] = pm->start[m], end[m] = (uint64_t)pm->start[m] + pm->len[m];
+        contig[m] = pm->contig_idx ? pm->contig_idx[m] : 0u, start[m] = pm->start[m], end[m] = (uint64_t)pm->start[m] + wh.len[m];
         for (uint32_t i = 0; i < k; ++i) {
-            in_off[m * k + i] = v, in_cnt[m * k + i] = pm->in_cnt[m * k + i];
-            for (uint32_t q = 0; q < pm->in_cnt[m * k + i]; ++q, ++v) {
+            in_off[m * k + i] = v, in_cnt[m * k + i] = wh.cnt[m * k + i];
+            for (uint32_t q = 0; q < wh.cnt[m * k + i]; ++q, ++v) {
                 if (v >= nv) return fail(ctx, AVK_E_ARG, "packed batch: the call counts sum to more than n_variants %llu", (unsigned long long)nv);
-                pos[v] = start[m] + pm->var_rel_pos[v];
+                pos[v] = start[m] + wh.rel[v];
             }
         }
     }
     if (v != nv) return fail(ctx, AVK_E_ARG, "packed batch: the call counts sum to %llu (n_variants %llu)", (unsigned long long)v, (unsigned long long)nv);
     for (v = 0; v < nv; ++v) {
-        a0_off[v] = ab, a0_len[v] = pm->a0_len[v], a1_off[v] = ab + a0_len[v], a1_len[v] = pm->a1_len[v], ab += (uint64_t)a0_len[v] + a1_len[v];
+        a0_off[v] = ab, a0_len[v] = wh.a0[v], a1_off[v] = ab + a0_len[v], a1_len[v] = wh.a1[v], ab += (uint64_t)a0_len[v] + a1_len[v];
         raw[v] = pm->var_raw_space ? pm->var_raw_space[v] : (a0_len[v] > a1_len[v] ? a0_len[v] : a1_len[v]);
         type[v] = pm->var_type_zyg[v] & 15u, zyg[v] = pm->var_type_zyg[v] >> 4;
     }
@@ -3437,7 +3474,7 @@ int avk_merge_batch(avk_ctx *ctx, const avk_multi_batch *mb, const avk_merge_con
 }
 
 static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                uint64_t *members) {
+                                uint64_t *members, const avk_packed_escapes *esc) {
     if (!ctx || !mb || !cfg || !status || !classification || !members) return AVK_E_ARG;
     const uint32_t k = mb->n_inputs;
     if (k < 1 || k > 64) return fail(ctx, AVK_E_ARG, "n_inputs must be in [1, 64]");
@@ -3447,7 +3484,7 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
         if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
         AVK_HIP(ctx, hipSetDevice(ctx->device));
         avk_dev_batch *db = nullptr;
-        int rc = upload_device_packed(ctx, nullptr, nullptr, true, &db, mb, nullptr, pm);
+        int rc = upload_device_packed(ctx, nullptr, nullptr, true, &db, mb, nullptr, pm, nullptr, esc);
         if (rc) return rc;
         avk_compare_config pcfg;
         pcfg.max_branch_factor = cfg->max_branch_factor, pcfg.enable_sequences = 0, pcfg.enable_exact_shortcut = 0;

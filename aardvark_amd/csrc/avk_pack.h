@@ -7,6 +7,11 @@
  * :757,:773; unsorted variants, query_optimizer.rs:370-371 "pre-sorted"; empty alleles,
  * variants.rs:103-355; raw_allele_space < allele length, variants.rs:364-370; non-ALT zygosities hit
  * assert_eq! at query_optimizer.rs:315): those regions get a status instead of aborting the process.
+ *
+ * The escape rule (avk_packed_escapes, include/aardvark_amd.h): a packed batch's escapes are applied BEFORE any rule here — a listed region's window length,
+ * a listed count slot's count and a listed call's relative position and allele lengths replace the narrow fields (which are 0), the offsets are the running
+ * sums over the values so replaced — and the result is validated and laid out as the wide batch it stands for (the device: dp_widen_packed_esc, then the same
+ * dp_region; the host: packed_widen_host).  Escapes change where a value travels, never a record.
  */
 #ifndef AVK_PACK_H
 #define AVK_PACK_H

@@ -9,8 +9,38 @@
 
 #include <dlfcn.h>
 
+/* the escapes of a shard (avk_packed_escapes of the whole batch, gathered with the shard's regions and calls and rebased to the shard's indices) */
+struct ShardEscapes {
+    avk_packed_escapes e;
+    std::vector<uint64_t> region, slot, call;
+    std::vector<uint32_t> len, cnt, rel, a0, a1;
+    /* the whole batch's lists are walked once, in step with the shard's ascending regions */
+    uint64_t pr = 0, ps = 0, pc = 0;
+    void take(const avk_packed_escapes *w, uint64_t r, uint64_t k, uint64_t slots_per_region, uint64_t v0, uint64_t calls, uint64_t at_v) {
+        if (!w) return;
+        while (pr < w->n_esc_regions && w->esc_region[pr] - w->first_region < r) ++pr;
+        if (pr < w->n_esc_regions && w->esc_region[pr] - w->first_region == r) region.push_back(k), len.push_back(w->esc_len[pr]);
+        const uint64_t s0 = r * slots_per_region;
+        while (ps < w->n_esc_slots && w->esc_slot[ps] - w->first_slot < s0) ++ps;
+        for (; ps < w->n_esc_slots && w->esc_slot[ps] - w->first_slot < s0 + slots_per_region; ++ps)
+            slot.push_back(k * slots_per_region + (w->esc_slot[ps] - w->first_slot - s0)), cnt.push_back(w->esc_cnt[ps]);
+        while (pc < w->n_esc_calls && w->esc_call[pc] - w->first_call < v0) ++pc;
+        for (; pc < w->n_esc_calls && w->esc_call[pc] - w->first_call < v0 + calls; ++pc)
+            call.push_back(at_v + (w->esc_call[pc] - w->first_call - v0)), rel.push_back(w->esc_rel_pos[pc]), a0.push_back(w->esc_a0_len[pc]), a1.push_back(w->esc_a1_len[pc]);
+    }
+    void finish() {
+        memset(&e, 0, sizeof(e));
+        e.n_esc_regions = region.size(), e.n_esc_slots = slot.size(), e.n_esc_calls = call.size();
+        region.push_back(0), len.push_back(0), slot.push_back(0), cnt.push_back(0), call.push_back(0), rel.push_back(0), a0.push_back(0), a1.push_back(0); /* (never NULL) */
+        e.esc_region = region.data(), e.esc_len = len.data(), e.esc_slot = slot.data(), e.esc_cnt = cnt.data();
+        e.esc_call = call.data(), e.esc_rel_pos = rel.data(), e.esc_a0_len = a0.data(), e.esc_a1_len = a1.data();
+    }
+};
+
 struct avk_packed_shard {
     avk_packed_batch b;
+    ShardEscapes esc;
+    std::vector<uint64_t> calls;      /* the shard's k-th region has calls[k] calls (its narrow counts do not say so when they are escaped) */
     std::vector<uint64_t> index;      /* the shard's k-th region is region index[k] of the whole batch */
     std::vector<uint64_t> whole_call; /* ... and its calls start at call whole_call[k] of the whole batch */
     std::vector<uint16_t> contig_idx, len, rel;
@@ -20,6 +50,7 @@ struct avk_packed_shard {
 
 struct avk_packed_multi_shard {
     avk_packed_multi_batch b;
+    ShardEscapes esc;
     std::vector<uint64_t> index; /* the shard's j-th region is region index[j] of the whole batch */
     std::vector<uint16_t> contig_idx, len, rel;
     std::vector<uint32_t> start, raw;
@@ -29,21 +60,28 @@ struct avk_packed_multi_shard {
 extern "C" {
 
 int avk_packed_shard_make(const avk_packed_batch *whole, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world, avk_packed_shard **out) {
+    return avk_packed_shard_make_esc(whole, nullptr, region_id, first_id, rank, world, out);
+}
+int avk_packed_shard_make_esc(const avk_packed_batch *whole, const avk_packed_escapes *esc, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world,
+                              avk_packed_shard **out) {
     if (!whole || !out || world == 0 || rank >= world) return AVK_E_ARG;
     *out = nullptr;
+    if (!esc_present(esc)) esc = nullptr;
     const uint64_t n = whole->n_regions, nv = whole->n_variants;
     if (n && (!whole->start || !whole->len || !whole->t_cnt || !whole->q_cnt)) return AVK_E_ARG;
     if (nv && (!whole->var_rel_pos || !whole->var_type_zyg || !whole->a0_len || !whole->a1_len || !whole->allele_bytes)) return AVK_E_ARG;
+    PackedWideHost wh; /* (with escapes: the counts and lengths the running sums are made of) */
+    if (esc && !packed_widen_host(whole->len, n, whole->t_cnt, whole->q_cnt, 2 * n, whole->var_rel_pos, whole->a0_len, whole->a1_len, nv, esc, wh)) return AVK_E_ARG;
     avk_packed_shard *s = new avk_packed_shard();
     memset(&s->b, 0, sizeof(s->b));
     /* the packed form's offsets are running sums: where every region's calls and every call's alleles start */
     std::vector<uint64_t> v_first(n + 1, 0), a_first(nv + 1, 0);
-    for (uint64_t r = 0; r < n; ++r) v_first[r + 1] = v_first[r] + whole->t_cnt[r] + whole->q_cnt[r];
+    for (uint64_t r = 0; r < n; ++r) v_first[r + 1] = v_first[r] + (esc ? (uint64_t)wh.cnt[2 * r] + wh.cnt[2 * r + 1] : (uint64_t)whole->t_cnt[r] + whole->q_cnt[r]);
     if (v_first[n] != nv) {
         delete s;
         return AVK_E_ARG;
     }
-    for (uint64_t v = 0; v < nv; ++v) a_first[v + 1] = a_first[v] + whole->a0_len[v] + whole->a1_len[v];
+    for (uint64_t v = 0; v < nv; ++v) a_first[v + 1] = a_first[v] + (esc ? (uint64_t)wh.a0[v] + wh.a1[v] : (uint64_t)whole->a0_len[v] + whole->a1_len[v]);
     if (a_first[nv] != whole->allele_bytes_len) {
         delete s;
         return AVK_E_ARG;
@@ -57,7 +95,7 @@ int avk_packed_shard_make(const avk_packed_batch *whole, const uint64_t *region_
         mv += v_first[r + 1] - v_first[r];
         ma += a_first[v_first[r + 1]] - a_first[v_first[r]];
     }
-    s->whole_call.resize(m + 1);
+    s->whole_call.resize(m + 1), s->calls.resize(m + 1);
     s->start.resize(m + 1), s->len.resize(m + 1), s->t_cnt.resize(m + 1), s->q_cnt.resize(m + 1);
     if (whole->contig_idx) s->contig_idx.resize(m + 1);
     s->rel.resize(mv + 1), s->tz.resize(mv + 1), s->a0.resize(mv + 1), s->a1.resize(mv + 1), s->alleles.resize(ma + 1);
@@ -65,7 +103,8 @@ int avk_packed_shard_make(const avk_packed_batch *whole, const uint64_t *region_
     uint64_t at_v = 0, at_a = 0;
     for (uint64_t k = 0; k < m; ++k) {
         const uint64_t r = s->index[k], v0 = v_first[r], cnt = v_first[r + 1] - v0, ab = a_first[v0 + cnt] - a_first[v0];
-        s->whole_call[k] = v0;
+        s->whole_call[k] = v0, s->calls[k] = cnt;
+        s->esc.take(esc, r, k, 2, v0, cnt, at_v);
         s->start[k] = whole->start[r], s->len[k] = whole->len[r], s->t_cnt[k] = whole->t_cnt[r], s->q_cnt[k] = whole->q_cnt[r];
         if (whole->contig_idx) s->contig_idx[k] = whole->contig_idx[r];
         memcpy(s->rel.data() + at_v, whole->var_rel_pos + v0, cnt * 2);
@@ -83,11 +122,13 @@ int avk_packed_shard_make(const avk_packed_batch *whole, const uint64_t *region_
     s->b.var_rel_pos = s->rel.data(), s->b.var_type_zyg = s->tz.data(), s->b.a0_len = s->a0.data(), s->b.a1_len = s->a1.data();
     s->b.var_raw_space = whole->var_raw_space ? s->raw.data() : nullptr;
     s->b.allele_bytes = s->alleles.data();
+    s->esc.finish();
     *out = s;
     return AVK_E_OK;
 }
 
 const avk_packed_batch *avk_packed_shard_batch(const avk_packed_shard *s) { return s ? &s->b : nullptr; }
+const avk_packed_escapes *avk_packed_shard_escapes(const avk_packed_shard *s) { return s ? &s->esc.e : nullptr; }
 
 uint64_t avk_packed_shard_regions(const avk_packed_shard *s, const uint64_t **index_in_whole) {
     if (!s) return 0;
@@ -102,7 +143,7 @@ int avk_packed_shard_scatter(const avk_packed_shard *s, const avk_result_batch *
     const uint64_t m = s->index.size();
     uint64_t at_v = 0;
     for (uint64_t k = 0; k < m; ++k) {
-        const uint64_t r = s->index[k], cnt = (uint64_t)s->t_cnt[k] + s->q_cnt[k], v0 = s->whole_call[k];
+        const uint64_t r = s->index[k], cnt = s->calls[k], v0 = s->whole_call[k];
         if (from->status && to->status) to->status[r] = from->status[k];
         if (from->ed_h1 && to->ed_h1) to->ed_h1[r] = from->ed_h1[k];
         if (from->ed_h2 && to->ed_h2) to->ed_h2[r] = from->ed_h2[k];
@@ -125,19 +166,26 @@ void avk_packed_shard_free(avk_packed_shard *s) { delete s; }
 
 int avk_packed_multi_shard_make(const avk_packed_multi_batch *whole, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world,
                                 avk_packed_multi_shard **out) {
+    return avk_packed_multi_shard_make_esc(whole, nullptr, region_id, first_id, rank, world, out);
+}
+int avk_packed_multi_shard_make_esc(const avk_packed_multi_batch *whole, const avk_packed_escapes *esc, const uint64_t *region_id, uint64_t first_id, uint32_t rank,
+                                    uint32_t world, avk_packed_multi_shard **out) {
     if (!whole || !out || world == 0 || rank >= world || whole->n_inputs < 2 || whole->n_inputs > 64) return AVK_E_ARG;
     *out = nullptr;
+    if (!esc_present(esc)) esc = nullptr;
     const uint64_t n = whole->n_regions, nv = whole->n_variants, k = whole->n_inputs;
     if (n && (!whole->start || !whole->len || !whole->in_cnt)) return AVK_E_ARG;
     if (nv && (!whole->var_rel_pos || !whole->var_type_zyg || !whole->a0_len || !whole->a1_len || !whole->allele_bytes)) return AVK_E_ARG;
     std::vector<uint64_t> v_first(n + 1, 0), a_first(nv + 1, 0);
+    PackedWideHost wh;
+    if (esc && !packed_widen_host(whole->len, n, whole->in_cnt, nullptr, n * k, whole->var_rel_pos, whole->a0_len, whole->a1_len, nv, esc, wh)) return AVK_E_ARG;
     for (uint64_t r = 0; r < n; ++r) {
         uint64_t c = 0;
-        for (uint64_t i = 0; i < k; ++i) c += whole->in_cnt[r * k + i];
+        for (uint64_t i = 0; i < k; ++i) c += esc ? wh.cnt[r * k + i] : (uint32_t)whole->in_cnt[r * k + i];
         v_first[r + 1] = v_first[r] + c;
     }
     if (v_first[n] != nv) return AVK_E_ARG;
-    for (uint64_t v = 0; v < nv; ++v) a_first[v + 1] = a_first[v] + whole->a0_len[v] + whole->a1_len[v];
+    for (uint64_t v = 0; v < nv; ++v) a_first[v + 1] = a_first[v] + (esc ? (uint64_t)wh.a0[v] + wh.a1[v] : (uint64_t)whole->a0_len[v] + whole->a1_len[v]);
     if (a_first[nv] != whole->allele_bytes_len) return AVK_E_ARG;
     avk_packed_multi_shard *s = new avk_packed_multi_shard();
     memset(&s->b, 0, sizeof(s->b));
@@ -158,6 +206,7 @@ int avk_packed_multi_shard_make(const avk_packed_multi_batch *whole, const uint6
     for (uint64_t j = 0; j < m; ++j) {
         const uint64_t r = s->index[j], v0 = v_first[r], cnt = v_first[r + 1] - v0, ab = a_first[v0 + cnt] - a_first[v0];
         s->start[j] = whole->start[r], s->len[j] = whole->len[r];
+        s->esc.take(esc, r, j, k, v0, cnt, at_v);
         memcpy(s->in_cnt.data() + j * k, whole->in_cnt + r * k, k);
         if (whole->contig_idx) s->contig_idx[j] = whole->contig_idx[r];
         memcpy(s->rel.data() + at_v, whole->var_rel_pos + v0, cnt * 2);
@@ -174,11 +223,13 @@ int avk_packed_multi_shard_make(const avk_packed_multi_batch *whole, const uint6
     s->b.var_rel_pos = s->rel.data(), s->b.var_type_zyg = s->tz.data(), s->b.a0_len = s->a0.data(), s->b.a1_len = s->a1.data();
     s->b.var_raw_space = whole->var_raw_space ? s->raw.data() : nullptr;
     s->b.allele_bytes = s->alleles.data();
+    s->esc.finish();
     *out = s;
     return AVK_E_OK;
 }
 
 const avk_packed_multi_batch *avk_packed_multi_shard_batch(const avk_packed_multi_shard *s) { return s ? &s->b : nullptr; }
+const avk_packed_escapes *avk_packed_multi_shard_escapes(const avk_packed_multi_shard *s) { return s ? &s->esc.e : nullptr; }
 
 uint64_t avk_packed_multi_shard_regions(const avk_packed_multi_shard *s, const uint64_t **index_in_whole) {
     if (!s) return 0;
@@ -224,16 +275,29 @@ uint32_t avk_merge_counts_reason(uint32_t n_inputs, uint8_t classification, uint
 }
 
 int avk_merge_counts(const avk_packed_multi_batch *b, const int32_t *status, const uint8_t *classification, const uint64_t *members, uint64_t *counts) {
+    return avk_merge_counts_esc(b, nullptr, status, classification, members, counts);
+}
+int avk_merge_counts_esc(const avk_packed_multi_batch *b, const avk_packed_escapes *esc, const int32_t *status, const uint8_t *classification, const uint64_t *members,
+                         uint64_t *counts) {
     if (!b || !status || !classification || !members || !counts) return AVK_E_ARG;
     const uint32_t k = b->n_inputs;
     if (avk_merge_counts_len(k) == 0) return AVK_E_ARG;
-    uint64_t v = 0;
+    if (!esc_present(esc) || !esc->n_esc_slots) esc = nullptr; /* (only the counts are read) */
+    if (esc && (!esc->esc_slot || !esc->esc_cnt)) return AVK_E_ARG;
+    for (uint64_t p = 0; esc && p < esc->n_esc_slots; ++p) /* ascending, inside the batch: checked before anything is added to counts[] */
+        if (esc->esc_slot[p] < esc->first_slot || esc->esc_slot[p] - esc->first_slot >= b->n_regions * k || (p && esc->esc_slot[p - 1] >= esc->esc_slot[p])) return AVK_E_ARG;
+    uint64_t v = 0, ps = 0;
     for (uint64_t r = 0; r < b->n_regions; ++r) {
         const uint8_t cls = classification[r];
         if (status[r] == 0 && (cls > AVK_MERGE_CONFLICT_SELECTION || (cls == AVK_MERGE_CONFLICT_SELECTION && members[r] >= k))) return AVK_E_ARG;
         const uint64_t reason = avk_merge_counts_reason(k, cls, members[r]);
         for (uint32_t i = 0; i < k; ++i) {
-            const uint32_t cnt = b->in_cnt[r * k + i];
+            uint32_t cnt = b->in_cnt[r * k + i];
+            if (esc) { /* the slot list in step with the slots */
+                while (ps < esc->n_esc_slots && esc->esc_slot[ps] - esc->first_slot < r * k + i) ++ps;
+                if (ps < esc->n_esc_slots && esc->esc_slot[ps] - esc->first_slot == r * k + i) cnt = esc->esc_cnt[ps];
+            }
+            if (cnt > b->n_variants - v) return AVK_E_ARG;
             if (status[r] == 0) { /* unsolved regions are not added (the reference logs the error and moves on, src/main.rs:481-497) */
                 /* is_passing (:61-72): every input of a BasepairIdentical region, the listed ones otherwise */
                 const bool passing = cls == AVK_MERGE_IDENTICAL || (cls == AVK_MERGE_CONFLICT_SELECTION ? members[r] == i : cls != AVK_MERGE_DIFFERENT && (members[r] >> i & 1));

@@ -273,13 +273,16 @@ int main(int argc, char **argv) {
     /* the feed in the library's packed form (10 bytes per region, 5 per call + allele bytes over PCIe instead of 479 MB per whole genome); the wide arrays
      * stay for the writers.  Ordinary memory: pinning it would cost more than the one pass through the library's bounce buffer it saves. */
     avk_packed_batch packed_all;
+    avk_packed_escapes esc_all; /* the plain pack first; then the pack with escapes (long alleles, long windows, dense sides); only then the wide form */
+    memset(&esc_all, 0, sizeof(esc_all));
     bool packed = false;
     if (want_packed && debug_dir.empty()) {
-        const int rc_pack = avf_feed_pack(feed, [](void *, size_t bytes) { return malloc(bytes); }, nullptr, &packed_all);
+        int rc_pack = avf_feed_pack(feed, [](void *, size_t bytes) { return malloc(bytes); }, nullptr, &packed_all);
+        if (rc_pack == 1) rc_pack = avf_feed_pack_esc(feed, [](void *, size_t bytes) { return malloc(bytes); }, nullptr, &packed_all, &esc_all);
         if (rc_pack < 0) die(70, "cannot pack the region batch", avf_last_error());
         packed = rc_pack == 0;
-        if (!packed && verbosity) fprintf(stderr, "The call set does not fit the packed batch form (window, call count or allele length limits): using the wide form.\n");
     }
+    const bool escaped = packed && (esc_all.n_esc_regions || esc_all.n_esc_slots || esc_all.n_esc_calls);
     /* regions [first + at, +n): as a batch in the chosen form; `out` is indexed by the feed's call arrays either way */
     auto out_for = [](avk_result_batch out, uint64_t v_first) { /* a packed part's results are indexed from its first call */
         if (out.var_expected) out.var_expected += v_first;
@@ -291,17 +294,19 @@ int main(int argc, char **argv) {
     auto compare_part = [&](avk_ctx *c, const avk_region_batch &b, uint64_t at_abs, uint64_t n, const avk_compare_config &cfg, const avk_result_batch &out) -> int {
         if (!packed) return avk_compare_batch(c, &b, &cfg, const_cast<avk_result_batch *>(&out));
         avk_packed_batch part;
+        avk_packed_escapes part_esc;
         uint64_t v_first = 0;
-        if (avf_packed_slice(feed, &packed_all, at_abs, n, &part, &v_first)) return AVK_E_ARG;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, &v_first)) return AVK_E_ARG;
         avk_result_batch shifted = out_for(out, v_first);
-        return avk_compare_packed(c, &part, &cfg, &shifted);
+        return avk_compare_packed_esc(c, &part, &part_esc, &cfg, &shifted);
     };
     auto upload_part = [&](avk_ctx *c, const avk_region_batch &b, uint64_t at_abs, uint64_t n, avk_dev_batch **db, uint64_t *v_first) -> int {
         *v_first = 0;
         if (!packed) return avk_batch_upload(c, &b, db);
         avk_packed_batch part;
-        if (avf_packed_slice(feed, &packed_all, at_abs, n, &part, v_first)) return AVK_E_ARG;
-        return avk_batch_upload_packed(c, &part, db);
+        avk_packed_escapes part_esc;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, v_first)) return AVK_E_ARG;
+        return avk_batch_upload_packed_esc(c, &part, &part_esc, db);
     };
 
     /* --skip / --take select regions by position in the iterator (src/main.rs:215-231) */
@@ -348,12 +353,17 @@ int main(int argc, char **argv) {
     /* --devices with the packed feed and no stratification: the job is cut by the library's ONE rule, shard = hash(region_id) % ranks (avk_region_shard, the rule of
      * aardvark_amd/dist.py), every context solves its shard, and the job tally is summed over the ranks — by one RCCL all-reduce (avk_tally_allreduce) when every
      * context has a GPU of its own, on the host when entries repeat (RCCL does not take two ranks on one device). */
+    if (verbosity)
+        fprintf(stderr, "Batch form: %s (%llu escaped regions, %llu escaped counts, %llu escaped calls); %zu context%s the job.\n",
+                !packed ? "wide" : escaped ? "packed with escapes" : "packed", (unsigned long long)esc_all.n_esc_regions, (unsigned long long)esc_all.n_esc_slots,
+                (unsigned long long)esc_all.n_esc_calls, n_workers, n_workers == 1 ? " solves" : "s solve");
     bool sharded = false;
     if (n_workers > 1 && packed && !n_labels) {
         sharded = true;
         avk_packed_batch sel;
+        avk_packed_escapes sel_esc;
         uint64_t sel_v = 0;
-        if (avf_packed_slice(feed, &packed_all, first, count, &sel, &sel_v)) die(70, "cannot select the regions", avf_last_error());
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, first, count, &sel, &sel_esc, &sel_v)) die(70, "cannot select the regions", avf_last_error());
         bool distinct = true;
         for (size_t i = 0; i < n_workers; ++i)
             for (size_t j = i + 1; j < n_workers; ++j) distinct = distinct && devices[i] != devices[j];
@@ -393,7 +403,7 @@ int main(int argc, char **argv) {
                 (void)avk_ctx_set_option(my, "emit_group_metrics", 0);
             }
             avk_packed_shard *shard = nullptr;
-            if (avk_packed_shard_make(&sel, all->region_id + first, 0, (uint32_t)w, (uint32_t)n_workers, &shard)) worker_err[w] = "cannot cut the shard";
+            if (avk_packed_shard_make_esc(&sel, &sel_esc, all->region_id + first, 0, (uint32_t)w, (uint32_t)n_workers, &shard)) worker_err[w] = "cannot cut the shard";
             else {
                 const avk_packed_batch *sb = avk_packed_shard_batch(shard);
                 std::vector<int32_t> s_status(sb->n_regions + 1);
@@ -401,7 +411,7 @@ int main(int argc, char **argv) {
                 avk_result_batch so;
                 memset(&so, 0, sizeof(so));
                 so.status = s_status.data(), so.var_expected = s_e.data(), so.var_observed = s_o.data(), so.var_class = s_c.data(), so.tally = w_total[w].data();
-                if (avk_compare_packed(my, sb, &cfg, &so)) worker_err[w] = std::string("compare failed: ") + avk_last_error(my);
+                if (avk_compare_packed_esc(my, sb, avk_packed_shard_escapes(shard), &cfg, &so)) worker_err[w] = std::string("compare failed: ") + avk_last_error(my);
                 else {
                     avk_result_batch to; /* the selected regions' part of the job's arrays: regions from `first`, calls from the selection's first call */
                     memset(&to, 0, sizeof(to));

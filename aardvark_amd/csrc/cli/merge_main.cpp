@@ -281,13 +281,16 @@ int main(int argc, char **argv) {
     cfg.conflict_selection = (int32_t)conflict_select;
     /* the feed in the library's packed form (8 + k bytes per region, 5 per call + allele bytes over PCIe instead of the wide arrays); the wide ones stay for the writers */
     avk_packed_multi_batch packed_all;
+    avk_packed_escapes esc_all; /* the plain pack first; then the pack with escapes (long alleles, long windows, dense inputs); only then the wide form */
+    memset(&esc_all, 0, sizeof(esc_all));
     bool packed = false;
     if (want_packed) {
-        const int rc_pack = avf_feed_pack_multi(feed, [](void *, size_t bytes) { return malloc(bytes); }, nullptr, &packed_all);
+        int rc_pack = avf_feed_pack_multi(feed, [](void *, size_t bytes) { return malloc(bytes); }, nullptr, &packed_all);
+        if (rc_pack == 1) rc_pack = avf_feed_pack_multi_esc(feed, [](void *, size_t bytes) { return malloc(bytes); }, nullptr, &packed_all, &esc_all);
         if (rc_pack < 0) die(70, "cannot pack the region batch", avf_last_error());
         packed = rc_pack == 0;
-        if (!packed && verbosity) fprintf(stderr, "The call sets do not fit the packed batch form (window, call count or allele length limits): using the wide form.\n");
     }
+    const bool escaped = packed && (esc_all.n_esc_regions || esc_all.n_esc_slots || esc_all.n_esc_calls);
     std::vector<int32_t> status(all->n_regions + 1, -1); /* regions outside --skip/--take stay unsolved and unwritten */
     std::vector<uint8_t> classification(all->n_regions + 1, 0);
     std::vector<uint64_t> members(all->n_regions + 1, 0);
@@ -299,10 +302,15 @@ int main(int argc, char **argv) {
      * repeat (RCCL does not take two ranks on one device) — and the summary table is written from those sums. */
     const size_t n_ranks = devices.size() >= 2 && packed ? devices.size() : 1;
     const uint64_t counts_len = avk_merge_counts_len(k);
+    if (verbosity)
+        fprintf(stderr, "Batch form: %s (%llu escaped regions, %llu escaped counts, %llu escaped calls); %zu context%s the job.\n",
+                !packed ? "wide" : escaped ? "packed with escapes" : "packed", (unsigned long long)esc_all.n_esc_regions, (unsigned long long)esc_all.n_esc_slots,
+                (unsigned long long)esc_all.n_esc_calls, n_ranks, n_ranks == 1 ? " solves" : "s solve");
     std::vector<uint64_t> job_counts;
     if (n_ranks > 1) {
         avk_packed_multi_batch sel;
-        if (avf_packed_multi_slice(feed, &packed_all, first, count, &sel)) die(70, "cannot select the regions", avf_last_error());
+        avk_packed_escapes sel_esc;
+        if (avf_packed_multi_slice_esc(feed, &packed_all, &esc_all, first, count, &sel, &sel_esc)) die(70, "cannot select the regions", avf_last_error());
         bool distinct = counts_len != 0;
         for (size_t i = 0; i < n_ranks; ++i)
             for (size_t j = i + 1; j < n_ranks; ++j) distinct = distinct && devices[i] != devices[j];
@@ -341,7 +349,7 @@ int main(int argc, char **argv) {
                 }
             }
             avk_packed_multi_shard *shard = nullptr;
-            if (avk_packed_multi_shard_make(&sel, all->region_id + first, 0, (uint32_t)w, (uint32_t)n_ranks, &shard)) {
+            if (avk_packed_multi_shard_make_esc(&sel, &sel_esc, all->region_id + first, 0, (uint32_t)w, (uint32_t)n_ranks, &shard)) {
                 rank_err[w] = "cannot cut the shard";
                 return;
             }
@@ -349,11 +357,12 @@ int main(int argc, char **argv) {
             std::vector<int32_t> s_status(sb->n_regions + 1);
             std::vector<uint8_t> s_cls(sb->n_regions + 1);
             std::vector<uint64_t> s_members(sb->n_regions + 1);
-            if (avk_merge_packed(my, sb, &cfg, s_status.data(), s_cls.data(), s_members.data())) rank_err[w] = std::string("merge failed: ") + avk_last_error(my);
+            const avk_packed_escapes *se = avk_packed_multi_shard_escapes(shard);
+            if (avk_merge_packed_esc(my, sb, se, &cfg, s_status.data(), s_cls.data(), s_members.data())) rank_err[w] = std::string("merge failed: ") + avk_last_error(my);
             else {
                 (void)avk_packed_multi_shard_scatter(shard, s_status.data(), s_cls.data(), s_members.data(), status.data() + first, classification.data() + first,
                                                      members.data() + first);
-                if (counts_len && avk_merge_counts(sb, s_status.data(), s_cls.data(), s_members.data(), r_counts[w].data())) rank_err[w] = "cannot count the shard's variants";
+                if (counts_len && avk_merge_counts_esc(sb, se, s_status.data(), s_cls.data(), s_members.data(), r_counts[w].data())) rank_err[w] = "cannot count the shard's variants";
             }
             avk_packed_multi_shard_free(shard);
         };
@@ -442,8 +451,9 @@ int main(int argc, char **argv) {
             int rc_merge = 0;
             if (packed) {
                 avk_packed_multi_batch part;
-                rc_merge = avf_packed_multi_slice(feed, &packed_all, first + at, n, &part);
-                if (!rc_merge) rc_merge = avk_merge_packed(my, &part, &cfg, status.data() + first + at, classification.data() + first + at, members.data() + first + at);
+                avk_packed_escapes part_esc;
+                rc_merge = avf_packed_multi_slice_esc(feed, &packed_all, &esc_all, first + at, n, &part, &part_esc);
+                if (!rc_merge) rc_merge = avk_merge_packed_esc(my, &part, &part_esc, &cfg, status.data() + first + at, classification.data() + first + at, members.data() + first + at);
             } else
                 rc_merge = avk_merge_batch(my, &b, &cfg, status.data() + first + at, classification.data() + first + at, members.data() + first + at);
             if (rc_merge) {

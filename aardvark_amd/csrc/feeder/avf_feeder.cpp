@@ -1727,6 +1727,169 @@ int avf_packed_multi_slice(const avf_feed *f, const avk_packed_multi_batch *all,
     part->allele_bytes = all->allele_bytes + a0, part->allele_bytes_len = a1 - a0;
     return 0;
 }
+/* ---- the packed forms with escapes (avk_packed_escapes): one packer for the compare and the merge feed — a feed is regions that own `slots` counts each (truth and
+ * query, or the k inputs), calls back to back in slot order, alleles back to back in call order */
+namespace {
+struct EscFeedView {
+    uint64_t n, slots, nv, na;
+    const uint32_t *contig_idx, *cnt_a, *cnt_b; /* cnt_b NULL: cnt_a holds n * slots counts; else slot 2r = cnt_a[r], 2r + 1 = cnt_b[r] */
+    const uint64_t *start, *end, *first_call;   /* first_call[r * stride]: the region's first call */
+    uint64_t stride;
+    const uint64_t *off_a, *off_b;              /* the slots' offsets, for the layout check */
+    const uint64_t *var_pos, *a0_off, *a1_off;
+    const uint32_t *a0_len, *a1_len, *raw;
+    const uint8_t *type, *zyg, *bytes;
+    uint32_t cnt(uint64_t s) const { return cnt_b ? (s & 1 ? cnt_b[s >> 1] : cnt_a[s >> 1]) : cnt_a[s]; }
+    uint64_t off(uint64_t s) const { return off_b ? (s & 1 ? off_b[s >> 1] : off_a[s >> 1]) : off_a[s]; }
+};
+struct EscPacked {
+    uint16_t *contig, *len, *rel;
+    uint32_t *start, *raw;
+    uint8_t *cnt, *tz, *l0, *l1, *bytes;
+};
+/* 0: packed; 1: beyond what the wide form takes (or a layout the packed forms cannot imply); AVK_E_OOM */
+int pack_with_escapes(const EscFeedView &b, void *(*alloc)(void *, size_t), void *user, EscPacked &o, avk_packed_escapes *esc) {
+    memset(esc, 0, sizeof(*esc));
+    if (b.nv >= (1ull << 32) || b.na >= (1ull << 32)) return 1;
+    uint64_t er = 0, es = 0, ec = 0, at = 0;
+    bool raw_differs = false;
+    for (uint64_t r = 0; r < b.n; ++r) {
+        if (b.end[r] < b.start[r] || b.end[r] - b.start[r] > 0xFFFFFFFFull || b.start[r] > 0xFFFFFFFFull || b.contig_idx[r] > 0xFFFF) return 1;
+        er += b.end[r] - b.start[r] > 0xFFFF;
+        for (uint64_t s = r * b.slots; s < (r + 1) * b.slots; ++s) {
+            if (b.off(s) != at) return 1;
+            es += b.cnt(s) > 255;
+            for (uint64_t v = at; v < at + b.cnt(s); ++v)
+                if (v >= b.nv || b.var_pos[v] < b.start[r] || b.var_pos[v] - b.start[r] > 0xFFFFFFFFull) return 1;
+            at += b.cnt(s);
+        }
+    }
+    if (at != b.nv) return 1;
+    uint64_t ab = 0;
+    for (uint64_t v = 0; v < b.nv; ++v) {
+        if (b.type[v] > 15 || b.zyg[v] > 15 || b.a0_off[v] != ab || b.a1_off[v] != ab + b.a0_len[v]) return 1;
+        ab += (uint64_t)b.a0_len[v] + b.a1_len[v];
+        if (b.raw[v] != std::max(b.a0_len[v], b.a1_len[v])) raw_differs = true;
+    }
+    if (b.nv && ab != b.na) return 1;
+    bool oom = false;
+    auto get = [&](size_t bytes) {
+        void *p = alloc(user, bytes ? bytes : 1);
+        if (!p) oom = true;
+        return p;
+    };
+    o.contig = (uint16_t *)get(b.n * 2), o.len = (uint16_t *)get(b.n * 2), o.rel = (uint16_t *)get(b.nv * 2), o.start = (uint32_t *)get(b.n * 4);
+    o.raw = raw_differs ? (uint32_t *)get(b.nv * 4) : nullptr;
+    o.cnt = (uint8_t *)get(b.n * b.slots), o.tz = (uint8_t *)get(b.nv), o.l0 = (uint8_t *)get(b.nv), o.l1 = (uint8_t *)get(b.nv), o.bytes = (uint8_t *)get(b.na);
+    /* the call list's length is known only after the positions are seen: one counting pass over the calls */
+    for (uint64_t r = 0; r < b.n && !oom; ++r) {
+        const uint64_t v0 = b.first_call[r * b.stride];
+        uint64_t calls = 0;
+        for (uint64_t s = r * b.slots; s < (r + 1) * b.slots; ++s) calls += b.cnt(s);
+        for (uint64_t v = v0; v < v0 + calls; ++v) ec += b.var_pos[v] - b.start[r] > 0xFFFF || b.a0_len[v] > 255 || b.a1_len[v] > 255;
+    }
+    uint64_t *x_region = (uint64_t *)get(er * 8), *x_slot = (uint64_t *)get(es * 8), *x_call = (uint64_t *)get(ec * 8);
+    uint32_t *x_len = (uint32_t *)get(er * 4), *x_cnt = (uint32_t *)get(es * 4), *x_rel = (uint32_t *)get(ec * 4), *x_a0 = (uint32_t *)get(ec * 4), *x_a1 = (uint32_t *)get(ec * 4);
+    if (oom) return AVK_E_OOM;
+    er = es = ec = 0;
+    for (uint64_t r = 0; r < b.n; ++r) { /* a listed entry's narrow fields are written as 0 */
+        const uint64_t len = b.end[r] - b.start[r];
+        o.contig[r] = (uint16_t)b.contig_idx[r], o.start[r] = (uint32_t)b.start[r], o.len[r] = len > 0xFFFF ? 0 : (uint16_t)len;
+        if (len > 0xFFFF) x_region[er] = r, x_len[er++] = (uint32_t)len;
+        uint64_t v = b.first_call[r * b.stride];
+        for (uint64_t s = r * b.slots; s < (r + 1) * b.slots; ++s) {
+            const uint32_t c = b.cnt(s);
+            o.cnt[s] = c > 255 ? 0 : (uint8_t)c;
+            if (c > 255) x_slot[es] = s, x_cnt[es++] = c;
+            for (const uint64_t end = v + c; v < end; ++v) {
+                const uint64_t rel = b.var_pos[v] - b.start[r];
+                const bool listed = rel > 0xFFFF || b.a0_len[v] > 255 || b.a1_len[v] > 255;
+                o.rel[v] = listed ? 0 : (uint16_t)rel, o.l0[v] = listed ? 0 : (uint8_t)b.a0_len[v], o.l1[v] = listed ? 0 : (uint8_t)b.a1_len[v];
+                if (listed) x_call[ec] = v, x_rel[ec] = (uint32_t)rel, x_a0[ec] = b.a0_len[v], x_a1[ec++] = b.a1_len[v];
+                o.tz[v] = (uint8_t)(b.type[v] | b.zyg[v] << 4);
+                if (o.raw) o.raw[v] = b.raw[v];
+            }
+        }
+    }
+    if (b.na) memcpy(o.bytes, b.bytes, b.na);
+    esc->n_esc_regions = er, esc->esc_region = x_region, esc->esc_len = x_len, esc->n_esc_slots = es, esc->esc_slot = x_slot, esc->esc_cnt = x_cnt;
+    esc->n_esc_calls = ec, esc->esc_call = x_call, esc->esc_rel_pos = x_rel, esc->esc_a0_len = x_a0, esc->esc_a1_len = x_a1;
+    return 0;
+}
+/* the escapes of regions [first, +n), slots [s0, s1) and calls [v0, v1): pointer ranges of the whole feed's lists, and the bases the listed indices are relative to */
+void slice_escapes(const avk_packed_escapes *all, uint64_t first, uint64_t n, uint64_t s0, uint64_t s1, uint64_t v0, uint64_t v1, avk_packed_escapes *part) {
+    memset(part, 0, sizeof(*part));
+    if (!all) return;
+    auto range = [](const uint64_t *idx, uint64_t count, uint64_t lo, uint64_t hi, uint64_t &a, uint64_t &b) {
+        a = (uint64_t)(std::lower_bound(idx, idx + count, lo) - idx), b = (uint64_t)(std::lower_bound(idx, idx + count, hi) - idx);
+    };
+    uint64_t a, b;
+    part->first_region = all->first_region + first, part->first_slot = all->first_slot + s0, part->first_call = all->first_call + v0;
+    range(all->esc_region, all->n_esc_regions, part->first_region, part->first_region + n, a, b);
+    part->n_esc_regions = b - a, part->esc_region = all->esc_region + a, part->esc_len = all->esc_len + a;
+    range(all->esc_slot, all->n_esc_slots, part->first_slot, all->first_slot + s1, a, b);
+    part->n_esc_slots = b - a, part->esc_slot = all->esc_slot + a, part->esc_cnt = all->esc_cnt + a;
+    range(all->esc_call, all->n_esc_calls, part->first_call, all->first_call + v1, a, b);
+    part->n_esc_calls = b - a, part->esc_call = all->esc_call + a, part->esc_rel_pos = all->esc_rel_pos + a, part->esc_a0_len = all->esc_a0_len + a, part->esc_a1_len = all->esc_a1_len + a;
+}
+} // namespace
+
+int avf_feed_pack_esc(const avf_feed *f, void *(*alloc)(void *, size_t), void *user, avk_packed_batch *out, avk_packed_escapes *esc) {
+    if (!f || f->is_merge || !alloc || !out || !esc) return fail(AVK_E_ARG, "null argument, or a merge feed");
+    const avk_region_batch &b = f->batch;
+    memset(out, 0, sizeof(*out));
+    const EscFeedView v = {b.n_regions, 2, b.n_variants, b.n_variants ? b.allele_bytes_len : 0, b.contig_idx, b.t_cnt, b.q_cnt, b.start, b.end, b.t_off, 1, b.t_off, b.q_off,
+                           b.var_pos, b.a0_off, b.a1_off, b.a0_len, b.a1_len, b.var_raw_space, b.var_type, b.var_zyg, b.allele_bytes};
+    EscPacked o;
+    const int rc = pack_with_escapes(v, alloc, user, o, esc);
+    if (rc < 0) return fail(rc, "the allocator returned NULL for an array of the packed form");
+    if (rc) return rc;
+    /* the interleaved counts as the form's two arrays */
+    uint8_t *tc = (uint8_t *)alloc(user, v.n ? v.n : 1), *qc = (uint8_t *)alloc(user, v.n ? v.n : 1);
+    if (!tc || !qc) return fail(AVK_E_OOM, "the allocator returned NULL for an array of the packed form");
+    for (uint64_t r = 0; r < v.n; ++r) tc[r] = o.cnt[2 * r], qc[r] = o.cnt[2 * r + 1];
+    out->n_regions = v.n, out->contig_idx = o.contig, out->start = o.start, out->len = o.len, out->t_cnt = tc, out->q_cnt = qc;
+    out->n_variants = v.nv, out->var_rel_pos = o.rel, out->var_type_zyg = o.tz, out->a0_len = o.l0, out->a1_len = o.l1, out->var_raw_space = o.raw;
+    out->allele_bytes = o.bytes, out->allele_bytes_len = v.na;
+    return 0;
+}
+
+int avf_packed_slice_esc(const avf_feed *f, const avk_packed_batch *all, const avk_packed_escapes *esc_all, uint64_t first, uint64_t n, avk_packed_batch *part,
+                         avk_packed_escapes *esc_part, uint64_t *v_first) {
+    if (!esc_part) return fail(AVK_E_ARG, "null argument");
+    const int rc = avf_packed_slice(f, all, first, n, part, v_first);
+    if (rc) return rc;
+    slice_escapes(esc_all, first, n, 2 * first, 2 * (first + n), *v_first, *v_first + part->n_variants, esc_part);
+    return 0;
+}
+
+int avf_feed_pack_multi_esc(const avf_feed *f, void *(*alloc)(void *, size_t), void *user, avk_packed_multi_batch *out, avk_packed_escapes *esc) {
+    if (!f || !f->is_merge || !alloc || !out || !esc) return fail(AVK_E_ARG, "null argument, or a compare feed");
+    const avk_multi_batch &b = f->multi;
+    memset(out, 0, sizeof(*out));
+    const EscFeedView v = {b.n_regions, b.n_inputs, b.n_variants, b.n_variants ? b.allele_bytes_len : 0, b.contig_idx, b.in_cnt, nullptr, b.start, b.end, b.in_off, b.n_inputs,
+                           b.in_off, nullptr, b.var_pos, b.a0_off, b.a1_off, b.a0_len, b.a1_len, b.var_raw_space, b.var_type, b.var_zyg, b.allele_bytes};
+    EscPacked o;
+    const int rc = pack_with_escapes(v, alloc, user, o, esc);
+    if (rc < 0) return fail(rc, "the allocator returned NULL for an array of the packed form");
+    if (rc) return rc;
+    out->n_regions = v.n, out->n_inputs = b.n_inputs, out->contig_idx = o.contig, out->start = o.start, out->len = o.len, out->in_cnt = o.cnt;
+    out->n_variants = v.nv, out->var_rel_pos = o.rel, out->var_type_zyg = o.tz, out->a0_len = o.l0, out->a1_len = o.l1, out->var_raw_space = o.raw;
+    out->allele_bytes = o.bytes, out->allele_bytes_len = v.na;
+    return 0;
+}
+
+int avf_packed_multi_slice_esc(const avf_feed *f, const avk_packed_multi_batch *all, const avk_packed_escapes *esc_all, uint64_t first, uint64_t n,
+                               avk_packed_multi_batch *part, avk_packed_escapes *esc_part) {
+    if (!esc_part) return fail(AVK_E_ARG, "null argument");
+    const int rc = avf_packed_multi_slice(f, all, first, n, part);
+    if (rc) return rc;
+    const avk_multi_batch &b = f->multi;
+    const uint64_t k = b.n_inputs, v0 = first < b.n_regions ? b.in_off[first * k] : b.n_variants;
+    slice_escapes(esc_all, first, n, first * k, (first + n) * k, v0, v0 + part->n_variants, esc_part);
+    return 0;
+}
+
 const uint64_t *avf_feed_var_record(const avf_feed *f) { return f ? f->var_record.data() : nullptr; }
 const uint32_t *avf_feed_var_alt_index(const avf_feed *f) { return f ? f->var_alt.data() : nullptr; }
 uint64_t avf_feed_loaded_variants(const avf_feed *f, int input) { return f && input >= 0 && (size_t)input < f->loaded.size() ? f->loaded[input] : 0; }

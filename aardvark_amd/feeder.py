@@ -139,15 +139,27 @@ class Feed:
     """The result of RegionIterator over a truth/query VCF pair: a RegionBatch plus provenance; `packed` = the same batch in the packed form
     (avf_feed_pack -> PackedBatch; merge feeds: avf_feed_pack_multi -> merge.PackedMultiBatch), None when the call sets do not fit that form."""
 
-    def __init__(self, batch, var_record, var_alt_index, loaded, packed=None):
+    def __init__(self, batch, var_record, var_alt_index, loaded, packed=None, packed_esc=None):
         self.batch, self.var_record, self.var_alt_index, self.loaded, self.packed = batch, var_record, var_alt_index, loaded, packed
+        # the feed packed WITH escapes (avf_feed_pack_esc / avf_feed_pack_multi_esc: a PackedBatch / PackedMultiBatch whose .escapes lists what the narrow fields
+        # cannot hold), taken when the plain pack refused the feed; None otherwise, or when the wide form's own limits refuse it too
+        self.packed_esc = packed_esc
 
 
 _ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
 
-def _take_packed_multi(lib, h):
-    """avf_feed_pack_multi into numpy-owned buffers -> merge.PackedMultiBatch, or None when the feed does not fit the form"""
+def _escapes_of(esc, view):
+    from ._abi import PackedEscapes
+    nr, ns, nc = int(esc.n_esc_regions), int(esc.n_esc_slots), int(esc.n_esc_calls)
+    return PackedEscapes(int(esc.first_region), int(esc.first_call), int(esc.first_slot), esc_region=view(esc.esc_region, nr, np.uint64), esc_len=view(esc.esc_len, nr, np.uint32),
+                         esc_slot=view(esc.esc_slot, ns, np.uint64), esc_cnt=view(esc.esc_cnt, ns, np.uint32), esc_call=view(esc.esc_call, nc, np.uint64),
+                         esc_rel_pos=view(esc.esc_rel_pos, nc, np.uint32), esc_a0_len=view(esc.esc_a0_len, nc, np.uint32), esc_a1_len=view(esc.esc_a1_len, nc, np.uint32))
+
+
+def _take_packed_multi(lib, h, escapes=False):
+    """avf_feed_pack_multi (escapes: avf_feed_pack_multi_esc) into numpy-owned buffers -> merge.PackedMultiBatch, or None when the feed does not fit the form"""
+    from ._abi import AvkPackedEscapes
     from .merge import AvkPackedMultiBatch, PackedMultiBatch
     bufs = {}
 
@@ -158,8 +170,10 @@ def _take_packed_multi(lib, h):
 
     cb = _ALLOC(alloc)
     out = AvkPackedMultiBatch()
+    esc = AvkPackedEscapes()
     lib.avf_feed_pack_multi.argtypes = [C.c_void_p, _ALLOC, C.c_void_p, C.POINTER(AvkPackedMultiBatch)]
-    rc = lib.avf_feed_pack_multi(h, cb, None, C.byref(out))
+    lib.avf_feed_pack_multi_esc.argtypes = [C.c_void_p, _ALLOC, C.c_void_p, C.POINTER(AvkPackedMultiBatch), C.POINTER(AvkPackedEscapes)]
+    rc = lib.avf_feed_pack_multi_esc(h, cb, None, C.byref(out), C.byref(esc)) if escapes else lib.avf_feed_pack_multi(h, cb, None, C.byref(out))
     if rc == 1:
         return None
     _check(lib, rc)
@@ -171,15 +185,15 @@ def _take_packed_multi(lib, h):
             return None
         return bufs[addr][:count * np.dtype(dtype).itemsize].view(dtype)
 
-    return PackedMultiBatch(k, contig_idx=view(out.contig_idx, n, np.uint16), start=view(out.start, n, np.uint32), len=view(out.len, n, np.uint16),
+    return PackedMultiBatch(k, escapes=_escapes_of(esc, view) if escapes else None, contig_idx=view(out.contig_idx, n, np.uint16), start=view(out.start, n, np.uint32), len=view(out.len, n, np.uint16),
                             in_cnt=view(out.in_cnt, n * k, np.uint8), var_rel_pos=view(out.var_rel_pos, nv, np.uint16), var_type_zyg=view(out.var_type_zyg, nv, np.uint8),
                             a0_len=view(out.a0_len, nv, np.uint8), a1_len=view(out.a1_len, nv, np.uint8), var_raw_space=view(out.var_raw_space, nv, np.uint32),
                             allele_bytes=view(out.allele_bytes, max(na, 1), np.uint8))
 
 
-def _take_packed(lib, h):
-    """avf_feed_pack into numpy-owned buffers -> PackedBatch, or None when the feed does not fit the form"""
-    from ._abi import AvkPackedBatch, PackedBatch
+def _take_packed(lib, h, escapes=False):
+    """avf_feed_pack (escapes: avf_feed_pack_esc) into numpy-owned buffers -> PackedBatch, or None when the feed does not fit the form"""
+    from ._abi import AvkPackedBatch, AvkPackedEscapes, PackedBatch
     bufs = {}
 
     def alloc(_user, nbytes):
@@ -189,8 +203,10 @@ def _take_packed(lib, h):
 
     cb = _ALLOC(alloc)
     out = AvkPackedBatch()
+    esc = AvkPackedEscapes()
     lib.avf_feed_pack.argtypes = [C.c_void_p, _ALLOC, C.c_void_p, C.POINTER(AvkPackedBatch)]
-    rc = lib.avf_feed_pack(h, cb, None, C.byref(out))
+    lib.avf_feed_pack_esc.argtypes = [C.c_void_p, _ALLOC, C.c_void_p, C.POINTER(AvkPackedBatch), C.POINTER(AvkPackedEscapes)]
+    rc = lib.avf_feed_pack_esc(h, cb, None, C.byref(out), C.byref(esc)) if escapes else lib.avf_feed_pack(h, cb, None, C.byref(out))
     if rc == 1:
         return None
     _check(lib, rc)
@@ -202,10 +218,17 @@ def _take_packed(lib, h):
             return None
         return bufs[addr][:count * np.dtype(dtype).itemsize].view(dtype)
 
-    return PackedBatch(contig_idx=view(out.contig_idx, n, np.uint16), start=view(out.start, n, np.uint32), len=view(out.len, n, np.uint16),
-                       t_cnt=view(out.t_cnt, n, np.uint8), q_cnt=view(out.q_cnt, n, np.uint8), var_rel_pos=view(out.var_rel_pos, nv, np.uint16),
+    return PackedBatch(escapes=_escapes_of(esc, view) if escapes else None, contig_idx=view(out.contig_idx, n, np.uint16), start=view(out.start, n, np.uint32),
+                       len=view(out.len, n, np.uint16), t_cnt=view(out.t_cnt, n, np.uint8), q_cnt=view(out.q_cnt, n, np.uint8), var_rel_pos=view(out.var_rel_pos, nv, np.uint16),
                        var_type_zyg=view(out.var_type_zyg, nv, np.uint8), a0_len=view(out.a0_len, nv, np.uint8), a1_len=view(out.a1_len, nv, np.uint8),
                        var_raw_space=view(out.var_raw_space, nv, np.uint32), allele_bytes=view(out.allele_bytes, na, np.uint8))
+
+
+def _both_packed(lib, h, merge):
+    """(Feed.packed, Feed.packed_esc): the plain pack first, the pack with escapes when it refuses"""
+    take = _take_packed_multi if merge else _take_packed
+    plain = take(lib, h)
+    return plain, (take(lib, h, escapes=True) if plain is None else None)
 
 
 def vcf_sample_name(vcf, index=0):
@@ -267,7 +290,7 @@ def _take_feed(lib, h, k, merge):
                                 _arr(b.a0_off, nv, np.uint64), _arr(b.a0_len, nv, np.uint32), _arr(b.a1_off, nv, np.uint64), _arr(b.a1_len, nv, np.uint32),
                                 _arr(b.allele_bytes, int(b.allele_bytes_len), np.uint8))
         return Feed(batch, _arr(lib.avf_feed_var_record(h), nv, np.uint64), _arr(lib.avf_feed_var_alt_index(h), nv, np.uint32),
-                    tuple(int(lib.avf_feed_loaded_variants(h, i)) for i in range(k)), _take_packed_multi(lib, h) if merge else _take_packed(lib, h))
+                    tuple(int(lib.avf_feed_loaded_variants(h, i)) for i in range(k)), *_both_packed(lib, h, merge))
     finally:
         lib.avf_feed_free(h)
 
@@ -286,7 +309,7 @@ def feed_compare(truth_vcf, query_vcf, regions_bed, genome, truth_sample="", que
                             _arr(b.a0_off, nv, np.uint64), _arr(b.a0_len, nv, np.uint32), _arr(b.a1_off, nv, np.uint64), _arr(b.a1_len, nv, np.uint32),
                             _arr(b.allele_bytes, int(b.allele_bytes_len), np.uint8))
         return Feed(batch, _arr(lib.avf_feed_var_record(h), nv, np.uint64), _arr(lib.avf_feed_var_alt_index(h), nv, np.uint32),
-                    (int(lib.avf_feed_loaded_variants(h, 0)), int(lib.avf_feed_loaded_variants(h, 1))), _take_packed(lib, h))
+                    (int(lib.avf_feed_loaded_variants(h, 0)), int(lib.avf_feed_loaded_variants(h, 1))), *_both_packed(lib, h, False))
     finally:
         lib.avf_feed_free(h)
 
@@ -410,7 +433,7 @@ def feed_merge(vcfs, regions_bed, genome, samples=None, min_variant_gap=50, enab
                         a1_off=_arr(b.a1_off, nv, np.uint64), a1_len=_arr(b.a1_len, nv, np.uint32),
                         allele_bytes=_arr(b.allele_bytes, int(b.allele_bytes_len), np.uint8))
         return Feed(mb, _arr(lib.avf_feed_var_record(h), nv, np.uint64), _arr(lib.avf_feed_var_alt_index(h), nv, np.uint32),
-                    tuple(int(lib.avf_feed_loaded_variants(h, i)) for i in range(k)), _take_packed_multi(lib, h))
+                    tuple(int(lib.avf_feed_loaded_variants(h, i)) for i in range(k)), *_both_packed(lib, h, True))
     finally:
         lib.avf_feed_free(h)
 

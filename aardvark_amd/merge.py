@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import ZYG, RegionBatch
+from ._abi import ZYG, AvkPackedEscapes, PackedEscapes, RegionBatch
 
 
 class MergeConfig:
@@ -172,17 +172,63 @@ class PackedMultiBatch:
     FIELDS = ("contig_idx", "start", "len", "in_cnt", "var_rel_pos", "var_type_zyg", "a0_len", "a1_len", "var_raw_space", "allele_bytes")
     DTYPES = (np.uint16, np.uint32, np.uint16, np.uint8, np.uint16, np.uint8, np.uint8, np.uint8, np.uint32, np.uint8)
 
-    def __init__(self, n_inputs, **arrays):
+    def __init__(self, n_inputs, escapes=None, **arrays):
         self.n_inputs = int(n_inputs)
         for name, dt in zip(self.FIELDS, self.DTYPES):
             a = arrays.get(name)
             setattr(self, name, None if a is None else np.ascontiguousarray(a, dtype=dt))
         self.n_regions = int(self.start.size)
         self.n_variants = int(self.var_rel_pos.size)
+        self.escapes = escapes  # a PackedEscapes (count slot m * k + i = in_cnt[m * k + i]), or None
         assert self.in_cnt.size == self.n_regions * self.n_inputs
 
     @classmethod
-    def from_multi(cls, mb, keep_raw_space=None):
+    def _from_multi_escaped(cls, mb, keep_raw_space):
+        n, nv, k = mb.n_regions, mb.n_variants, mb.n_inputs
+        cnt = mb.in_cnt.astype(np.int64)
+        ioff = np.concatenate([[0], np.cumsum(cnt)])
+        a0, a1 = mb.a0_len.astype(np.int64), mb.a1_len.astype(np.int64)
+        aoff = np.concatenate([[0], np.cumsum(a0 + a1)])
+        nbytes = int(aoff[-1])
+        ok = (np.array_equal(mb.in_off, ioff[:-1]) and int(ioff[-1]) == nv and np.array_equal(mb.a0_off, aoff[:-1]) and np.array_equal(mb.a1_off, aoff[:-1] + mb.a0_len) and
+              (nv == 0 or nbytes == mb.allele_bytes.size) and bool(np.all(mb.end >= mb.start)) and
+              (n == 0 or (int(mb.start.max()) < 2 ** 32 and int((mb.end - mb.start).max()) < 2 ** 32 and int(mb.contig_idx.max()) < 65536)) and
+              (nv == 0 or (int(mb.var_type.max()) < 16 and int(mb.var_zyg.max()) < 16)))
+        rel = None
+        if ok:
+            per_region = cnt.reshape(n, k).sum(axis=1) if n else np.zeros(0, np.int64)
+            rel = mb.var_pos.astype(np.int64) - np.repeat(mb.start.astype(np.int64), per_region)
+            ok = nv == 0 or (int(rel.min()) >= 0 and int(rel.max()) < 2 ** 32)
+        if not ok:
+            raise ValueError("the batch does not satisfy the constraints of the packed form with escapes (include/aardvark_amd.h: avk_packed_escapes)")
+        length = (mb.end - mb.start).astype(np.int64)
+        esc = PackedEscapes.build(length, cnt, rel, a0, a1)
+        length[esc.esc_region.astype(np.int64)] = 0  # a listed entry's narrow fields are written as 0
+        cnt[esc.esc_slot.astype(np.int64)] = 0
+        v = esc.esc_call.astype(np.int64)
+        rel[v], a0[v], a1[v] = 0, 0, 0
+        if keep_raw_space is None:
+            keep_raw_space = not np.array_equal(mb.var_raw_space, np.maximum(mb.a0_len, mb.a1_len))
+        return cls(k, escapes=esc, contig_idx=mb.contig_idx, start=mb.start, len=length, in_cnt=cnt, var_rel_pos=rel, var_type_zyg=mb.var_type | (mb.var_zyg << 4),
+                   a0_len=a0, a1_len=a1, var_raw_space=mb.var_raw_space if keep_raw_space else None, allele_bytes=mb.allele_bytes[:nbytes] if nv else np.zeros(1, np.uint8))
+
+    def _wide_fields(self):
+        """(len, in_cnt, relative positions, a0_len, a1_len) as int64 with the escapes applied"""
+        length, cnt, rel = self.len.astype(np.int64), self.in_cnt.astype(np.int64), self.var_rel_pos.astype(np.int64)
+        a0, a1 = self.a0_len.astype(np.int64), self.a1_len.astype(np.int64)
+        if self.escapes is not None:
+            self.escapes.apply(length, cnt, rel, a0, a1)
+        return length, cnt, rel, a0, a1
+
+    def c_escapes(self):
+        """the avk_packed_escapes to hand in with c_struct(), or None when the batch lists nothing"""
+        return None if self.escapes is None or self.escapes.empty() else self.escapes.c_struct()
+
+    @classmethod
+    def from_multi(cls, mb, keep_raw_space=None, escapes=False):
+        """escapes=True: values that do not fit the narrow fields go to the batch's PackedEscapes instead of raising"""
+        if escapes:
+            return cls._from_multi_escaped(mb, keep_raw_space)
         n, nv, k = mb.n_regions, mb.n_variants, mb.n_inputs
         cnt = mb.in_cnt.astype(np.int64)
         ioff = np.concatenate([[0], np.cumsum(cnt)])
@@ -209,18 +255,18 @@ class PackedMultiBatch:
     def widen(self):
         """back to the wide form (what the library's dp_widen_packed_multi kernel writes on the device)"""
         n, k = self.n_regions, self.n_inputs
-        cnt = self.in_cnt.astype(np.int64)
+        length, cnt, rel, a0, a1 = self._wide_fields()
         ioff = np.concatenate([[0], np.cumsum(cnt)])[:-1]
-        aoff = np.concatenate([[0], np.cumsum(self.a0_len.astype(np.int64) + self.a1_len)])[:-1]
+        aoff = np.concatenate([[0], np.cumsum(a0 + a1)])[:-1]
         per_region = cnt.reshape(n, k).sum(axis=1) if n else np.zeros(0, np.int64)
-        raw = self.var_raw_space if self.var_raw_space is not None else np.maximum(self.a0_len, self.a1_len)
+        raw = self.var_raw_space if self.var_raw_space is not None else np.maximum(a0, a1)
         return MultiBatch(k, region_id=np.arange(n), contig_idx=self.contig_idx if self.contig_idx is not None else np.zeros(n), start=self.start,
-                          end=self.start.astype(np.uint64) + self.len, in_off=ioff, in_cnt=self.in_cnt, var_pos=np.repeat(self.start.astype(np.int64), per_region) + self.var_rel_pos,
-                          var_type=self.var_type_zyg & 15, var_zyg=self.var_type_zyg >> 4, var_raw_space=raw, a0_off=aoff, a0_len=self.a0_len, a1_off=aoff + self.a0_len,
-                          a1_len=self.a1_len, allele_bytes=self.allele_bytes)
+                          end=self.start.astype(np.int64) + length, in_off=ioff, in_cnt=cnt, var_pos=np.repeat(self.start.astype(np.int64), per_region) + rel,
+                          var_type=self.var_type_zyg & 15, var_zyg=self.var_type_zyg >> 4, var_raw_space=raw, a0_off=aoff, a0_len=a0, a1_off=aoff + a0,
+                          a1_len=a1, allele_bytes=self.allele_bytes)
 
     def nbytes(self):
-        return sum(getattr(self, f).nbytes for f in self.FIELDS if getattr(self, f) is not None)
+        return sum(getattr(self, f).nbytes for f in self.FIELDS if getattr(self, f) is not None) + (self.escapes.nbytes() if self.escapes is not None else 0)
 
     def c_struct(self):
         b = AvkPackedMultiBatch()
@@ -268,6 +314,8 @@ def pinned_multi_batch(ctx, mb):
         out = ctx.host_array(a.shape, a.dtype)
         out[...] = a
         arrays[name] = out
+    if getattr(mb, "escapes", None) is not None:
+        arrays["escapes"] = mb.escapes.pinned(ctx.host_array)
     return type(mb)(mb.n_inputs, **arrays)
 
 
@@ -283,6 +331,13 @@ def merge_multi_batch(ctx, mb, config=None):
     P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
     cb = mb.c_struct()
     packed = isinstance(mb, PackedMultiBatch)
+    esc = mb.c_escapes() if packed else None
+    if esc is not None:
+        entry = ctx.lib.avk_merge_packed_esc
+        entry.argtypes = [C.c_void_p, C.POINTER(AvkPackedMultiBatch), C.POINTER(AvkPackedEscapes), C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
+                          C.POINTER(C.c_uint64)]
+        ctx._check(entry(ctx.handle, C.byref(cb), C.byref(esc), C.byref(cfg), P(st, C.c_int32), P(cls, C.c_uint8), P(members, C.c_uint64)))
+        return MergeResult(st[:n], cls[:n], members[:n], mb.n_inputs)
     entry = ctx.lib.avk_merge_packed if packed else ctx.lib.avk_merge_batch
     entry.argtypes = [C.c_void_p, C.POINTER(AvkPackedMultiBatch if packed else AvkMultiBatch), C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
     ctx._check(entry(ctx.handle, C.byref(cb), C.byref(cfg), P(st, C.c_int32), P(cls, C.c_uint8), P(members, C.c_uint64)))
@@ -319,6 +374,11 @@ def _shard_api(lib):
     lib.avk_merge_counts_reason.argtypes = [C.c_uint32, C.c_uint8, C.c_uint64]
     lib.avk_merge_counts.argtypes = [P(AvkPackedMultiBatch), P(C.c_int32), P(C.c_uint8), P(C.c_uint64), P(C.c_uint64)]
     lib.avk_counts_allreduce.argtypes = [C.c_void_p, C.c_void_p, P(C.c_uint64), C.c_uint64]
+    # packed batches with escapes
+    lib.avk_packed_multi_shard_make_esc.argtypes = [P(AvkPackedMultiBatch), P(AvkPackedEscapes), P(C.c_uint64), C.c_uint64, C.c_uint32, C.c_uint32, P(C.c_void_p)]
+    lib.avk_packed_multi_shard_escapes.restype = P(AvkPackedEscapes)
+    lib.avk_packed_multi_shard_escapes.argtypes = [C.c_void_p]
+    lib.avk_merge_counts_esc.argtypes = [P(AvkPackedMultiBatch), P(AvkPackedEscapes), P(C.c_int32), P(C.c_uint8), P(C.c_uint64), P(C.c_uint64)]
     lib._avk_multi_shard_api = True
     return lib
 
@@ -330,14 +390,19 @@ def shard_packed_multi(lib, pmb, region_id, rank, world):
     ids = np.ascontiguousarray(region_id, np.uint64)
     cb = pmb.c_struct()
     h = C.c_void_p()
-    rc = lib.avk_packed_multi_shard_make(C.byref(cb), ids.ctypes.data_as(C.POINTER(C.c_uint64)), 0, rank, world, C.byref(h))
+    esc = pmb.c_escapes()
+    if esc is None:
+        rc = lib.avk_packed_multi_shard_make(C.byref(cb), ids.ctypes.data_as(C.POINTER(C.c_uint64)), 0, rank, world, C.byref(h))
+    else:
+        rc = lib.avk_packed_multi_shard_make_esc(C.byref(cb), C.byref(esc), ids.ctypes.data_as(C.POINTER(C.c_uint64)), 0, rank, world, C.byref(h))
     if rc:
         raise ValueError("avk_packed_multi_shard_make failed (%d)" % rc)
     try:
         b = lib.avk_packed_multi_shard_batch(h).contents
         n, nv, na, k = int(b.n_regions), int(b.n_variants), int(b.allele_bytes_len), int(b.n_inputs)
         take = lambda ptr, m, dt: np.ctypeslib.as_array(ptr, shape=(max(m, 1),))[:m].astype(dt).copy() if ptr else None
-        shard = PackedMultiBatch(k, contig_idx=take(b.contig_idx, n, np.uint16), start=take(b.start, n, np.uint32), len=take(b.len, n, np.uint16),
+        shard_esc = None if pmb.escapes is None else (PackedEscapes() if esc is None else PackedEscapes.from_c(lib.avk_packed_multi_shard_escapes(h).contents))
+        shard = PackedMultiBatch(k, escapes=shard_esc, contig_idx=take(b.contig_idx, n, np.uint16), start=take(b.start, n, np.uint32), len=take(b.len, n, np.uint16),
                                  in_cnt=take(b.in_cnt, n * k, np.uint8), var_rel_pos=take(b.var_rel_pos, nv, np.uint16), var_type_zyg=take(b.var_type_zyg, nv, np.uint8),
                                  a0_len=take(b.a0_len, nv, np.uint8), a1_len=take(b.a1_len, nv, np.uint8), var_raw_space=take(b.var_raw_space, nv, np.uint32),
                                  allele_bytes=take(b.allele_bytes, na, np.uint8) if nv else np.zeros(1, np.uint8))
@@ -367,7 +432,11 @@ def merge_counts(lib, pmb, result, counts=None):
     if pmb.n_regions == 0:
         return counts
     cb = pmb.c_struct()
-    rc = lib.avk_merge_counts(C.byref(cb), P(st, C.c_int32), P(cls, C.c_uint8), P(mem, C.c_uint64), counts.ctypes.data_as(C.POINTER(C.c_uint64)))
+    esc = pmb.c_escapes()
+    if esc is None:
+        rc = lib.avk_merge_counts(C.byref(cb), P(st, C.c_int32), P(cls, C.c_uint8), P(mem, C.c_uint64), counts.ctypes.data_as(C.POINTER(C.c_uint64)))
+    else:
+        rc = lib.avk_merge_counts_esc(C.byref(cb), C.byref(esc), P(st, C.c_int32), P(cls, C.c_uint8), P(mem, C.c_uint64), counts.ctypes.data_as(C.POINTER(C.c_uint64)))
     if rc:
         raise ValueError("avk_merge_counts failed (%d)" % rc)
     return counts

@@ -155,7 +155,8 @@ typedef struct avk_compact_batch {
  * carry is implied by order: the calls of region r follow those of region r - 1 (truth calls, then query calls), the alleles of call v follow those of
  * call v - 1 (allele0, then allele1), call positions are relative to their region's start.  The library computes the offsets on the device (two prefix
  * sums) and writes the wide arrays there.  A whole genome: 94 MB over PCIe instead of 227 (compact) or 479 (wide).  Constraints: windows shorter than
- * 65,536 bases, at most 255 calls per region and side, alleles of at most 255 bases, fewer than 2^32 calls and allele bytes, contigs shorter than 4 Gbp,
+ * 65,536 bases, at most 255 calls per region and side, alleles of at most 255 bases — these three hold WITHOUT ESCAPES: a batch handed in with an
+ * avk_packed_escapes (below) lists the few regions, counts and calls that exceed them —, fewer than 2^32 calls and allele bytes, contigs shorter than 4 Gbp,
  * at most 65,535 contigs.  Results are indexed like the arrays here. */
 typedef struct avk_packed_batch {
     uint64_t n_regions;
@@ -171,6 +172,32 @@ typedef struct avk_packed_batch {
     const uint8_t  *allele_bytes;  /* allele0 then allele1 of call 0, of call 1, ... */
     uint64_t allele_bytes_len;     /* = sum of a0_len + a1_len */
 } avk_packed_batch;
+
+/* ESCAPES of a packed batch (avk_packed_batch and avk_packed_multi_batch alike): sparse overrides for the few entries whose values do not fit the narrow
+ * fields, so that one 300-base insertion, one window of 65,536 bases or one side with 256 calls no longer costs a call set the packed form.  Three sorted
+ * lists; an entry that is listed takes its value(s) from the list, its narrow field(s) are ignored and MUST be written as 0 (the running sums over the narrow
+ * arrays then count it as nothing, and the library adds the listed values); an entry that is not listed means what it means without escapes.
+ *   regions  esc_region[] ascending region indices; esc_len[] the window length (end - start)
+ *   counts   esc_slot[] ascending count slots; esc_cnt[] the count.  Compare form: slot 2r = t_cnt of region r, slot 2r + 1 = q_cnt of region r;
+ *            multi form: slot m * k + i = in_cnt[m * k + i]
+ *   calls    esc_call[] ascending call indices; esc_rel_pos[], esc_a0_len[], esc_a1_len[] replace all THREE narrow fields of the call
+ * The indices are those of a larger batch this one is a slice of: region r of the batch is listed as first_region + r, its count slots as first_slot + ..,
+ * call v as first_call + v — a slice of a batch is its pointer ranges plus these three bases, no copy.  What is left are the wide form's own limits: fewer
+ * than 2^32 calls and allele bytes, contigs shorter than 4 Gbp, at most 65,535 contigs, and per region what INTEGRATION.md section 4 states (60,000 calls,
+ * windows and alleles of 2^31 bases): AVK_E_ARG or AVK_ST_INVALID_INPUT exactly as for the same batch handed in wide.  A NULL pointer or three zero
+ * counts: no escapes.  A list that is not ascending, or names an entry outside the batch, is AVK_E_ARG. */
+typedef struct avk_packed_escapes {
+    uint64_t first_region, first_call, first_slot;
+    uint64_t n_esc_regions;
+    const uint64_t *esc_region;    /* [n_esc_regions] */
+    const uint32_t *esc_len;       /* [n_esc_regions] */
+    uint64_t n_esc_slots;
+    const uint64_t *esc_slot;      /* [n_esc_slots] */
+    const uint32_t *esc_cnt;       /* [n_esc_slots] */
+    uint64_t n_esc_calls;
+    const uint64_t *esc_call;      /* [n_esc_calls] */
+    const uint32_t *esc_rel_pos, *esc_a0_len, *esc_a1_len; /* [n_esc_calls] */
+} avk_packed_escapes;
 
 /* CompareConfig, src/waffle_solver.rs:94-115 */
 typedef struct avk_compare_config {
@@ -340,6 +367,9 @@ int  avk_compare_compact(avk_ctx *ctx, const avk_compact_batch *batch, const avk
 int  avk_batch_upload_compact(avk_ctx *ctx, const avk_compact_batch *batch, avk_dev_batch **out);
 /* and in the packed form (replaces the same loop, src/main.rs:251-268; the batch crosses PCIe as 94 MB per whole genome) */
 int  avk_compare_packed(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out);
+/* the same for a packed batch with escapes (esc may be NULL: avk_compare_packed is this call with NULL).  An escaped batch is widened on the device by
+ * escape-aware kernels (avk_devpack.inl: dp_widen_packed_esc) and planned from the wide arrays: same work plan, same results as the batch handed in wide. */
+int  avk_compare_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_compare_config *cfg, avk_result_batch *out);
 
 /* The same call in two halves, for a caller with several batches (the reference streams its regions through one rayon loop and collects at the end,
  * src/main.rs:251-268): batches in flight inside ONE context.  avk_compare_packed_submit copies the batch's arrays on the context's copy stream — beside the
@@ -366,7 +396,12 @@ static inline uint32_t avk_region_shard(uint64_t region_id, uint32_t ranks) { re
  * by call; the tally is left to the caller: add the ranks' tallies, or avk_tally_allreduce) */
 typedef struct avk_packed_shard avk_packed_shard;
 int  avk_packed_shard_make(const avk_packed_batch *whole, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world, avk_packed_shard **out);
+/* with escapes: the shard owns escape lists of its own, rebased to the shard's indices (bases 0); avk_packed_shard_escapes returns them (counts 0 when the
+ * shard holds no escaped entry) */
+int  avk_packed_shard_make_esc(const avk_packed_batch *whole, const avk_packed_escapes *esc, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world,
+                               avk_packed_shard **out);
 const avk_packed_batch *avk_packed_shard_batch(const avk_packed_shard *s);
+const avk_packed_escapes *avk_packed_shard_escapes(const avk_packed_shard *s);
 uint64_t avk_packed_shard_regions(const avk_packed_shard *s, const uint64_t **index_in_whole);
 int  avk_packed_shard_scatter(const avk_packed_shard *s, const avk_result_batch *shard_results, avk_result_batch *whole_results);
 void avk_packed_shard_free(avk_packed_shard *s);
@@ -380,6 +415,11 @@ typedef struct avk_ticket avk_ticket;
 int  avk_compare_packed_submit(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket);
 int  avk_wait(avk_ctx *ctx, avk_ticket *ticket);
 int  avk_batch_upload_packed(avk_ctx *ctx, const avk_packed_batch *batch, avk_dev_batch **out);
+/* both with escapes (NULL: the calls above).  For a submit to stay asynchronous the escape lists must be pinned like the batch's arrays: they are copied on the
+ * copy stream with the rest */
+int  avk_compare_packed_submit_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_compare_config *cfg, avk_result_batch *out,
+                                   avk_ticket **ticket);
+int  avk_batch_upload_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, avk_dev_batch **out);
 
 /* The same in three steps, for callers that keep batches resident in HBM. */
 int  avk_batch_upload(avk_ctx *ctx, const avk_region_batch *batch, avk_dev_batch **out);
@@ -508,8 +548,8 @@ typedef struct avk_multi_batch {
 /* The same batch in the PACKED form (round 3; avk_packed_batch's rules): every offset implied by order — the calls of region m follow those of region
  * m - 1, input by input; the alleles of call v follow those of call v - 1 (allele0, then allele1); call positions are relative to their region's start.
  * 8 + k bytes per region and 5 per call plus the allele bytes: a three-caller whole genome crosses PCIe as 0.13 GB instead of 0.72.  Constraints: windows
- * shorter than 65,536 bases, at most 255 calls per region and input, alleles of at most 255 bases, fewer than 2^32 calls and allele bytes, contigs shorter
- * than 4 Gbp, at most 65,535 contigs. */
+ * shorter than 65,536 bases, at most 255 calls per region and input, alleles of at most 255 bases — these three hold WITHOUT ESCAPES (avk_packed_escapes;
+ * count slot m * k + i is in_cnt[m * k + i]) —, fewer than 2^32 calls and allele bytes, contigs shorter than 4 Gbp, at most 65,535 contigs. */
 typedef struct avk_packed_multi_batch {
     uint64_t n_regions;
     uint32_t n_inputs;               /* k, 2..64 */
@@ -536,6 +576,9 @@ int avk_merge_batch(avk_ctx *ctx, const avk_multi_batch *batch, const avk_merge_
 /* the same for a batch in the packed form (offsets by two prefix sums on the device, one kernel that writes the wide arrays there) */
 int avk_merge_packed(avk_ctx *ctx, const avk_packed_multi_batch *batch, const avk_merge_config *cfg,
                      int32_t *status, uint8_t *classification, uint64_t *members);
+/* ... with escapes (NULL: avk_merge_packed) */
+int avk_merge_packed_esc(avk_ctx *ctx, const avk_packed_multi_batch *batch, const avk_packed_escapes *esc, const avk_merge_config *cfg,
+                         int32_t *status, uint8_t *classification, uint64_t *members);
 
 /* ---- merge on several GPUs (BASELINE configs[4]): merge regions are mapped exactly like compare regions (src/main.rs:463-478), so the same rule cuts a packed
  * multi-region batch: avk_packed_multi_shard_make gathers the regions rank `rank` of `world` owns (avk_region_shard of region_id[r], or of first_id + r), in the
@@ -549,7 +592,10 @@ int avk_merge_packed(avk_ctx *ctx, const avk_packed_multi_batch *batch, const av
 typedef struct avk_packed_multi_shard avk_packed_multi_shard;
 int  avk_packed_multi_shard_make(const avk_packed_multi_batch *whole, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world,
                                  avk_packed_multi_shard **out);
+int  avk_packed_multi_shard_make_esc(const avk_packed_multi_batch *whole, const avk_packed_escapes *esc, const uint64_t *region_id, uint64_t first_id, uint32_t rank,
+                                     uint32_t world, avk_packed_multi_shard **out);
 const avk_packed_multi_batch *avk_packed_multi_shard_batch(const avk_packed_multi_shard *s);
+const avk_packed_escapes *avk_packed_multi_shard_escapes(const avk_packed_multi_shard *s);
 uint64_t avk_packed_multi_shard_regions(const avk_packed_multi_shard *s, const uint64_t **index_in_whole);
 int  avk_packed_multi_shard_scatter(const avk_packed_multi_shard *s, const int32_t *status, const uint8_t *classification, const uint64_t *members,
                                     int32_t *whole_status, uint8_t *whole_classification, uint64_t *whole_members);
@@ -558,6 +604,9 @@ void avk_packed_multi_shard_free(avk_packed_multi_shard *s);
 uint64_t avk_merge_counts_len(uint32_t n_inputs);
 uint32_t avk_merge_counts_reason(uint32_t n_inputs, uint8_t classification, uint64_t members);
 int  avk_merge_counts(const avk_packed_multi_batch *batch, const int32_t *status, const uint8_t *classification, const uint64_t *members, uint64_t *counts);
+/* the same for a batch with escapes (it reads in_cnt; NULL: avk_merge_counts) */
+int  avk_merge_counts_esc(const avk_packed_multi_batch *batch, const avk_packed_escapes *esc, const int32_t *status, const uint8_t *classification, const uint64_t *members,
+                          uint64_t *counts);
 
 /* Host utility (no GPU involved): unit-cost edit distance of two byte strings, the value of the reference's
  * wfa_ed (src/util/sequence_alignment.rs:9-13).  The batch packer uses it for Variant::alt_ed

@@ -73,6 +73,13 @@ int avf_feed_pack(const avf_feed *f, void *(*alloc)(void *user, size_t bytes), v
 /* Regions [first, first + n) of a packed feed as a batch of their own (its arrays point into `all`'s); *v_first = index of the part's first call in the
  * feed's call arrays: the part's per-call results are indexed from there. */
 int avf_packed_slice(const avf_feed *f, const avk_packed_batch *all, uint64_t first, uint64_t n, avk_packed_batch *part, uint64_t *v_first);
+/* The same with ESCAPES (avk_packed_escapes, aardvark_amd.h): windows of 65,536 bases or more, sides with more than 255 calls and calls with an allele over 255
+ * bases (or further than 65,535 bases from their window's start) are listed in `esc` — its arrays come from `alloc` too — and their narrow fields are 0.  Returns 1
+ * only for feeds the wide form's own limits refuse too (2^32 calls or allele bytes, a contig of 4 Gbp, more than 65,535 contigs).  A feed that needs no escape
+ * gives the arrays of avf_feed_pack and empty lists.  avf_packed_slice_esc: the slice's escapes are ranges of `esc_all`'s lists plus bases, no copy. */
+int avf_feed_pack_esc(const avf_feed *f, void *(*alloc)(void *user, size_t bytes), void *user, avk_packed_batch *out, avk_packed_escapes *esc);
+int avf_packed_slice_esc(const avf_feed *f, const avk_packed_batch *all, const avk_packed_escapes *esc_all, uint64_t first, uint64_t n, avk_packed_batch *part,
+                         avk_packed_escapes *esc_part, uint64_t *v_first);
 /* Region generation for `merge` (RegionIterator::new_merge_iterator, region_generation.rs:129-192): the same walk over
  * n_inputs VCFs (1..64), in priority order.  samples: NULL, or per input NULL / "" = that file's first sample
  * (src/cli/merge.rs:196-198).  The feed hands out an avk_multi_batch for avk_merge_batch; avf_feed_batch is NULL for it
@@ -84,6 +91,10 @@ const avk_multi_batch *avf_feed_multi_batch(const avf_feed *f);
  * avf_packed_slice for compare feeds (returns 1 when the feed does not meet the form's constraints: use avf_feed_multi_batch). */
 int avf_feed_pack_multi(const avf_feed *f, void *(*alloc)(void *user, size_t bytes), void *user, avk_packed_multi_batch *out);
 int avf_packed_multi_slice(const avf_feed *f, const avk_packed_multi_batch *all, uint64_t first, uint64_t n, avk_packed_multi_batch *part);
+/* ... and with escapes, as avf_feed_pack_esc / avf_packed_slice_esc (count slot m * k + i is in_cnt[m * k + i]) */
+int avf_feed_pack_multi_esc(const avf_feed *f, void *(*alloc)(void *user, size_t bytes), void *user, avk_packed_multi_batch *out, avk_packed_escapes *esc);
+int avf_packed_multi_slice_esc(const avf_feed *f, const avk_packed_multi_batch *all, const avk_packed_escapes *esc_all, uint64_t first, uint64_t n,
+                               avk_packed_multi_batch *part, avk_packed_escapes *esc_part);
 /* The two halves of a feed on their own, so that a caller can read the VCFs while the reference genome is still loading (the reference
  * preloads its variants the same way, RegionIterator::preload_all_variants, region_generation.rs:199-279):
  * avf_calls_load parses one VCF (every chromosome), avf_feed_from_calls walks the regions over already loaded call sets.
