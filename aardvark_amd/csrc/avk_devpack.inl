@@ -303,6 +303,22 @@ AVK_DEV u64 dp_esc_lower(const u64 *list, u64 n, u64 key) { /* the first p with 
     }
     return lo;
 }
+/* The narrow arrays one list overrides (each may be NULL).  pair: a8 / b8 are the two halves of interleaved count slots, slot s = (s & 1 ? b8 : a8)[s >> 1] (the compare
+ * form's t_cnt / q_cnt); otherwise entry j is a8[j], b8[j] and h16[j]. */
+struct DpEscNarrow {
+    const u8 *a8, *b8;
+    const uint16_t *h16;
+    u32 pair;
+};
+/* entry i of a list breaks the form: outside [lo, hi), not above its left neighbour, or a narrow field of the entry it names is not 0 (the sums over the narrow
+ * arrays would count the entry twice, and a position or length would be silently dropped): AVK_E_ARG for the batch */
+AVK_DEV bool dp_esc_entry_bad(const u64 *idx, u64 i, u64 lo, u64 hi, const DpEscNarrow &z) {
+    const u64 x = idx[i];
+    if (x < lo || x >= hi || (i && idx[i - 1] >= x)) return true;
+    const u64 j = x - lo;
+    if (z.pair) return ((j & 1u) ? z.b8 : z.a8)[j >> 1] != 0;
+    return (z.a8 && z.a8[j]) || (z.b8 && z.b8[j]) || (z.h16 && z.h16[j]);
+}
 /* the positions of calls [vo, vo + calls): one walk along the call list from the first listed call at or behind vo */
 AVK_DEV void dp_esc_positions(const DpEsc &e, const uint16_t *rel_pos, u64 *w_pos, u64 st, u64 vo, u64 calls, u64 n_variants) {
     u64 pc = dp_esc_lower(e.call, e.n_calls, e.first_call + vo);

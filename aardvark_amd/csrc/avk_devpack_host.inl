@@ -20,18 +20,19 @@ __global__ void __launch_bounds__(256) avk_dp_widen_packed_esc_kernel(dpk::DpPac
 __global__ void __launch_bounds__(256) avk_dp_widen_packed_multi_esc_kernel(dpk::DpPackedMulti c, dpk::DpEsc e, uint64_t *w_in_off) {
     dpk::dp_widen_packed_multi_esc(c, e, w_in_off, (uint64_t)blockIdx.x * 256u + threadIdx.x);
 }
-/* One escape list of a packed batch (avk_packed_escapes), one workgroup: checks that idx[] is strictly ascending inside [lo, hi) — *err is set otherwise —, writes
+/* One escape list of a packed batch (avk_packed_escapes), one workgroup: checks that idx[] is strictly ascending inside [lo, hi) and that the narrow fields `z` of
+ * every listed entry are 0 (dp_esc_entry_bad: the check sits here, with the sparse lists, not in the widening's every lane) — *err is set otherwise —, writes
  * the exclusive sums of a[i] + b[i] to before[0 .. n] (b may be NULL; a NULL: a list without values to sum) and adds their total to *total: the sums over the narrow
  * arrays count a listed entry as 0, this is what they lack.  The lists are sparse (a genome's long alleles: thousands), so one workgroup's chunks of 1024 do. */
-__global__ void __launch_bounds__(1024) avk_esc_scan_kernel(const uint64_t *idx, const uint32_t *a, const uint32_t *b, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *before,
-                                                            uint64_t *total, uint64_t *err) {
+__global__ void __launch_bounds__(1024) avk_esc_scan_kernel(const uint64_t *idx, const uint32_t *a, const uint32_t *b, uint64_t n, uint64_t lo, uint64_t hi, dpk::DpEscNarrow z,
+                                                            uint64_t *before, uint64_t *total, uint64_t *err) {
     __shared__ uint64_t part[1024];
     __shared__ uint64_t carry;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
     for (uint64_t base = 0; base < n; base += 1024u) {
         const uint64_t i = base + threadIdx.x;
-        if (i < n && (idx[i] < lo || idx[i] >= hi || (i && idx[i - 1] >= idx[i]))) *err = 1; /* (every writer stores the same word) */
+        if (i < n && dpk::dp_esc_entry_bad(idx, i, lo, hi, z)) *err = 1; /* (every writer stores the same word) */
         const uint64_t x = i < n && a ? (uint64_t)a[i] + (b ? (uint64_t)b[i] : 0ull) : 0ull;
         part[threadIdx.x] = x;
         __syncthreads();
@@ -880,7 +881,8 @@ static inline bool esc_arrays_ok(const avk_packed_escapes *e) {
 }
 /* host: the narrow per-entry fields of a packed batch with its escapes applied — for the host-side utilities (shards, merge counts, the merge path's host
  * fallback).  cnt[] has one entry per count slot: 2r / 2r + 1 = t_cnt / q_cnt of region r (compare form, cnt_b given), or in_cnt as it is (multi form, cnt_b NULL).
- * false: a list is not ascending or names an entry outside the batch. */
+ * false: a list is not ascending or names an entry outside the batch, or a listed entry's narrow field is not 0 (the rule of avk_packed_escapes; the device refuses
+ * the same batches: dp_esc_entry_bad). */
 struct PackedWideHost {
     std::vector<uint32_t> len, cnt, rel, a0, a1;
 };
@@ -898,15 +900,20 @@ static bool packed_widen_host(const uint16_t *len, uint64_t n, const uint8_t *cn
     auto listed = [](const uint64_t *idx, uint64_t p, uint64_t first, uint64_t count) { return idx[p] >= first && idx[p] - first < count && (p == 0 || idx[p - 1] < idx[p]); };
     for (uint64_t p = 0; p < esc->n_esc_regions; ++p) {
         if (!listed(esc->esc_region, p, esc->first_region, n)) return false;
-        w.len[esc->esc_region[p] - esc->first_region] = esc->esc_len[p];
+        const uint64_t r = esc->esc_region[p] - esc->first_region;
+        if (len[r]) return false;
+        w.len[r] = esc->esc_len[p];
     }
     for (uint64_t p = 0; p < esc->n_esc_slots; ++p) {
         if (!listed(esc->esc_slot, p, esc->first_slot, n_slots)) return false;
-        w.cnt[esc->esc_slot[p] - esc->first_slot] = esc->esc_cnt[p];
+        const uint64_t i = esc->esc_slot[p] - esc->first_slot;
+        if (w.cnt[i]) return false;
+        w.cnt[i] = esc->esc_cnt[p];
     }
     for (uint64_t p = 0; p < esc->n_esc_calls; ++p) {
         if (!listed(esc->esc_call, p, esc->first_call, nv)) return false;
         const uint64_t v = esc->esc_call[p] - esc->first_call;
+        if (rel[v] || a0[v] || a1[v]) return false;
         w.rel[v] = esc->esc_rel_pos[p], w.a0[v] = esc->esc_a0_len[p], w.a1[v] = esc->esc_a1_len[p];
     }
     return true;
@@ -1055,13 +1062,14 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
                         {esc->esc_rel_pos, x_rel, ec * 4}, {esc->esc_a0_len, x_a0, ec * 4}, {esc->esc_a1_len, x_a1, ec * 4}};
     }
     /* (side stream, behind the sums over the narrow arrays and the lists' copies) the lists are checked and summed; totals[0..1] gain what the narrow sums lack, totals[2] is the error word */
-    auto esc_scans = [&](hipStream_t side, uint64_t *totals, uint64_t n_slots_all, uint64_t n_calls_all, uint64_t n_regions_all) {
+    auto esc_scans = [&](hipStream_t side, uint64_t *totals, uint64_t n_slots_all, uint64_t n_calls_all, uint64_t n_regions_all, const dpk::DpEscNarrow &z_slot,
+                         const dpk::DpEscNarrow &z_call, const dpk::DpEscNarrow &z_region) {
         hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.slot, de.cnt, (const uint32_t *)nullptr, de.n_slots, de.first_slot, de.first_slot + n_slots_all,
-                           (uint64_t *)de.cnt_before, totals, totals + 2);
-        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.call, de.a0, de.a1, de.n_calls, de.first_call, de.first_call + n_calls_all, (uint64_t *)de.bytes_before,
-                           totals + 1, totals + 2);
+                           z_slot, (uint64_t *)de.cnt_before, totals, totals + 2);
+        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.call, de.a0, de.a1, de.n_calls, de.first_call, de.first_call + n_calls_all, z_call,
+                           (uint64_t *)de.bytes_before, totals + 1, totals + 2);
         hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.region, (const uint32_t *)nullptr, (const uint32_t *)nullptr, de.n_regions, de.first_region,
-                           de.first_region + n_regions_all, (uint64_t *)nullptr, (uint64_t *)nullptr, totals + 2);
+                           de.first_region + n_regions_all, z_region, (uint64_t *)nullptr, (uint64_t *)nullptr, totals + 2);
     };
     if (pk) { /* the packed arrays as they are, two prefix sums for the offsets they leave out, one kernel that writes the wide arrays */
         /* (the packed arrays stay with the batch when they are what the packer and the later record writers read; a staging slot's stay with its ticket) */
@@ -1145,7 +1153,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             a.in.pk_a1 = p_a1, a.in.pk_voff = p_voff, a.in.pk_aoff = p_aoff;
             db->d_pk_voff = p_voff, db->d_pk_tc = p_tc, db->d_pk_qc = p_qc;
         } else if (has_esc && ew == hipSuccess) {
-            esc_scans(side, pk_totals, 2 * n, nv, n);
+            esc_scans(side, pk_totals, 2 * n, nv, n, dpk::DpEscNarrow{p_tc, p_qc, nullptr, 1u}, dpk::DpEscNarrow{p_a0, p_a1, p_rel, 0u}, dpk::DpEscNarrow{nullptr, nullptr, p_len, 0u});
             if (m) hipLaunchKernelGGL(avk_dp_widen_packed_esc_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, side, c, de);
             ew = hipGetLastError();
         } else if (m && ew == hipSuccess) {
@@ -1219,7 +1227,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             const uint64_t mx = nm > nv ? nm : nv;
             hipError_t ew = hipStreamWaitEvent(side, ctx->ev_copy_mid, 0);
             if (has_esc && ew == hipSuccess) {
-                esc_scans(side, pk_totals, ni, nv, nm);
+                esc_scans(side, pk_totals, ni, nv, nm, dpk::DpEscNarrow{p_ic, nullptr, nullptr, 0u}, dpk::DpEscNarrow{p_a0, p_a1, p_rel, 0u}, dpk::DpEscNarrow{nullptr, nullptr, p_len, 0u});
                 if (mx) hipLaunchKernelGGL(avk_dp_widen_packed_multi_esc_kernel, dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, side, w, de, db->d_m_in_off);
                 ew = hipGetLastError();
             } else if (mx && ew == hipSuccess) {
@@ -1341,7 +1349,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     if (e == hipSuccess && (pk || pm)) { /* the two sums the packed form implies must be what the caller says they are */
         uint64_t tot[3] = {0, 0, 0};
         memcpy(tot, hs + 1, has_esc ? 24 : 16);
-        if (has_esc && tot[2]) return bail(fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending or names an entry outside the batch"));
+        if (has_esc && tot[2]) return bail(fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending, names an entry outside the batch, or lists an entry whose narrow field is not 0"));
         if ((((pm ? pm->n_regions : n) && tot[0] != nv) || (nv && tot[1] != alen)))
             return bail(fail(ctx, AVK_E_ARG, "packed batch: the call counts sum to %llu (n_variants %llu), the allele lengths to %llu (allele_bytes_len %llu)",
                              (unsigned long long)tot[0], (unsigned long long)nv, (unsigned long long)tot[1], (unsigned long long)alen));

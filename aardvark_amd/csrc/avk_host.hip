@@ -3441,7 +3441,7 @@ int avk_merge_packed_esc(avk_ctx *ctx, const avk_packed_multi_batch *pm, const a
     if (merge_on_device(ctx, n, k)) return merge_batch_internal(ctx, &mb, pm, cfg, status, classification, members, esc);
     PackedWideHost wh;
     if (!packed_widen_host(pm->len, n, pm->in_cnt, nullptr, n * k, pm->var_rel_pos, pm->a0_len, pm->a1_len, nv, esc, wh))
-        return fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending or names an entry outside the batch");
+        return fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending, names an entry outside the batch, or lists an entry whose narrow field is not 0");
     /* no device path for this batch (more than DP_MERGE_KMAX inputs, an empty batch, device_pack = 0): the wide form, made here, through avk_merge_batch */
     std::vector<uint64_t> start(n), end(n), in_off(n * k), pos(nv), a0_off(nv), a1_off(nv);
     std::vector<uint32_t> contig(n), in_cnt(n * k), a0_len(nv), a1_len(nv), raw(nv);

@@ -284,8 +284,10 @@ int avk_merge_counts_esc(const avk_packed_multi_batch *b, const avk_packed_escap
     if (avk_merge_counts_len(k) == 0) return AVK_E_ARG;
     if (!esc_present(esc) || !esc->n_esc_slots) esc = nullptr; /* (only the counts are read) */
     if (esc && (!esc->esc_slot || !esc->esc_cnt)) return AVK_E_ARG;
-    for (uint64_t p = 0; esc && p < esc->n_esc_slots; ++p) /* ascending, inside the batch: checked before anything is added to counts[] */
+    for (uint64_t p = 0; esc && p < esc->n_esc_slots; ++p) { /* ascending, inside the batch, the narrow count of a listed slot 0: checked before anything is added to counts[] */
         if (esc->esc_slot[p] < esc->first_slot || esc->esc_slot[p] - esc->first_slot >= b->n_regions * k || (p && esc->esc_slot[p - 1] >= esc->esc_slot[p])) return AVK_E_ARG;
+        if (b->in_cnt[esc->esc_slot[p] - esc->first_slot]) return AVK_E_ARG;
+    }
     uint64_t v = 0, ps = 0;
     for (uint64_t r = 0; r < b->n_regions; ++r) {
         const uint8_t cls = classification[r];

@@ -175,8 +175,10 @@ typedef struct avk_packed_batch {
 
 /* ESCAPES of a packed batch (avk_packed_batch and avk_packed_multi_batch alike): sparse overrides for the few entries whose values do not fit the narrow
  * fields, so that one 300-base insertion, one window of 65,536 bases or one side with 256 calls no longer costs a call set the packed form.  Three sorted
- * lists; an entry that is listed takes its value(s) from the list, its narrow field(s) are ignored and MUST be written as 0 (the running sums over the narrow
- * arrays then count it as nothing, and the library adds the listed values); an entry that is not listed means what it means without escapes.
+ * lists; an entry that is listed takes its value(s) from the list, whatever the value, and its narrow field(s) MUST be written as 0 (the running sums over the
+ * narrow arrays then count it as nothing, and the library adds the listed values).  A listed entry with a non-zero narrow field — len, t_cnt / q_cnt / in_cnt,
+ * var_rel_pos, a0_len or a1_len — is AVK_E_ARG from every function that takes the lists, on the device and on the host alike (avk_merge_counts_esc reads the count
+ * slots only and checks those).  An entry that is not listed means what it means without escapes.
  *   regions  esc_region[] ascending region indices; esc_len[] the window length (end - start)
  *   counts   esc_slot[] ascending count slots; esc_cnt[] the count.  Compare form: slot 2r = t_cnt of region r, slot 2r + 1 = q_cnt of region r;
  *            multi form: slot m * k + i = in_cnt[m * k + i]

@@ -1189,6 +1189,62 @@ int emu_merge_batch(const avk_multi_batch *mb, const uint8_t *const *refs, const
     return 0;
 }
 
+/* ---- packed batches with escapes (avk_packed_escapes): the per-lane widening functions of avk_devpack.inl, lane by lane in a plain loop (they meet no wave
+ * rendezvous).  The caller hands in what the kernels around them make on the device: the exclusive sums over the narrow arrays (v_off / in_off, a_off) and over the
+ * lists' values (cnt_before / bytes_before, n + 1 entries each).  Returns what avk_esc_scan_kernel's check says of the three lists (dp_esc_entry_bad for every
+ * entry): 0 fine, 1 refused — the widening runs either way, as it does on the device, where the error word is read afterwards. */
+struct emu_wide_arrays {
+    uint32_t *contig, *t_cnt, *q_cnt, *a0_len, *a1_len, *raw, *in_cnt;
+    uint64_t *start, *end, *t_off, *q_off, *pos, *a0_off, *a1_off, *in_off;
+    uint8_t *type, *zyg;
+};
+static dpk::DpEsc emu_esc_of(const avk_packed_escapes *e, const uint64_t *cnt_before, const uint64_t *bytes_before) {
+    dpk::DpEsc d;
+    memset(&d, 0, sizeof(d));
+    d.region = e->esc_region, d.slot = e->esc_slot, d.call = e->esc_call, d.len = e->esc_len, d.cnt = e->esc_cnt, d.rel = e->esc_rel_pos, d.a0 = e->esc_a0_len, d.a1 = e->esc_a1_len;
+    d.cnt_before = cnt_before, d.bytes_before = bytes_before;
+    d.n_regions = e->n_esc_regions, d.n_slots = e->n_esc_slots, d.n_calls = e->n_esc_calls;
+    d.first_region = e->first_region, d.first_slot = e->first_slot, d.first_call = e->first_call;
+    return d;
+}
+static int emu_esc_lists_bad(const dpk::DpEsc &d, uint64_t n_regions, uint64_t n_slots, uint64_t n_calls, const dpk::DpEscNarrow &z_region, const dpk::DpEscNarrow &z_slot,
+                             const dpk::DpEscNarrow &z_call) {
+    int bad = 0;
+    for (uint64_t i = 0; i < d.n_slots; ++i) bad |= dpk::dp_esc_entry_bad(d.slot, i, d.first_slot, d.first_slot + n_slots, z_slot) ? 1 : 0;
+    for (uint64_t i = 0; i < d.n_calls; ++i) bad |= dpk::dp_esc_entry_bad(d.call, i, d.first_call, d.first_call + n_calls, z_call) ? 1 : 0;
+    for (uint64_t i = 0; i < d.n_regions; ++i) bad |= dpk::dp_esc_entry_bad(d.region, i, d.first_region, d.first_region + n_regions, z_region) ? 1 : 0;
+    return bad;
+}
+int emu_widen_packed_esc(const avk_packed_batch *pk, const avk_packed_escapes *esc, const uint64_t *v_off, const uint64_t *a_off, const uint64_t *cnt_before,
+                         const uint64_t *bytes_before, const emu_wide_arrays *w) {
+    const dpk::DpEsc d = emu_esc_of(esc, cnt_before, bytes_before);
+    dpk::DpPacked c;
+    memset(&c, 0, sizeof(c));
+    c.contig_idx = pk->contig_idx, c.len = pk->len, c.rel_pos = pk->var_rel_pos, c.start = pk->start, c.var_raw = pk->var_raw_space, c.t_cnt = pk->t_cnt, c.q_cnt = pk->q_cnt,
+    c.var_type_zyg = pk->var_type_zyg, c.a0_len = pk->a0_len, c.a1_len = pk->a1_len, c.v_off = v_off, c.a_off = a_off, c.n_regions = pk->n_regions, c.n_variants = pk->n_variants;
+    c.w_contig = pk->contig_idx ? w->contig : nullptr, c.w_t_cnt = w->t_cnt, c.w_q_cnt = w->q_cnt, c.w_a0_len = w->a0_len, c.w_a1_len = w->a1_len, c.w_raw = w->raw, c.w_start = w->start,
+    c.w_end = w->end, c.w_t_off = w->t_off, c.w_q_off = w->q_off, c.w_pos = w->pos, c.w_a0_off = w->a0_off, c.w_a1_off = w->a1_off, c.w_type = w->type, c.w_zyg = w->zyg;
+    const uint64_t m = c.n_regions > c.n_variants ? c.n_regions : c.n_variants;
+    for (uint64_t i = 0; i < m; ++i) dpk::dp_widen_packed_esc(c, d, i);
+    return emu_esc_lists_bad(d, c.n_regions, 2 * c.n_regions, c.n_variants, dpk::DpEscNarrow{nullptr, nullptr, pk->len, 0u}, dpk::DpEscNarrow{pk->t_cnt, pk->q_cnt, nullptr, 1u},
+                             dpk::DpEscNarrow{pk->a0_len, pk->a1_len, pk->var_rel_pos, 0u});
+}
+int emu_widen_packed_multi_esc(const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const uint64_t *in_off, const uint64_t *a_off, const uint64_t *cnt_before,
+                               const uint64_t *bytes_before, const emu_wide_arrays *w) {
+    const dpk::DpEsc d = emu_esc_of(esc, cnt_before, bytes_before);
+    dpk::DpPackedMulti c;
+    memset(&c, 0, sizeof(c));
+    c.contig_idx = pm->contig_idx, c.len = pm->len, c.rel_pos = pm->var_rel_pos, c.start = pm->start, c.var_raw = pm->var_raw_space, c.in_cnt = pm->in_cnt, c.var_type_zyg = pm->var_type_zyg,
+    c.a0_len = pm->a0_len, c.a1_len = pm->a1_len, c.in_off = in_off, c.a_off = a_off, c.n_multi = pm->n_regions, c.n_variants = pm->n_variants, c.k = pm->n_inputs;
+    c.w_contig = pm->contig_idx ? w->contig : nullptr, c.w_in_cnt = w->in_cnt, c.w_a0_len = w->a0_len, c.w_a1_len = w->a1_len, c.w_raw = w->raw, c.w_start = w->start, c.w_end = w->end,
+    c.w_pos = w->pos, c.w_a0_off = w->a0_off, c.w_a1_off = w->a1_off, c.w_type = w->type, c.w_zyg = w->zyg;
+    const uint64_t m = c.n_multi > c.n_variants ? c.n_multi : c.n_variants;
+    for (uint64_t i = 0; i < m; ++i) dpk::dp_widen_packed_multi_esc(c, d, w->in_off, i);
+    return emu_esc_lists_bad(d, c.n_multi, c.n_multi * c.k, c.n_variants, dpk::DpEscNarrow{nullptr, nullptr, pm->len, 0u}, dpk::DpEscNarrow{pm->in_cnt, nullptr, nullptr, 0u},
+                             dpk::DpEscNarrow{pm->a0_len, pm->a1_len, pm->var_rel_pos, 0u});
+}
+uint64_t emu_esc_lower(const uint64_t *list, uint64_t n, uint64_t key) { return dpk::dp_esc_lower(list, n, key); }
+
 void emu_set_lane_kernel(int on) { g_lane_kernel = on; }
 void emu_set_team(int on) { g_team = on; }
 void emu_set_device_pack(int on) { g_device_pack = on; }

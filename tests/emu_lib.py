@@ -32,8 +32,61 @@ def load():
         lib.emu_set_lane_pool.argtypes = [C.c_int]
         lib.emu_set_lane_quad.argtypes = [C.c_int]
         lib.emu_last_quad_solved.restype = C.c_uint64
+        lib.emu_widen_packed_esc.argtypes = [C.c_void_p, C.c_void_p, u64p, u64p, u64p, u64p, C.POINTER(EmuWideArrays)]
+        lib.emu_widen_packed_multi_esc.argtypes = [C.c_void_p, C.c_void_p, u64p, u64p, u64p, u64p, C.POINTER(EmuWideArrays)]
+        lib.emu_esc_lower.restype = C.c_uint64
+        lib.emu_esc_lower.argtypes = [u64p, C.c_uint64, C.c_uint64]
         _lib = lib
     return _lib
+
+
+class EmuWideArrays(C.Structure):
+    """emu_wide_arrays of tests/emu/wave_emu.cpp: the wide arrays the widening functions of avk_devpack.inl write"""
+    U32 = ("contig", "t_cnt", "q_cnt", "a0_len", "a1_len", "raw", "in_cnt")
+    U64 = ("start", "end", "t_off", "q_off", "pos", "a0_off", "a1_off", "in_off")
+    U8 = ("type", "zyg")
+    _fields_ = [(f, C.POINTER(C.c_uint32)) for f in U32] + [(f, u64p) for f in U64] + [(f, u8p) for f in U8]
+
+
+GUARD = 16  # guard elements behind every output array of widen_packed_esc, checked after the run
+PER_REGION = ("contig", "t_cnt", "q_cnt", "start", "end", "t_off", "q_off")
+PER_SLOT = ("in_cnt", "in_off")
+
+
+def widen_packed_esc(pb, sums):
+    """dp_widen_packed_esc (PackedBatch) / dp_widen_packed_multi_esc (PackedMultiBatch) for every lane i in [0, max(n_regions, n_variants)), on CPU lanes.
+    sums = (narrow call offsets [v_off or in_off], narrow allele offsets a_off, cnt_before, bytes_before): uint64 exclusive sums, the last two with the total
+    as entry n.  -> (dict of the wide arrays, refused: what the scan of the three lists says).  Every output array has GUARD elements behind it that must
+    come back untouched, and starts out as 0xEE bytes."""
+    import numpy as np
+    lib = load()
+    multi = hasattr(pb, "n_inputs")
+    n, nv = pb.n_regions, pb.n_variants
+    ns = n * pb.n_inputs if multi else 2 * n
+    w, out = EmuWideArrays(), {}
+    for names, dt, ct in ((EmuWideArrays.U32, np.uint32, C.c_uint32), (EmuWideArrays.U64, np.uint64, C.c_uint64), (EmuWideArrays.U8, np.uint8, C.c_uint8)):
+        for f in names:
+            size = n if f in PER_REGION else (ns if f in PER_SLOT else nv)
+            a = np.empty(size + GUARD, dt)
+            a.view(np.uint8)[:] = 0xEE
+            out[f] = (a, size)
+            setattr(w, f, a.ctypes.data_as(C.POINTER(ct)))
+    v_off, a_off, cnt_before, bytes_before = [np.ascontiguousarray(x, np.uint64) for x in sums]
+    assert cnt_before.size == pb.escapes.esc_slot.size + 1 and bytes_before.size == pb.escapes.esc_call.size + 1 and v_off.size >= (ns if multi else n) and a_off.size >= nv
+    st, esc = pb.c_struct(), pb.escapes.c_struct()
+    P = lambda x: x.ctypes.data_as(u64p)
+    entry = lib.emu_widen_packed_multi_esc if multi else lib.emu_widen_packed_esc
+    refused = entry(C.byref(st), C.byref(esc), P(v_off), P(a_off), P(cnt_before), P(bytes_before), C.byref(w))
+    for f, (a, size) in out.items():
+        assert np.all(a[size:].view(np.uint8) == 0xEE), "the widening wrote behind the end of " + f
+    return {f: a[:size] for f, (a, size) in out.items()}, int(refused)
+
+
+def esc_lower(lst, key):
+    """dp_esc_lower: the first p with lst[p] >= key"""
+    import numpy as np
+    lst = np.ascontiguousarray(lst, np.uint64)
+    return int(load().emu_esc_lower(lst.ctypes.data_as(u64p), lst.size, int(key)))
 
 
 def compare_batch(batch, contigs, max_branch_factor=50, sequences=False, exact_shortcut=False,

@@ -79,14 +79,43 @@ def with_injections(contigs, batch, **kw):
     return synth.concat_batches([batch, extra])
 
 
-def genome_job(scale=0.004):
+def reordered(b, order):
+    """RegionBatch `b` with its regions in the order `order` (indices into b): calls and allele bytes follow their regions, region ids are renumbered"""
+    order = np.asarray(order, np.int64)
+    assert np.array_equal(b.q_off, b.t_off + b.t_cnt.astype(np.uint64)) and np.array_equal(b.a1_off, b.a0_off + b.a0_len.astype(np.uint64))
+    excl = lambda x: np.concatenate([[0], np.cumsum(x)[:-1]]).astype(np.int64) if x.size else np.zeros(0, np.int64)
+    cnt = (b.t_cnt.astype(np.int64) + b.q_cnt)[order]
+    voff = excl(cnt)
+    calls = np.repeat(b.t_off.astype(np.int64)[order] - voff, cnt) + np.arange(int(cnt.sum()))
+    alen = (b.a0_len.astype(np.int64) + b.a1_len)[calls]
+    aoff = excl(alen)
+    src = np.repeat(b.a0_off.astype(np.int64)[calls] - aoff, alen) + np.arange(int(alen.sum()))
+    return RegionBatch(np.arange(order.size).astype(np.uint64), b.contig_idx[order], b.start[order], b.end[order], voff, b.t_cnt[order], voff + b.t_cnt[order], b.q_cnt[order],
+                       b.var_pos[calls], b.var_type[calls], b.var_zyg[calls], b.var_raw_space[calls], aoff, b.a0_len[calls], aoff + b.a0_len[calls], b.a1_len[calls],
+                       b.allele_bytes[src])
+
+
+WHERE = ("last", "first", "middle")
+
+
+def placed(batch, n_injected, where):
+    """`batch` whose last `n_injected` regions are the injected ones, with those regions last (as it is), first or in the middle of the ordinary regions: the
+    truly oversize values then precede tens of thousands of ordinary entries"""
+    n = batch.n_regions - n_injected
+    body, extra = np.arange(n), np.arange(n, batch.n_regions)
+    if where == "last":
+        return batch
+    return reordered(batch, np.concatenate([extra, body] if where == "first" else [body[:n // 2], extra, body[n // 2:]]))
+
+
+def genome_job(scale=0.004, where="last"):
     contigs, batch = synth.config_genome(scale=scale, threads=4)
-    return contigs, with_injections(contigs, batch, at=60_000)
+    return contigs, placed(with_injections(contigs, batch, at=60_000), len(injected_regions(np.asarray(contigs[0]).tobytes(), at=60_000)), where)
 
 
-def indel_mix_job(n_truth=3000, contig_len=1_200_000):
+def indel_mix_job(n_truth=3000, contig_len=1_200_000, where="last"):
     contig, batch = synth.config_indel_mix_v2(n_truth=n_truth, contig_len=contig_len)
-    return [contig], with_injections([contig], batch, at=300_000)
+    return [contig], placed(with_injections([contig], batch, at=300_000), len(injected_regions(np.asarray(contig).tobytes(), at=300_000)), where)
 
 
 def escaped(batch):
@@ -95,9 +124,9 @@ def escaped(batch):
     return cb, PackedBatch.from_compact(cb, escapes=True)
 
 
-def merge_job(scale=0.0008, at=30_000, many=260):
+def merge_job(scale=0.0008, at=30_000, many=260, where="last"):
     """three call sets (synth.config_genome_merge) plus injected MultiRegions: long alleles in one, two or all inputs, a long window, an input with more than
-    255 calls -> (contigs, MultiBatch)"""
+    255 calls -> (contigs, MultiBatch); where: the injected MultiRegions last, first or in the middle of the others"""
     contigs, mb = synth.config_genome_merge(scale=scale, k=3, threads=4)
     contig = np.asarray(contigs[0]).tobytes()
     rng = np.random.default_rng(11)
@@ -115,11 +144,199 @@ def merge_job(scale=0.0008, at=30_000, many=260):
     regions.append({"start": p, "end": p + 12 * many + 120, "contig": 0, "inputs": [calls, calls[:255], calls]})
     extra = MultiBatch.from_regions(regions)
     cat = lambda f, sh=0: np.concatenate([getattr(mb, f), getattr(extra, f) + np.asarray(sh, getattr(extra, f).dtype)])
-    return contigs, MultiBatch(3, region_id=np.arange(mb.n_regions + extra.n_regions), contig_idx=cat("contig_idx"), start=cat("start"), end=cat("end"),
-                               in_off=cat("in_off", mb.n_variants), in_cnt=cat("in_cnt"), var_pos=cat("var_pos"), var_type=cat("var_type"), var_zyg=cat("var_zyg"),
-                               var_raw_space=cat("var_raw_space"), a0_off=cat("a0_off", mb.allele_bytes.size if mb.n_variants else 0), a0_len=cat("a0_len"),
-                               a1_off=cat("a1_off", mb.allele_bytes.size if mb.n_variants else 0), a1_len=cat("a1_len"),
-                               allele_bytes=np.concatenate([mb.allele_bytes[:int((mb.a0_len.astype(np.int64) + mb.a1_len).sum())], extra.allele_bytes]))
+    whole = MultiBatch(3, region_id=np.arange(mb.n_regions + extra.n_regions), contig_idx=cat("contig_idx"), start=cat("start"), end=cat("end"),
+                       in_off=cat("in_off", mb.n_variants), in_cnt=cat("in_cnt"), var_pos=cat("var_pos"), var_type=cat("var_type"), var_zyg=cat("var_zyg"),
+                       var_raw_space=cat("var_raw_space"), a0_off=cat("a0_off", mb.allele_bytes.size if mb.n_variants else 0), a0_len=cat("a0_len"),
+                       a1_off=cat("a1_off", mb.allele_bytes.size if mb.n_variants else 0), a1_len=cat("a1_len"),
+                       allele_bytes=np.concatenate([mb.allele_bytes[:int((mb.a0_len.astype(np.int64) + mb.a1_len).sum())], extra.allele_bytes]))
+    if where == "last":
+        return contigs, whole
+    n = mb.n_regions
+    body, tail = np.arange(n), np.arange(n, whole.n_regions)
+    return contigs, reordered_multi(whole, np.concatenate([tail, body] if where == "first" else [body[:n // 2], tail, body[n // 2:]]))
+
+
+def reordered_multi(mb, order):
+    """MultiBatch `mb` with its MultiRegions in the order `order`: calls and allele bytes follow their regions"""
+    order, k = np.asarray(order, np.int64), mb.n_inputs
+    excl = lambda x: np.concatenate([[0], np.cumsum(x)[:-1]]).astype(np.int64) if x.size else np.zeros(0, np.int64)
+    ic = mb.in_cnt.astype(np.int64).reshape(-1, k)[order]
+    cnt = ic.sum(axis=1)
+    voff = excl(cnt)
+    calls = np.repeat(mb.in_off.astype(np.int64).reshape(-1, k)[order, 0] - voff, cnt) + np.arange(int(cnt.sum()))
+    alen = (mb.a0_len.astype(np.int64) + mb.a1_len)[calls]
+    aoff = excl(alen)
+    src = np.repeat(mb.a0_off.astype(np.int64)[calls] - aoff, alen) + np.arange(int(alen.sum()))
+    return MultiBatch(k, region_id=np.arange(order.size), contig_idx=mb.contig_idx[order], start=mb.start[order], end=mb.end[order], in_off=excl(ic.reshape(-1)),
+                      in_cnt=ic.reshape(-1), var_pos=mb.var_pos[calls], var_type=mb.var_type[calls], var_zyg=mb.var_zyg[calls], var_raw_space=mb.var_raw_space[calls],
+                      a0_off=aoff, a0_len=mb.a0_len[calls], a1_off=aoff + mb.a0_len[calls].astype(np.int64), a1_len=mb.a1_len[calls], allele_bytes=mb.allele_bytes[src])
+
+
+# ---- promotion: the same batch with more of its entries in the escape lists -------------------------------------------------------------------
+
+def promote(pb, regions=(), slots=(), calls=()):
+    """A PackedBatch / PackedMultiBatch that stands for the same batch as `pb`, with regions `regions`, count slots `slots` (compare form: 2r / 2r + 1 = t_cnt / q_cnt
+    of region r; multi form: m * k + i) and calls `calls` — indices into pb's own arrays — moved into the escape lists: their values go to the lists, their narrow
+    fields are zeroed, the lists stay merged and ascending with what pb already lists and keep pb's bases.  A listed entry takes its value from the list whatever
+    the value (include/aardvark_amd.h: avk_packed_escapes), so lists of any length cost nothing to solve."""
+    from aardvark_amd._abi import PackedEscapes
+    length, cnt, rel, a0, a1 = pb._wide_fields()
+    e = pb.escapes if pb.escapes is not None else PackedEscapes()
+    local = lambda idx, first, more: np.union1d((idx - np.uint64(first)).astype(np.int64), np.asarray(more, np.int64).reshape(-1))
+    r, s, v = local(e.esc_region, e.first_region, regions), local(e.esc_slot, e.first_slot, slots), local(e.esc_call, e.first_call, calls)
+    assert (r.size == 0 or (r[0] >= 0 and r[-1] < length.size)) and (s.size == 0 or (s[0] >= 0 and s[-1] < cnt.size)) and (v.size == 0 or (v[0] >= 0 and v[-1] < rel.size))
+    esc = PackedEscapes(e.first_region, e.first_call, e.first_slot, esc_region=r + e.first_region, esc_len=length[r], esc_slot=s + e.first_slot, esc_cnt=cnt[s],
+                        esc_call=v + e.first_call, esc_rel_pos=rel[v], esc_a0_len=a0[v], esc_a1_len=a1[v])
+    length[r], cnt[s], rel[v], a0[v], a1[v] = 0, 0, 0, 0, 0
+    arrays = {f: getattr(pb, f) for f in type(pb).FIELDS}
+    arrays.update(len=length, var_rel_pos=rel, a0_len=a0, a1_len=a1)
+    if hasattr(pb, "n_inputs"):
+        return type(pb)(pb.n_inputs, escapes=esc, in_cnt=cnt, **{f: x for f, x in arrays.items() if f != "in_cnt"})
+    return type(pb)(escapes=esc, t_cnt=cnt[0::2], q_cnt=cnt[1::2], **{f: x for f, x in arrays.items() if f not in ("t_cnt", "q_cnt")})
+
+
+BLOCK_EDGES = (4095, 4096, 4097, 8191, 8192)  # both sides of the first two edges of the 4096-element blocks the narrow prefix sums run in (AVK_PS_BLOCK)
+DRAWS = tuple((seed, size) for seed in (1, 2, 3) for size in (1023, 1024, 1025, 3000))
+
+
+def promotion_table(pb, draws=True):
+    """name -> (regions, slots, calls) to promote, chosen by rule: the places where a search, a running sum or a block edge can be off by one.  A list shorter than
+    an index or a draw asks for takes what it has (the tests that need the full size assert it)."""
+    n, nv = pb.n_regions, pb.n_variants
+    per = pb.n_inputs if hasattr(pb, "n_inputs") else 2
+    ns = n * per
+    cnt = pb._wide_fields()[1].reshape(n, per).sum(axis=1)
+    voff = np.concatenate([[0], np.cumsum(cnt)])
+    busy = int(np.argmax(cnt))  # the region with the most calls (an injected one: a listed count among its slots)
+    plain = int(np.flatnonzero((cnt >= 2) & (np.arange(n) > n // 3))[0])  # an ordinary region with calls, a third of the way in
+    inside = lambda idx, size: [i for i in idx if i < size]
+    every = lambda r: np.arange(r * per, (r + 1) * per)
+    table = {
+        "nothing": ([], [], []),
+        "entry_0": ([0], [0], [0]),
+        "last_entry": ([n - 1], [ns - 1], [nv - 1]),
+        "slots_and_window_of_one_region": ([plain], every(plain), []),
+        "slots_and_window_of_the_busiest_region": ([busy], every(busy), []),
+        "64_consecutive_calls": ([], [], np.arange(nv // 2, min(nv // 2 + 64, nv))),
+        "every_call_of_one_region": ([], [], np.arange(voff[plain], voff[plain + 1])),
+        "every_call_of_the_busiest_region": ([busy], every(busy), np.arange(voff[busy], voff[busy + 1])),
+        "block_edges": (inside(BLOCK_EDGES, n), inside(BLOCK_EDGES, ns), inside(BLOCK_EDGES, nv)),
+        "every_second": (np.arange(0, n, 2), np.arange(0, ns, 2), np.arange(0, nv, 2)),
+        "every_second_odd": (np.arange(1, n, 2), np.arange(1, ns, 2), np.arange(1, nv, 2)),
+        "all_calls": ([], [], np.arange(nv)),
+        "everything": (np.arange(n), np.arange(ns), np.arange(nv)),
+    }
+    for seed, size in DRAWS if draws else ():
+        table["draw_%d_of_%d" % (seed, size)] = exact_promotion(pb, (min(size, n), min(size, ns), min(size, nv)), seed, edges=False)
+    return table
+
+
+def promotion(pb, name):
+    """promotion_table(pb)[name] without making the rest of the table's draws"""
+    if name.startswith("draw_"):
+        seed, size = int(name.split("_")[1]), int(name.rsplit("_", 1)[1])
+        per = pb.n_inputs if hasattr(pb, "n_inputs") else 2
+        return exact_promotion(pb, (min(size, pb.n_regions), min(size, pb.n_regions * per), min(size, pb.n_variants)), seed, edges=False)
+    return promotion_table(pb, draws=False)[name]
+
+
+def exact_promotion(pb, sizes, seed=0, edges=True):
+    """(regions, slots, calls) to promote so that the three lists of the promoted batch have exactly `sizes` entries, what pb lists already included: a seeded
+    draw; edges: both ends of the batch and both sides of the block edges first — lists of an exact length for the scan's chunks of 1024"""
+    per = pb.n_inputs if hasattr(pb, "n_inputs") else 2
+    e, out = pb.escapes, []
+    for m, size, idx, first in ((pb.n_regions, sizes[0], e.esc_region, e.first_region), (pb.n_regions * per, sizes[1], e.esc_slot, e.first_slot),
+                                (pb.n_variants, sizes[2], e.esc_call, e.first_call)):
+        have = (idx - np.uint64(first)).astype(np.int64)
+        assert have.size <= size <= m, (have.size, size, m)
+        must = np.setdiff1d([i for i in BLOCK_EDGES + (0, m - 1) if i < m] if edges else [], have).astype(np.int64)[:size - have.size]
+        rest = np.setdiff1d(np.arange(m), np.concatenate([have, must]))
+        rng = np.random.default_rng(1000 * seed + size)
+        out.append(np.sort(np.concatenate([must, rng.choice(rest, size - have.size - must.size, replace=False)])))
+    return tuple(out)
+
+
+PROMOTIONS = ("nothing", "entry_0", "last_entry", "slots_and_window_of_one_region", "slots_and_window_of_the_busiest_region", "64_consecutive_calls",
+              "every_call_of_one_region", "every_call_of_the_busiest_region", "block_edges", "every_second", "every_second_odd", "all_calls", "everything") + tuple(
+                  "draw_%d_of_%d" % d for d in DRAWS)
+
+
+# ---- batches that break the form: AVK_E_ARG everywhere, by contract ----------------------------------------------------------------------------
+
+LISTS = {"region": ("esc_region", "first_region"), "slot": ("esc_slot", "first_slot"), "call": ("esc_call", "first_call")}
+SPOILS = ("duplicate", "swap_0_1", "swap_1023_1024", "last_is_count", "first_below_base")
+
+
+def copy_of(pb):
+    """a deep copy of a PackedBatch / PackedMultiBatch and its escapes"""
+    from aardvark_amd._abi import PackedEscapes
+    e = pb.escapes
+    esc = PackedEscapes(e.first_region, e.first_call, e.first_slot, **{f: getattr(e, f).copy() for f in PackedEscapes.FIELDS})
+    arrays = {f: (None if getattr(pb, f) is None else getattr(pb, f).copy()) for f in type(pb).FIELDS}
+    return type(pb)(pb.n_inputs, escapes=esc, **arrays) if hasattr(pb, "n_inputs") else type(pb)(escapes=esc, **arrays)
+
+
+def rebased(pb, regions=1_000, slots=None, calls=77_777):
+    """`pb` as a slice of a larger batch that has `regions` regions, `slots` count slots (default: regions times the slots of a region) and `calls` calls in front of
+    it: the three bases and every listed index shifted by these constants, nothing else (avk_packed_escapes carries the bases for both forms; a batch that has no
+    slicing of its own in Python, the multi form, gets non-zero bases this way)"""
+    out = copy_of(pb)
+    e = out.escapes
+    slots = regions * (pb.n_inputs if hasattr(pb, "n_inputs") else 2) if slots is None else slots
+    e.first_region, e.first_slot, e.first_call = e.first_region + regions, e.first_slot + slots, e.first_call + calls
+    e.esc_region += np.uint64(regions)
+    e.esc_slot += np.uint64(slots)
+    e.esc_call += np.uint64(calls)
+    return out
+
+
+def spoiled(pb, which, how):
+    """a copy of `pb` whose list `which` (LISTS) breaks the rule `how` (SPOILS): an equal neighbour; a swapped pair at 0 / 1 or across the scan's chunk edge at
+    1023 / 1024; a last index equal to first + count; a first index of first - 1 (pb must be a slice with non-zero bases).  Only indices change: every value the
+    lists and the batch hold stays a value the good batch holds."""
+    bad = copy_of(pb)
+    per = pb.n_inputs if hasattr(pb, "n_inputs") else 2
+    name, first = LISTS[which]
+    idx, first = getattr(bad.escapes, name), getattr(bad.escapes, first)
+    count = {"region": pb.n_regions, "slot": pb.n_regions * per, "call": pb.n_variants}[which]
+    if how == "duplicate":
+        assert idx.size >= 2
+        idx[idx.size // 2] = idx[idx.size // 2 - 1]
+    elif how == "swap_0_1":
+        assert idx.size >= 2
+        idx[:2] = idx[:2][::-1].copy()
+    elif how == "swap_1023_1024":
+        assert idx.size >= 2048
+        idx[1023:1025] = idx[1023:1025][::-1].copy()
+    elif how == "last_is_count":
+        assert idx.size >= 1
+        idx[-1] = first + count
+    elif how == "first_below_base":
+        assert idx.size >= 1 and first > 0
+        idx[0] = first - 1
+    else:
+        raise KeyError(how)
+    return bad
+
+
+def narrow_fields(pb):
+    return ("len", "in_cnt", "var_rel_pos", "a0_len", "a1_len") if hasattr(pb, "n_inputs") else ("len", "t_cnt", "q_cnt", "var_rel_pos", "a0_len", "a1_len")
+
+
+def nonzero_under_a_listed_entry(pb, field):
+    """a copy of `pb` with a 1 in narrow field `field` of one LISTED entry (the middle one of its list): the form says that field MUST be 0"""
+    bad = copy_of(pb)
+    e = bad.escapes
+    if field == "len":
+        getattr(bad, field)[int(e.esc_region[e.esc_region.size // 2] - e.first_region)] = 1
+    elif field in ("var_rel_pos", "a0_len", "a1_len"):
+        getattr(bad, field)[int(e.esc_call[e.esc_call.size // 2] - e.first_call)] = 1
+    else:
+        s = (e.esc_slot - np.uint64(e.first_slot)).astype(np.int64)
+        if field != "in_cnt":
+            s = s[s % 2 == (0 if field == "t_cnt" else 1)] // 2
+        getattr(bad, field)[int(s[s.size // 2])] = 1
+    return bad
 
 
 def region_contents(b, idx):

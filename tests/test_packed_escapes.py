@@ -154,6 +154,51 @@ def test_escape_lists_that_are_not_ascending_or_leave_the_batch_are_refused(job)
         assert lib.avk_packed_shard_make_esc(C.byref(st), C.byref(esc), None, 0, 0, 2, C.byref(h)) == -1  # AVK_E_ARG
 
 
+@pytest.fixture(scope="module")
+def long_part():
+    """(the genome job's packed batch, its second half — non-zero bases — with 2,048 entries in each list)"""
+    pb = el.escaped(el.genome_job()[1])[1]
+    part = pb.split(2)[1]
+    assert part.escapes.first_region > 0 and part.escapes.first_call > 0
+    return pb, el.promote(part, *el.exact_promotion(part, (2048, 2048, 2048)))
+
+
+def _shard_rc(lib, pb):
+    st, esc, h = pb.c_struct(), pb.escapes.c_struct(), C.c_void_p()
+    rc = lib.avk_packed_shard_make_esc(C.byref(st), C.byref(esc), None, 0, 0, 2, C.byref(h))
+    if rc == 0:
+        lib.avk_packed_shard_free(h)
+    return rc
+
+
+@pytest.mark.parametrize("which", sorted(el.LISTS))
+def test_every_list_is_checked_on_the_host_duplicates_chunk_edges_and_both_ends_of_the_range(long_part, which):
+    lib = shard_api()
+    good = long_part[1]
+    assert _shard_rc(lib, good) == 0
+    for how in el.SPOILS:
+        assert _shard_rc(lib, el.spoiled(good, which, how)) == -1, how  # AVK_E_ARG
+    # n_esc_* > 0 with a NULL index or value array
+    for name in {"region": ("esc_region", "esc_len"), "slot": ("esc_slot", "esc_cnt"), "call": ("esc_call", "esc_rel_pos", "esc_a0_len", "esc_a1_len")}[which]:
+        st, esc, h = good.c_struct(), good.escapes.c_struct(), C.c_void_p()
+        setattr(esc, name, None)
+        assert lib.avk_packed_shard_make_esc(C.byref(st), C.byref(esc), None, 0, 0, 2, C.byref(h)) == -1, name
+
+
+def test_a_listed_entry_whose_narrow_field_is_not_zero_is_refused_by_the_shards(long_part):
+    """the rule of avk_packed_escapes, for all five narrow fields (six arrays): the host route refuses what the device route refuses (tests/test_gpu_packed_escapes.py
+    hands the same batches to avk_compare_packed_esc)"""
+    lib = shard_api()
+    plain, good = long_part
+    assert _shard_rc(lib, good) == 0
+    for field in el.narrow_fields(good):
+        assert _shard_rc(lib, el.nonzero_under_a_listed_entry(good, field)) == -1, field
+    # ... and of the batch as the packer made it (short lists; it lists no query-side count)
+    assert not (plain.escapes.esc_slot % np.uint64(2)).any() and _shard_rc(lib, plain) == 0
+    for field in [f for f in el.narrow_fields(plain) if f != "q_cnt"]:
+        assert _shard_rc(lib, el.nonzero_under_a_listed_entry(plain, field)) == -1, field
+
+
 # ---- the multi form ---------------------------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
@@ -233,6 +278,39 @@ def test_multi_shards_with_escapes_scatter_and_counts(multi_job, world):
     P = lambda a, t: np.ascontiguousarray(a).ctypes.data_as(C.POINTER(t))
     cb, plain = pm.c_struct(), np.zeros(summed.size, np.uint64)
     assert _shard_api(lib).avk_merge_counts(C.byref(cb), P(res.status, C.c_int32), P(res.classification, C.c_uint8), P(res.members, C.c_uint64), P(plain, C.c_uint64)) == -1
+
+
+def test_the_multi_form_refuses_bad_lists_and_non_zero_narrow_fields_on_the_host(multi_job):
+    from aardvark_amd.merge import _shard_api
+    contigs, mb, pm = multi_job
+    lib = _shard_api(aardvark_amd.load_library())
+    ids = mb.region_id + np.uint64(5)
+    res = random_results(pm.n_regions, 3, 9)
+    # 2,048 entries in each list, and the bases of a slice of a larger batch: avk_packed_escapes carries them for both forms
+    good = el.rebased(el.promote(pm, *el.exact_promotion(pm, (2048, 2048, 2048))))
+    assert good.escapes.first_region > 0 and good.escapes.first_slot > 0 and good.escapes.first_call > 0
+    assert np.array_equal(merge_counts(lib, good, res), merge_counts(lib, pm, res))  # the promoted, rebased batch is the same batch
+    shard, idx = shard_packed_multi(lib, good, ids, 0, 2)
+    assert el.same_contents(multi_contents(shard.widen(), np.arange(shard.n_regions)), multi_contents(mb, idx)) == []
+    bad = [(which, el.spoiled(good, which, how)) for which in sorted(el.LISTS) for how in el.SPOILS]
+    bad += [(field, el.nonzero_under_a_listed_entry(b, field)) for b in (good, pm) for field in el.narrow_fields(good)]
+    assert len(bad) == 15 + 10
+    for what, b in bad:
+        with pytest.raises(ValueError):
+            shard_packed_multi(lib, b, ids, 0, 2)
+        if what in ("slot", "in_cnt"):  # avk_merge_counts_esc reads the count slots only: it checks what it reads
+            with pytest.raises(ValueError):
+                merge_counts(lib, b, res)
+    # n_esc_* > 0 with a NULL index or value array
+    P = lambda a, t: np.ascontiguousarray(a).ctypes.data_as(C.POINTER(t))
+    for name in PackedEscapes.FIELDS:
+        st, esc, h = good.c_struct(), good.escapes.c_struct(), C.c_void_p()
+        setattr(esc, name, None)
+        assert lib.avk_packed_multi_shard_make_esc(C.byref(st), C.byref(esc), P(ids, C.c_uint64), 0, 0, 2, C.byref(h)) == -1 and not h.value, name
+        if name in ("esc_slot", "esc_cnt"):
+            counts = np.zeros(merge_counts_len(lib, 3), np.uint64)
+            assert lib.avk_merge_counts_esc(C.byref(st), C.byref(esc), P(res.status, C.c_int32), P(res.classification, C.c_uint8), P(res.members, C.c_uint64), P(counts, C.c_uint64)) == -1
+            assert not counts.any()
 
 
 # ---- the feeder -------------------------------------------------------------------------------------------------------------------------------
