@@ -129,6 +129,24 @@ class AvkPackedEscapes(C.Structure):
     ]
 
 
+class AvkRegionLabels(C.Structure):
+    """avk_region_labels: the containment labels of a batch's regions (label_idx[label_off[r] .. label_off[r + 1]) are region r's)"""
+    _fields_ = [
+        ("n_labels", C.c_uint32),
+        ("label_off", _p(C.c_uint64)),
+        ("label_idx", _p(C.c_uint32)),
+    ]
+
+
+def region_labels(n_labels, label_off, label_idx):
+    """(AvkRegionLabels, the arrays it points into) from the three parts of a labels=(n_labels, off, idx) argument"""
+    off = np.ascontiguousarray(label_off, np.uint64)
+    idx = np.ascontiguousarray(label_idx, np.uint32)
+    if idx.size == 0:
+        idx = np.zeros(1, np.uint32)
+    return AvkRegionLabels(int(n_labels), off.ctypes.data_as(_p(C.c_uint64)), idx.ctypes.data_as(_p(C.c_uint32))), (off, idx)
+
+
 class AvkCompareConfig(C.Structure):
     _fields_ = [
         ("max_branch_factor", C.c_uint32),

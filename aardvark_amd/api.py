@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkResultBatch, CompactBatch, PackedBatch,
-                   RegionBatch, ResultBatch)
+from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
+                   PackedBatch, RegionBatch, ResultBatch, region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -68,6 +68,14 @@ def load_library():
     lib.avk_compare_packed_esc.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch)]
     lib.avk_compare_packed_submit_esc.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), C.POINTER(vp)]
     lib.avk_batch_upload_packed_esc.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, C.POINTER(vp)]
+    if hasattr(lib, "avk_label_block"):  # stratified sums from the compact results (avk_labels.inl); (AVK_LIB may name an older in-tree build: A/B runs)
+        lab = C.POINTER(AvkRegionLabels)
+        lib.avk_label_block.restype = C.c_uint32
+        lib.avk_label_block.argtypes = [vp]
+        lib.avk_label_tallies_compact.argtypes = [vp, vp, lab, u64p]
+        lib.avk_compare_packed_labels.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, lab, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p]
+        lib.avk_compare_packed_submit_labels.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, lab, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p, C.POINTER(vp)]
+        lib.avk_packed_shard_labels.argtypes = [vp, lab, u64p, C.POINTER(C.c_uint32)]
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
     lib.avk_results_download.argtypes = [vp, vp, C.POINTER(AvkResultBatch)]
     lib.avk_batch_free.argtypes = [vp, vp]
@@ -237,24 +245,42 @@ class Context:
         esc = None if pbatch.escapes is None else pbatch.escapes.pinned(self.host_array)
         return PackedBatch(escapes=esc, **{f: pin(getattr(pbatch, f)) for f in PackedBatch.FIELDS})
 
-    def solve_packed(self, pbatch, config=None, res=None):
-        """avk_compare_packed: solve_compare_region for every region of a batch in the packed form -> ResultBatch (indexed like the packed arrays)"""
+    def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None):
+        """avk_compare_packed: solve_compare_region for every region of a batch in the packed form -> ResultBatch (indexed like the packed arrays).
+        labels=(n_labels, label_off, label_idx): avk_compare_packed_labels — the per-label sums come back as res.label_tallies, a [n_labels, TALLY_LEN] uint64
+        array (label_tallies: an array of that shape the sums are added to instead)"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
         pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
+        if labels is not None:
+            lab, _keep = region_labels(*labels)
+            sums = np.zeros((int(labels[0]), TALLY_LEN), np.uint64) if label_tallies is None else label_tallies
+            self._check(self.lib.avk_compare_packed_labels(self.handle, C.byref(pb), None if esc is None else C.byref(esc), C.byref(lab), C.byref(cfg), C.byref(ro),
+                                                           sums.ctypes.data_as(u64p)))
+            res.label_tallies = sums
+            return res
         if esc is None:
             self._check(self.lib.avk_compare_packed(self.handle, C.byref(pb), C.byref(cfg), C.byref(ro)))
         else:
             self._check(self.lib.avk_compare_packed_esc(self.handle, C.byref(pb), C.byref(esc), C.byref(cfg), C.byref(ro)))
         return res
 
-    def submit_packed(self, pbatch, config=None, res=None):
+    def submit_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None):
         """avk_compare_packed_submit: the batch is queued (its copies run beside the kernels of the batch submitted before) -> a Ticket; Ticket.wait() -> ResultBatch.
-        `pbatch` and `res` must live in pinned memory (pinned_packed / pinned_results) for the copies to overlap anything; at most four tickets are in flight."""
+        `pbatch` and `res` must live in pinned memory (pinned_packed / pinned_results) for the copies to overlap anything; at most four tickets are in flight.
+        labels=(n_labels, label_off, label_idx): avk_compare_packed_submit_labels — res.label_tallies holds the per-label sums once wait() has returned (pin the
+        two arrays with host_array for the submit to stay asynchronous)"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
         pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
         handle = C.c_void_p()
+        if labels is not None:
+            lab, keep = region_labels(*labels)
+            sums = np.zeros((int(labels[0]), TALLY_LEN), np.uint64) if label_tallies is None else label_tallies
+            self._check(self.lib.avk_compare_packed_submit_labels(self.handle, C.byref(pb), None if esc is None else C.byref(esc), C.byref(lab), C.byref(cfg), C.byref(ro),
+                                                                  sums.ctypes.data_as(u64p), C.byref(handle)))
+            res.label_tallies = sums
+            return Ticket(self, handle, res, (pbatch, pb, ro, esc, lab, keep, sums))
         if esc is None:
             self._check(self.lib.avk_compare_packed_submit(self.handle, C.byref(pb), C.byref(cfg), C.byref(ro), C.byref(handle)))
         else:
@@ -347,6 +373,18 @@ class Context:
         self.lib.avk_label_tallies.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         self._check(self.lib.avk_label_tallies(self.handle, rb.handle, n_labels, off.ctypes.data_as(C.POINTER(C.c_uint64)), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def label_block(self):
+        """avk_label_block: how many labels one launch of the compact label kernel sums (more labels: more passes over the regions)"""
+        return int(self.lib.avk_label_block(self.handle))
+
+    def label_tallies_compact(self, rb, n_labels, label_off, label_idx, out=None):
+        """avk_label_tallies_compact: the sums of label_tallies without per-region metric blocks — from the resident batch's compact results (needs
+        emit_bp_groups during compare_resident; emit_group_metrics may be 0); returns / adds to a [n_labels, TALLY_LEN] uint64 array"""
+        out = np.zeros((n_labels, TALLY_LEN), np.uint64) if out is None else out
+        lab, _keep = region_labels(n_labels, label_off, label_idx)
+        self._check(self.lib.avk_label_tallies_compact(self.handle, rb.handle, C.byref(lab), out.ctypes.data_as(u64p)))
         return out
 
     def synchronize(self):

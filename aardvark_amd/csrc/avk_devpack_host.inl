@@ -871,6 +871,9 @@ struct PackedOnDevice {
     /* the escape lists of the batch (avk_packed_escapes), copied with the rest; NULL without escapes */
     uint64_t *esc_region, *esc_slot, *esc_call;
     uint32_t *esc_len, *esc_cnt, *esc_rel, *esc_a0, *esc_a1;
+    /* the label lists of a batch submitted with labels (avk_region_labels), copied with the rest; NULL without labels */
+    uint64_t *lab_off;
+    uint32_t *lab_idx;
 };
 /* an avk_packed_escapes that lists something, with every array it needs */
 static inline bool esc_present(const avk_packed_escapes *e) { return e && (e->n_esc_regions || e->n_esc_slots || e->n_esc_calls); }
@@ -1511,6 +1514,10 @@ struct DownloadLater {
     /* the parts of ONE split call (compare_packed_split) spill their BASEPAIR groups into one device buffer behind one counter: a part's dp_unpack appends where the
      * part before it stopped, the words it writes index the call's one list, and the caller reads the count and copies the list once, after the last part */
     uint32_t *shared_spill = nullptr, *shared_spill_count = nullptr;
+    /* a batch submitted with labels (avk_compare_packed_submit_labels): the labels' sums cross with the results, in front of ev_done */
+    const void *lab_dev = nullptr;
+    void *lab_host = nullptr;
+    size_t lab_bytes = 0;
 };
 static int download_device_packed(avk_ctx *ctx, avk_dev_batch *db, avk_result_batch *out, uint8_t *pair_exact, uint64_t *tally_words /* [AVK_TALLY_STRIDE] */,
                                   DownloadLater *later = nullptr) {
@@ -1607,6 +1614,7 @@ static int download_device_packed(avk_ctx *ctx, avk_dev_batch *db, avk_result_ba
         for (const CopySeg &sg : segs)
             if (el == hipSuccess && sg.bytes && sg.host) el = hipMemcpyAsync((void *)sg.host, sg.dev, sg.bytes, hipMemcpyDeviceToHost, so);
         if (el == hipSuccess) el = hipMemcpyAsync(later->h_tally, db->d_tally, (size_t)AVK_TALLY_STRIDE * 8, hipMemcpyDeviceToHost, so);
+        if (el == hipSuccess && later->lab_bytes) el = hipMemcpyAsync(later->lab_host, later->lab_dev, later->lab_bytes, hipMemcpyDeviceToHost, so);
         if (el == hipSuccess) el = hipEventRecord(later->ev_done, so);
         if (el != hipSuccess) {
             (void)hipStreamSynchronize(so);

@@ -35,6 +35,7 @@
 #include "avk_wide.inl"
 #include "avk_dwfa_script.inl"
 #include "avk_devpack.inl"
+#include "avk_labels.inl"
 
 /* ---------------------------------------------------------------------------------- kernels */
 /* LDS passes: regions in the LDS slice of their wavefront (small slices at high occupancy first, then
@@ -359,7 +360,12 @@ struct avk_ctx {
         uint64_t *h_tally = nullptr; /* pinned: the batch's tally lands here */
         hipEvent_t ev_in = nullptr, ev_unpacked = nullptr, ev_done = nullptr;
         bool busy = false;
+        uint64_t *h_labels = nullptr; /* pinned: the label sums of a batch submitted with labels land here (grown on demand) */
+        size_t h_labels_words = 0;
     } stage[4];
+    hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr; /* AVK_TIMING: around the label kernels */
+    int64_t label_lds_bytes = 0;       /* LDS a launch of avk_label_tally_compact_kernel gets (0: not asked yet) */
+    struct LabelFix *label_fix = nullptr; /* set while a one-call form with labels downloads: the capacity retry adds the repaired regions' blocks to the labels' sums */
     /* options */
     int64_t lds_bytes_per_wave = 10 * 1024;
     int64_t lds_ed_cap = 48;
@@ -507,6 +513,7 @@ struct avk_dev_batch {
     avk_compare_config last_cfg = {50, 0, 0}; /* the configuration of the last run (the capacity retry of avk_results_download repeats it) */
     uint32_t last_mode = 0;
     bool has_run = false;
+    bool bp_valid = false; /* d_bp holds the groups of the last run (it ran in compare mode with emit_bp_groups) */
     bool scratch_clean = false; /* partial tallies and counters are zero */
     bool with_gm = true;
     /* device-packed batches (avk_devpack_host.inl): every buffer comes from the context's pool; `host` stays empty unless the capacity retry or
@@ -710,6 +717,7 @@ void avk_ctx_destroy(avk_ctx *ctx) {
     for (auto &sl : ctx->stage) { /* staging slots of the asynchronous boundary */
         if (sl.dev) (void)hipFree(sl.dev);
         if (sl.h_tally) (void)hipHostFree(sl.h_tally);
+        if (sl.h_labels) (void)hipHostFree(sl.h_labels);
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
         if (sl.ev_unpacked) (void)hipEventDestroy(sl.ev_unpacked);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
@@ -730,6 +738,8 @@ void avk_ctx_destroy(avk_ctx *ctx) {
     for (hipEvent_t &t : ctx->ev_tl)
         if (t) (void)hipEventDestroy(t);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
+    if (ctx->ev_lab0) (void)hipEventDestroy(ctx->ev_lab0);
+    if (ctx->ev_lab1) (void)hipEventDestroy(ctx->ev_lab1);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->evk1) (void)hipEventDestroy(ctx->evk1);
     if (ctx->ev_lane) (void)hipEventDestroy(ctx->ev_lane);
@@ -2163,6 +2173,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
     db->last_cfg = *cfg;
     db->last_mode = mode;
     db->has_run = true;
+    db->bp_valid = ctx->emit_bp_groups && mode == 0 && db->d_bp != nullptr;
     if (timed) AVK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->ev_valid = timed;
     return 0;
@@ -2383,6 +2394,18 @@ static int rerun_capacity_regions(avk_ctx *ctx, avk_dev_batch *db, const std::ve
 }
 
 } /* extern "C" */
+/* a one-call form with labels (avk_compare_packed_labels, avk_wait of a submit with labels): its label kernel ran before the capacity retry, so the blocks of the
+ * regions the retry repairs are added to the labels' sums here, on the host */
+struct LabelFix {
+    const avk_region_labels *lab;
+    uint64_t *out; /* [n_labels * AVK_TALLY_LEN] */
+};
+static void label_fix_add(LabelFix *lf, uint64_t r, const uint32_t *block) {
+    for (uint64_t q = lf->lab->label_off[r]; q < lf->lab->label_off[r + 1]; ++q) {
+        uint64_t *dst = lf->out + (size_t)lf->lab->label_idx[q] * AVK_TALLY_LEN;
+        for (int i = 0; i < AVK_N_GROUPS * AVK_N_FIELDS; ++i) dst[i] += block[i];
+    }
+}
 /* avk_results_download in one piece (later == NULL), or in the two pieces of the asynchronous boundary: everything up to the queued copies (later given, tally_ready
  * NULL), and everything behind them — the tally, the statistics, the capacity retry — once the copies have arrived (tally_ready = the batch's tally words) */
 static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_batch *out, DownloadLater *later, const uint64_t *tally_ready) {
@@ -2499,9 +2522,11 @@ static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_bat
             if ((int64_t)slice <= ctx->big_ws_bytes) continue;
             CapacityFix fx;
             const bool dev_gm = ctx->emit_group_metrics && db->d_gm; /* the batch keeps per-region blocks on the device (avk_label_tallies reads them) */
-            const bool want_gm = (out->group_metrics && ctx->emit_group_metrics && db->d_gm) || dev_gm;
+            /* ... or the compact view avk_label_tallies_compact reads: the repaired region's per-call words and BASEPAIR groups are patched as well */
+            const bool dev_compact = db->dev_packed && db->bp_valid && db->d_bp && db->d_bp_off && db->d_var_out;
+            const bool want_gm = (out->group_metrics && ctx->emit_group_metrics && db->d_gm) || dev_gm || ctx->label_fix != nullptr;
             const bool want_bp_words = out->bp_packed && out->bp_spilled && out->bp_groups && db->d_bp;
-            const bool want_bp = (out->bp_off && out->bp_groups && db->d_bp) || want_bp_words;
+            const bool want_bp = (out->bp_off && out->bp_groups && db->d_bp) || want_bp_words || dev_compact;
             const int rc = rerun_capacity_regions(ctx, db, cap, want_gm, want_seq, want_bp, slice, &fx);
             if (rc == AVK_E_OOM) break; /* the device cannot hold slices of this size: the regions keep their status */
             if (rc) { /* reported after the statistics and the shared slices are back as they were (below) */
@@ -2531,13 +2556,31 @@ static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_bat
                     const uint64_t sv = fx.v_first[k] + i;
                     put_call(db->host.dev2host[dr.v_off + i], fx.ve[sv], fx.vo[sv], fx.vc[sv], fx.vz[sv]);
                 }
+                if (dev_compact) { /* the device's per-call words and groups of the region, as the kernels would have left them */
+                    const uint32_t nc = dr.t_cnt + dr.q_cnt, ng = fx.bp_off[k + 1] - fx.bp_off[k];
+                    std::vector<uint32_t> words(nc + 1);
+                    for (uint32_t i = 0; i < nc; ++i) {
+                        const uint64_t sv = fx.v_first[k] + i;
+                        words[i] = (uint32_t)fx.ve[sv] | (uint32_t)fx.vo[sv] << 8 | (uint32_t)fx.vc[sv] << 16 | (uint32_t)fx.vz[sv] << 24;
+                    }
+                    uint32_t bo[2] = {0, 0};
+                    hipError_t ew = hipMemcpyAsync(bo, db->d_bp_off + r, sizeof(bo), hipMemcpyDeviceToHost, s);
+                    if (ew == hipSuccess && nc) ew = hipMemcpyAsync(db->d_var_out + dr.v_off, words.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s);
+                    if (ew == hipSuccess) ew = hipStreamSynchronize(s);
+                    if (ew == hipSuccess && ng && bo[1] - bo[0] == ng) { /* the same calls, so the same groups */
+                        ew = hipMemcpyAsync(db->d_bp + 4 * (size_t)bo[0], fx.bp.data() + 4 * (size_t)fx.bp_off[k], 16 * (size_t)ng, hipMemcpyHostToDevice, s);
+                        if (ew == hipSuccess) ew = hipStreamSynchronize(s);
+                    }
+                    if (ew != hipSuccess && !retry_rc) retry_rc = fail(ctx, AVK_E_HIP, "capacity retry: %s", hipGetErrorString(ew));
+                }
+                if (ctx->label_fix && fx.status[k] == 0) label_fix_add(ctx->label_fix, r, fx.gm.data() + (size_t)k * AVK_N_GROUPS * AVK_N_FIELDS);
                 if (want_gm && out->group_metrics) memcpy(out->group_metrics + (size_t)r * AVK_N_GROUPS * AVK_N_FIELDS, fx.gm.data() + (size_t)k * AVK_N_GROUPS * AVK_N_FIELDS, sizeof(uint32_t) * AVK_N_GROUPS * AVK_N_FIELDS);
                 if (want_bp_words) { /* the packed form: the repaired region's groups join the spilled ones */
                     const uint32_t ng = fx.bp_off[k + 1] - fx.bp_off[k], at = out->bp_spilled[0];
                     memcpy(out->bp_groups + 4 * (size_t)at, fx.bp.data() + 4 * (size_t)fx.bp_off[k], 16 * (size_t)ng);
                     out->bp_packed[r] = AVK_BP_SPILL | at;
                     out->bp_spilled[0] = at + ng;
-                } else if (want_bp && out->bp_off[r + 1] - out->bp_off[r] == fx.bp_off[k + 1] - fx.bp_off[k]) /* the same calls, so the same groups */
+                } else if (want_bp && out->bp_off && out->bp_groups && out->bp_off[r + 1] - out->bp_off[r] == fx.bp_off[k + 1] - fx.bp_off[k]) /* the same calls, so the same groups */
                     memcpy(out->bp_groups + 4 * (size_t)out->bp_off[r], fx.bp.data() + 4 * (size_t)fx.bp_off[k], 16 * (size_t)(fx.bp_off[k + 1] - fx.bp_off[k]));
                 if (want_seq)
                     for (int q = 0; q < 5; ++q) {
@@ -2584,7 +2627,83 @@ struct avk_ticket {
     avk_result_batch out;
     DownloadLater later;
     int64_t keep_gm = 0, keep_bp = 0;
+    /* submitted with labels: the lists (the caller's arrays, read again should the capacity retry repair a region), where the sums go, the device sums */
+    bool has_lab = false;
+    avk_region_labels lab;
+    uint64_t *lab_out = nullptr;
+    void *d_lab_out = nullptr;
 };
+
+/* ---- stratified sums from the compact results (avk_labels.inl) -------------------------------------------------------------------------------- */
+static int64_t label_lds(avk_ctx *ctx) { /* the LDS a launch of the label kernel really gets: the whole CU's where the runtime grants it */
+    if (!ctx->label_lds_bytes) {
+        int64_t b = 64 * 1024;
+        if (hipFuncSetAttribute((const void *)avk_label_tally_compact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) b = 160 * 1024;
+        else {
+            (void)hipGetLastError();
+            int attr = 0;
+            if (hipDeviceGetAttribute(&attr, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) == hipSuccess && attr > 0 && attr < b) b = attr;
+            else (void)hipGetLastError();
+        }
+        ctx->label_lds_bytes = b;
+    }
+    return ctx->label_lds_bytes;
+}
+static uint32_t label_block(avk_ctx *ctx) {
+    const int64_t b = label_lds(ctx) / AVK_LB_LABEL_BYTES;
+    return b < 1 ? 1u : (uint32_t)b;
+}
+/* the refusals of every entry point with labels, before anything is queued */
+static int labels_check(avk_ctx *ctx, uint64_t n, const avk_region_labels *lab, const uint64_t *label_tallies) {
+    if (!lab->label_off) return fail(ctx, AVK_E_ARG, "label_off missing");
+    for (uint64_t r = 0; r < n; ++r)
+        if (lab->label_off[r + 1] < lab->label_off[r]) return fail(ctx, AVK_E_ARG, "label_off must not decrease");
+    const uint64_t n_idx = lab->label_off[n];
+    if (n_idx && !lab->label_idx) return fail(ctx, AVK_E_ARG, "label_idx missing: label_off names %llu entries", (unsigned long long)n_idx);
+    for (uint64_t q = lab->label_off[0]; q < n_idx; ++q)
+        if (lab->label_idx[q] >= lab->n_labels) return fail(ctx, AVK_E_ARG, "label index %u of %u", lab->label_idx[q], lab->n_labels);
+    if (!label_tallies) return fail(ctx, AVK_E_ARG, "label_tallies missing");
+    return 0;
+}
+/* the label kernel over the blocks of labels, on stream s behind the batch's solve: d_out[n_labels * AVK_TALLY_LEN] gains the sums */
+static int labels_launch(avk_ctx *ctx, avk_dev_batch *db, const uint64_t *d_off, const uint32_t *d_idx, uint32_t n_labels, uint64_t *d_out, hipStream_t s) {
+    const uint64_t n = db->n_regions;
+    if (!n || !n_labels) return 0;
+    avk::lb::LbView v;
+    memset(&v, 0, sizeof(v));
+    v.in = db->dp_args.in, v.vinfo = db->dp_args.vinfo, v.region_out = db->d_region_out, v.var_out = db->d_var_out, v.v_off = db->d_voff, v.bp_off = db->d_bp_off, v.bp = db->d_bp;
+    const uint32_t B = label_block(ctx);
+    const bool timing = getenv("AVK_TIMING") != nullptr;
+    if (timing) {
+        if (!ctx->ev_lab0 && hipEventCreate(&ctx->ev_lab0) != hipSuccess) ctx->ev_lab0 = nullptr, (void)hipGetLastError();
+        if (!ctx->ev_lab1 && hipEventCreate(&ctx->ev_lab1) != hipSuccess) ctx->ev_lab1 = nullptr, (void)hipGetLastError();
+        if (ctx->ev_lab0) (void)hipEventRecord(ctx->ev_lab0, s);
+    }
+    for (uint32_t lo = 0; lo < n_labels; lo += B) {
+        const uint32_t hi = n_labels - lo > B ? lo + B : n_labels;
+        const size_t lds = (size_t)(hi - lo) * AVK_LB_LABEL_BYTES;
+        /* a CU runs 2,048 work-items: two workgroups where their sums fit beside each other */
+        const uint32_t per_cu = lds * 2 <= (size_t)label_lds(ctx) ? 2u : 1u;
+        uint64_t blocks = (n + 1023) / 1024;
+        if (blocks > (uint64_t)ctx->n_cus * per_cu) blocks = (uint64_t)ctx->n_cus * per_cu;
+        hipLaunchKernelGGL(avk_label_tally_compact_kernel, dim3((unsigned)blocks), dim3(1024), lds, s, v, (const unsigned long long *)d_off, d_idx, (uint32_t)n, lo, hi,
+                           (unsigned long long *)d_out);
+        AVK_HIP(ctx, hipGetLastError());
+    }
+    if (timing && ctx->ev_lab1) (void)hipEventRecord(ctx->ev_lab1, s);
+    return 0;
+}
+static void labels_timing_print(avk_ctx *ctx, const char *route, uint32_t n_labels, uint64_t n, uint64_t n_idx) { /* behind a synchronisation with the kernels' stream */
+    if (!getenv("AVK_TIMING") || !ctx->ev_lab0 || !ctx->ev_lab1) return;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev_lab0, ctx->ev_lab1) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    const uint32_t B = label_block(ctx);
+    fprintf(stderr, "avk label tallies (compact, %s): %u labels in %u launches of at most %u, %llu regions, %llu list entries: kernels %.3f ms\n", route, n_labels, (n_labels + B - 1) / B, B,
+            (unsigned long long)n, (unsigned long long)n_idx, ms);
+}
 
 static int stage_slot_prepare(avk_ctx *ctx, avk_ctx::StageSlot &sl, size_t bytes) {
     if (!ctx->copy_in_stream || !ctx->copy_out_stream || !ctx->pack_stream || !ctx->pack_side_stream) {
@@ -2626,13 +2745,15 @@ static int stage_slot_prepare(avk_ctx *ctx, avk_ctx::StageSlot &sl, size_t bytes
 
 /* the eleven arrays of `batch` into a staging slot: the slot is (re)sized and the copies are queued on the copy-in stream, counts and lengths first as in
  * avk_compare_packed — nothing of this context reads or writes the slot */
-static int stage_layout(avk_ctx *ctx, avk_ctx::StageSlot &sl, const avk_packed_batch *batch, const avk_packed_escapes *esc, PackedOnDevice *pre) {
+static int stage_layout(avk_ctx *ctx, avk_ctx::StageSlot &sl, const avk_packed_batch *batch, const avk_packed_escapes *esc, PackedOnDevice *pre,
+                        const avk_region_labels *lab = nullptr) {
     const uint64_t n = batch->n_regions, nv = batch->n_variants, alen = batch->allele_bytes_len;
     const bool has_contig = batch->contig_idx != nullptr, has_raw = batch->var_raw_space != nullptr;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const uint64_t er = esc ? esc->n_esc_regions : 0, es = esc ? esc->n_esc_slots : 0, ec = esc ? esc->n_esc_calls : 0; /* (esc: NULL unless it lists something) */
     const size_t need = 2 * up(n + 16) + 3 * up(nv + 16) + up(n * 4 + 16) + 2 * up(n * 2 + 16) + up(nv * 2 + 16) + up(nv * 4 + 16) + up(alen + 16) +
-                        (esc ? up(er * 8 + 16) + up(er * 4 + 16) + up(es * 8 + 16) + up(es * 4 + 16) + up(ec * 8 + 16) + 3 * up(ec * 4 + 16) : 0);
+                        (esc ? up(er * 8 + 16) + up(er * 4 + 16) + up(es * 8 + 16) + up(es * 4 + 16) + up(ec * 8 + 16) + 3 * up(ec * 4 + 16) : 0) +
+                        (lab ? up((n + 1) * 8 + 16) + up(lab->label_off[n] * 4 + 16) : 0);
     {
         const int rc = stage_slot_prepare(ctx, sl, need);
         if (rc) return rc;
@@ -2658,6 +2779,16 @@ static int stage_layout(avk_ctx *ctx, avk_ctx::StageSlot &sl, const avk_packed_b
                 (void)hipStreamSynchronize(ctx->copy_in_stream);
                 return fail(ctx, AVK_E_HIP, "queueing the batch's copies failed: %s", hipGetErrorString(hipGetLastError()));
             }
+    }
+    if (lab) { /* the label lists ride on the copy stream as well */
+        const uint64_t n_idx = lab->label_off[n];
+        pre->lab_off = (uint64_t *)take((n + 1) * 8), pre->lab_idx = (uint32_t *)take(n_idx * 4);
+        hipError_t el = hipMemcpyAsync(pre->lab_off, lab->label_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->copy_in_stream);
+        if (el == hipSuccess && n_idx) el = hipMemcpyAsync(pre->lab_idx, lab->label_idx, n_idx * 4, hipMemcpyHostToDevice, ctx->copy_in_stream);
+        if (el != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->copy_in_stream);
+            return fail(ctx, AVK_E_HIP, "queueing the batch's copies failed: %s", hipGetErrorString(el));
+        }
     }
     const struct { const void *src; void *dst; size_t bytes; } cp[] = {
         {batch->t_cnt, pre->t_cnt, n}, {batch->q_cnt, pre->q_cnt, n}, {batch->a0_len, pre->a0_len, nv}, {batch->a1_len, pre->a1_len, nv}, {batch->start, pre->start, n * 4},
@@ -2685,7 +2816,7 @@ static bool packed_inputs_pinned(const avk_packed_batch *batch, const avk_packed
 }
 
 static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket, uint32_t *shared_spill,
-                       uint32_t *shared_spill_count, const avk_packed_escapes *esc = nullptr);
+                       uint32_t *shared_spill_count, const avk_packed_escapes *esc = nullptr, const avk_region_labels *lab = nullptr, uint64_t *label_tallies = nullptr);
 int avk_compare_packed_submit(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket) {
     return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr);
 }
@@ -2696,7 +2827,12 @@ int avk_compare_packed_submit_esc(avk_ctx *ctx, const avk_packed_batch *batch, c
 /* shared_spill / shared_spill_count: the device list and counter the parts of one split call spill their BASEPAIR groups into (compare_packed_split); with them a
  * batch that returns the packed groups can be queued like any other */
 static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket, uint32_t *shared_spill,
-                       uint32_t *shared_spill_count, const avk_packed_escapes *esc) {
+                       uint32_t *shared_spill_count, const avk_packed_escapes *esc, const avk_region_labels *lab, uint64_t *label_tallies) {
+    if (lab && lab->n_labels == 0) lab = nullptr; /* (no labels: the call without them, launch for launch) */
+    if (lab && batch) { /* (first of all: these refusals need no device, avk_last_error(NULL) has their text when ctx is NULL) */
+        const int rl = labels_check(ctx, batch->n_regions, lab, label_tallies);
+        if (rl) return rl;
+    }
     if (!ctx || !batch || !cfg || !out || !ticket || !(out->status || out->region_packed)) return AVK_E_ARG;
     *ticket = nullptr;
     if (!esc_present(esc)) esc = nullptr;
@@ -2717,6 +2853,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     pinned = pinned && is_pinned(out->status, n * 4) && is_pinned(out->region_packed, n * 8) && is_pinned(out->ed_h1, n * 4) && is_pinned(out->ed_h2, n * 4) && is_pinned(out->n_optima, n * 4) &&
              is_pinned(out->type_present, n * 2) && is_pinned(out->var_expected, nv) && is_pinned(out->var_observed, nv) && is_pinned(out->var_class, nv) && is_pinned(out->var_zyg, nv) &&
              is_pinned(out->var_packed, nv) && is_pinned(out->group_metrics, n * AVK_N_GROUPS * AVK_N_FIELDS * 4);
+    if (lab) pinned = pinned && is_pinned(lab->label_off, (n + 1) * 8) && is_pinned(lab->label_idx, lab->label_off[n] * 4);
     const bool seq_out = out->seq_bytes && out->seq_len && out->seq_off && out->seq_stride && cfg->enable_sequences;
     int slot = -1;
     const bool bp_words = out->bp_packed && out->bp_spilled && out->bp_groups && !out->bp_off;
@@ -2732,7 +2869,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
         return fail(ctx, AVK_E_STATE, "four batches are in flight: avk_wait for one of them first");
     }
     if (slot < 0) { /* solved here and now (it uses no staging slot): a complete ticket on success, no ticket on failure — the caller owns what it is handed */
-        const int rc_now = avk_compare_packed_esc(ctx, batch, esc, cfg, out);
+        const int rc_now = lab ? avk_compare_packed_labels(ctx, batch, esc, lab, cfg, out, label_tallies) : avk_compare_packed_esc(ctx, batch, esc, cfg, out);
         if (rc_now) {
             delete t;
             return rc_now;
@@ -2743,17 +2880,26 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     }
     avk_ctx::StageSlot &sl = ctx->stage[slot];
     PackedOnDevice pre;
-    int rc = stage_layout(ctx, sl, batch, esc, &pre);
+    int rc = stage_layout(ctx, sl, batch, esc, &pre, lab);
+    if (!rc && lab && sl.h_labels_words < (size_t)lab->n_labels * AVK_TALLY_LEN) { /* the pinned block the sums land in */
+        if (sl.h_labels) (void)hipHostFree(sl.h_labels);
+        sl.h_labels = nullptr, sl.h_labels_words = 0;
+        hipError_t eh = hipHostMalloc((void **)&sl.h_labels, (size_t)lab->n_labels * AVK_TALLY_LEN * sizeof(uint64_t), hipHostMallocDefault);
+        if (eh != hipSuccess) rc = fail(ctx, AVK_E_HIP, "pinned block of the label sums: %s", hipGetErrorString(eh));
+        else sl.h_labels_words = (size_t)lab->n_labels * AVK_TALLY_LEN;
+    }
     if (rc) {
+        (void)hipStreamSynchronize(ctx->copy_in_stream);
         delete t;
         return rc;
     }
+    if (lab) t->has_lab = true, t->lab = *lab, t->lab_out = label_tallies;
     const double ts1 = now_ms();
     sl.busy = true;
     t->slot = slot;
     t->keep_gm = ctx->emit_group_metrics, t->keep_bp = ctx->emit_bp_groups;
     if (!out->group_metrics) ctx->emit_group_metrics = 0;
-    if (bp_queueable) ctx->emit_bp_groups = 1;
+    if (bp_queueable || lab) ctx->emit_bp_groups = 1;
     t->later.h_tally = sl.h_tally, t->later.ev_unpacked = sl.ev_unpacked, t->later.ev_done = sl.ev_done;
     t->later.shared_spill = bp_queueable ? shared_spill : nullptr, t->later.shared_spill_count = bp_queueable ? shared_spill_count : nullptr;
     /* Packing on a stream of its own: its kernels stream the batch's arrays through HBM while the solver launches of the batch before are busy with their searches,
@@ -2775,6 +2921,13 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     ctx->up_stream = nullptr, ctx->up_side = nullptr;
     const double ts2 = now_ms();
     if (!rc) rc = avk_compare_resident(ctx, t->db, cfg, nullptr);
+    if (!rc && lab) { /* behind the solve's tally reduce: the label kernel, its sums cross with the results */
+        const size_t words = (size_t)lab->n_labels * AVK_TALLY_LEN;
+        rc = pool_alloc(ctx, &t->d_lab_out, words * sizeof(uint64_t));
+        if (!rc && hipMemsetAsync(t->d_lab_out, 0, words * sizeof(uint64_t), ctx->stream) != hipSuccess) rc = fail(ctx, AVK_E_HIP, "label sums: %s", hipGetErrorString(hipGetLastError()));
+        if (!rc) rc = labels_launch(ctx, t->db, pre.lab_off, pre.lab_idx, lab->n_labels, (uint64_t *)t->d_lab_out, ctx->stream);
+        t->later.lab_dev = t->d_lab_out, t->later.lab_host = sl.h_labels, t->later.lab_bytes = words * sizeof(uint64_t);
+    }
     const double ts3 = now_ms();
     if (!rc) rc = results_download_impl(ctx, t->db, out, &t->later, nullptr);
     if (timing)
@@ -2788,6 +2941,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamSynchronize(ctx->copy_out_stream);
         for (void *p : t->later.temps) pool_release(ctx, p);
+        if (t->d_lab_out) pool_release(ctx, t->d_lab_out);
         if (t->db) avk_batch_free(ctx, t->db);
         sl.busy = false;
         delete t;
@@ -2814,9 +2968,18 @@ int avk_wait(avk_ctx *ctx, avk_ticket *t) {
     if (!rc) { /* the tally, the statistics and — should a region have come back AVK_ST_CAPACITY — the retry, as in avk_results_download */
         const int64_t gm = ctx->emit_group_metrics;
         if (!t->out.group_metrics) ctx->emit_group_metrics = 0;
+        LabelFix lf{&t->lab, t->lab_out};
+        if (t->has_lab) ctx->label_fix = &lf; /* (a region the retry repairs was not solved when the label kernel ran) */
         rc = results_download_impl(ctx, t->db, &t->out, nullptr, sl.h_tally);
+        ctx->label_fix = nullptr;
         ctx->emit_group_metrics = gm;
+        if (!rc && t->has_lab) {
+            const size_t words = (size_t)t->lab.n_labels * AVK_TALLY_LEN;
+            for (size_t k = 0; k < words; ++k) t->lab_out[k] += sl.h_labels[k];
+            labels_timing_print(ctx, "submitted", t->lab.n_labels, t->db->n_regions, t->lab.label_off[t->db->n_regions]);
+        }
     }
+    if (t->d_lab_out) pool_release(ctx, t->d_lab_out);
     /* the batch's buffers go back to the pool: its work is over (the copies out ran behind its last kernel), so whoever is handed them next may use them at once */
     for (void *p : t->later.temps) pool_release(ctx, p);
     if (t->db) {
@@ -3357,6 +3520,104 @@ int avk_label_tallies(avk_ctx *ctx, avk_dev_batch *db, uint32_t n_labels, const 
     if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(e));
     for (size_t k = 0; k < host.size(); ++k) out[k] += host[k];
     return 0;
+}
+
+uint32_t avk_label_block(const avk_ctx *ctx) {
+    if (!ctx) return 0;
+    (void)hipSetDevice(ctx->device);
+    return label_block(const_cast<avk_ctx *>(ctx));
+}
+
+/* the label lists into pool buffers on the context's stream, the sums cleared */
+static int labels_upload(avk_ctx *ctx, uint64_t n, const avk_region_labels *lab, void **d_off, void **d_idx, void **d_out) {
+    const uint64_t n_idx = lab->label_off[n];
+    const size_t words = (size_t)lab->n_labels * AVK_TALLY_LEN;
+    int rc = pool_alloc(ctx, d_off, (n + 1) * 8);
+    if (!rc) rc = pool_alloc(ctx, d_idx, n_idx * 4);
+    if (!rc) rc = pool_alloc(ctx, d_out, words * 8);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(*d_off, lab->label_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && n_idx) e = hipMemcpyAsync(*d_idx, lab->label_idx, n_idx * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(*d_out, 0, words * 8, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "label lists: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int avk_label_tallies_compact(avk_ctx *ctx, avk_dev_batch *db, const avk_region_labels *lab, uint64_t *out) {
+    if (!ctx || !db || !lab) return AVK_E_ARG;
+    {
+        const int rl = labels_check(ctx, db->n_regions, lab, out);
+        if (rl) return rl;
+    }
+    if (lab->n_labels == 0) return 0;
+    if (!db->dev_packed) return fail(ctx, AVK_E_STATE, "label sums from the compact results need a device-packed batch: the option device_pack was 0 at its upload");
+    if (!db->has_run || db->last_mode != 0) return fail(ctx, AVK_E_STATE, "label sums from the compact results need a batch that avk_compare_resident has solved");
+    if (!db->bp_valid) return fail(ctx, AVK_E_STATE, "the batch has no BASEPAIR groups on the device: set emit_bp_groups before avk_compare_resident");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = db->n_regions;
+    const size_t words = (size_t)lab->n_labels * AVK_TALLY_LEN;
+    void *d_off = nullptr, *d_idx = nullptr, *d_out = nullptr;
+    std::vector<uint64_t> host(words, 0);
+    int rc = labels_upload(ctx, n, lab, &d_off, &d_idx, &d_out);
+    if (!rc) rc = labels_launch(ctx, db, (const uint64_t *)d_off, (const uint32_t *)d_idx, lab->n_labels, (uint64_t *)d_out, ctx->stream);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && e == hipSuccess) e = hipGetLastError();
+    pool_release(ctx, d_off), pool_release(ctx, d_idx), pool_release(ctx, d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(e));
+    labels_timing_print(ctx, "resident", lab->n_labels, n, lab->label_off[n]);
+    for (size_t k = 0; k < words; ++k) out[k] += host[k];
+    return 0;
+}
+
+int avk_compare_packed_labels(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_region_labels *lab, const avk_compare_config *cfg,
+                              avk_result_batch *out, uint64_t *label_tallies) {
+    if (!lab || lab->n_labels == 0) return avk_compare_packed_esc(ctx, batch, esc, cfg, out); /* the call without labels, launch for launch */
+    if (!batch) return AVK_E_ARG;
+    { /* (first of all: these refusals need no device, avk_last_error(NULL) has their text when ctx is NULL) */
+        const int rl = labels_check(ctx, batch->n_regions, lab, label_tallies);
+        if (rl) return rl;
+    }
+    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    ctx->last_one_shot = 0;
+    if (!esc_present(esc)) esc = nullptr;
+    const uint64_t n = batch->n_regions;
+    const size_t words = (size_t)lab->n_labels * AVK_TALLY_LEN;
+    avk_dev_batch *db = nullptr;
+    const int64_t keep_gm = ctx->emit_group_metrics, keep_bp = ctx->emit_bp_groups;
+    if (!out->group_metrics) ctx->emit_group_metrics = 0;
+    ctx->emit_bp_groups = 1; /* the groups are what the label kernel reads, whether the caller asked for them or not */
+    void *d_off = nullptr, *d_idx = nullptr, *d_out = nullptr;
+    std::vector<uint64_t> host(words, 0);
+    int rc = avk_batch_upload_packed_esc(ctx, batch, esc, &db);
+    if (!rc) rc = labels_upload(ctx, n, lab, &d_off, &d_idx, &d_out);
+    if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
+    if (!rc) rc = labels_launch(ctx, db, (const uint64_t *)d_off, (const uint32_t *)d_idx, lab->n_labels, (uint64_t *)d_out, ctx->stream);
+    if (!rc && hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc) { /* (the download waits for the stream; a region its capacity retry repairs is added on the host: it was not solved when the label kernel ran) */
+        LabelFix lf{lab, label_tallies};
+        ctx->label_fix = &lf;
+        rc = avk_results_download(ctx, db, out);
+        ctx->label_fix = nullptr;
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->emit_group_metrics = keep_gm, ctx->emit_bp_groups = keep_bp;
+    pool_release(ctx, d_off), pool_release(ctx, d_idx), pool_release(ctx, d_out);
+    if (db) {
+        ctx->last_one_shot = 1;
+        avk_batch_free(ctx, db);
+    }
+    if (rc) return rc;
+    labels_timing_print(ctx, "one call", lab->n_labels, n, lab->label_off[n]);
+    for (size_t k = 0; k < words; ++k) label_tallies[k] += host[k];
+    return 0;
+}
+
+int avk_compare_packed_submit_labels(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_region_labels *lab, const avk_compare_config *cfg,
+                                     avk_result_batch *out, uint64_t *label_tallies, avk_ticket **ticket) {
+    return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr, esc, lab, label_tallies);
 }
 
 /* solve_merge_region's pairwise test (merge_solver.rs:128-147) for every region of the batch: the "truth"

@@ -162,6 +162,22 @@ int avk_packed_shard_scatter(const avk_packed_shard *s, const avk_result_batch *
 
 void avk_packed_shard_free(avk_packed_shard *s) { delete s; }
 
+/* the whole job's label lists for the shard's regions, in shard order (host only; shard_idx == NULL: the offsets alone, to size the index array) */
+int avk_packed_shard_labels(const avk_packed_shard *s, const avk_region_labels *whole, uint64_t *shard_off, uint32_t *shard_idx) {
+    if (!s || !whole || !whole->label_off || !shard_off) return AVK_E_ARG;
+    const uint64_t m = s->index.size();
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < m; ++k) {
+        const uint64_t r = s->index[k], lo = whole->label_off[r], hi = whole->label_off[r + 1];
+        if (hi < lo || (hi > lo && shard_idx && !whole->label_idx)) return AVK_E_ARG;
+        shard_off[k] = at;
+        if (shard_idx && hi > lo) memcpy(shard_idx + at, whole->label_idx + lo, (hi - lo) * sizeof(uint32_t));
+        at += hi - lo;
+    }
+    shard_off[m] = at;
+    return AVK_E_OK;
+}
+
 /* ---- merge (solve_merge_region): regions are mapped like compare regions (src/main.rs:463-478), so a packed multi-region batch is cut by the same rule ---- */
 
 int avk_packed_multi_shard_make(const avk_packed_multi_batch *whole, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world,

@@ -300,6 +300,18 @@ int main(int argc, char **argv) {
         avk_result_batch shifted = out_for(out, v_first);
         return avk_compare_packed_esc(c, &part, &part_esc, &cfg, &shifted);
     };
+    /* the same with the stratified sums: the labels' sums come from the batch's compact results on the device (avk_compare_packed_labels), no metric blocks */
+    auto compare_part_labels = [&](avk_ctx *c, uint64_t at_abs, uint64_t n, const avk_compare_config &cfg, const avk_result_batch &out, uint32_t n_lab, const uint64_t *label_off,
+                                   const uint32_t *label_idx, uint64_t *sums) -> int {
+        avk_packed_batch part;
+        avk_packed_escapes part_esc;
+        uint64_t v_first = 0;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, &v_first)) return AVK_E_ARG;
+        avk_result_batch shifted = out_for(out, v_first);
+        avk_region_labels lab;
+        lab.n_labels = n_lab, lab.label_off = label_off, lab.label_idx = label_idx;
+        return avk_compare_packed_labels(c, &part, &part_esc, &lab, &cfg, &shifted, sums);
+    };
     auto upload_part = [&](avk_ctx *c, const avk_region_batch &b, uint64_t at_abs, uint64_t n, avk_dev_batch **db, uint64_t *v_first) -> int {
         *v_first = 0;
         if (!packed) return avk_batch_upload(c, &b, db);
@@ -325,10 +337,16 @@ int main(int argc, char **argv) {
     /* stratified tallies (SummaryWriter::add_comparison_benchmark, summary.rs:146-163): label l sums the metric blocks of the
      * regions it contains, so the per-region blocks come back from the GPU, in batches that keep them at a few hundred MB */
     const bool debug = !debug_dir.empty();
-    (void)avk_ctx_set_option(ctx, "emit_group_metrics", n_labels || debug ? 1 : 0);
-    /* the per-region blocks only come back to the host for the debug tables; the stratified tallies are summed on the GPU
-     * (avk_label_tallies) from the region labels the feeder library lists (avf_strat_batch_labels) */
+    /* the per-region blocks only come back to the host for the debug tables; the stratified tallies are summed on the GPU from the region labels the feeder
+     * library lists (avf_strat_batch_labels): on the packed feed from the batch's compact results (avk_compare_packed_labels: no per-region blocks at all), on the
+     * wide feed from per-region blocks that stay on the device (avk_label_tallies) */
     const bool device_labels = n_labels && !debug;
+    const bool compact_labels = device_labels && packed;
+    (void)avk_ctx_set_option(ctx, "emit_group_metrics", (n_labels && !compact_labels) || debug ? 1 : 0);
+    if (verbosity && n_labels)
+        fprintf(stderr, "Stratified sums: %s.\n", compact_labels ? "from the compact results on the GPU (avk_compare_packed_labels), no per-region metric blocks"
+                                                     : device_labels ? "from per-region metric blocks on the GPU (avk_label_tallies)"
+                                                                     : "from the per-region metric blocks of the debug tables, on the host");
     if (debug && batch_regions > 262144) batch_regions = 262144;
     cfg.enable_sequences = debug ? 1 : 0; /* enable_sequences(region_seq_writer.is_some()), src/main.rs:236 */
     uint32_t mask = AVF_METRIC_GT | AVF_METRIC_BASEPAIR;
@@ -503,7 +521,7 @@ int main(int argc, char **argv) {
                     avk_ctx_destroy(my);
                     return;
                 }
-                (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels ? 1 : 0);
+                (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels && !compact_labels ? 1 : 0);
             }
             std::vector<uint64_t> w_tally(AVK_TALLY_LEN);
             for (uint64_t bi = next_batch.fetch_add(1); bi < n_batches; bi = next_batch.fetch_add(1)) {
@@ -539,14 +557,17 @@ int main(int argc, char **argv) {
                         worker_err[w] = std::string("cannot list the region labels: ") + avf_last_error();
                         break;
                     }
-                    avk_dev_batch *db = nullptr;
-                    uint64_t v_first = 0;
-                    rc = upload_part(my, b, first + at, n, &db, &v_first);
-                    if (!rc) rc = avk_compare_resident(my, db, &cfg, nullptr);
-                    avk_result_batch shifted = out_for(out, v_first);
-                    if (!rc) rc = avk_results_download(my, db, &shifted);
-                    if (!rc) rc = avk_label_tallies(my, db, n_labels, label_off.data(), label_idx.data(), w_strat[w].data());
-                    if (db) avk_batch_free(my, db);
+                    if (compact_labels) rc = compare_part_labels(my, first + at, n, cfg, out, n_labels, label_off.data(), label_idx.data(), w_strat[w].data());
+                    else {
+                        avk_dev_batch *db = nullptr;
+                        uint64_t v_first = 0;
+                        rc = upload_part(my, b, first + at, n, &db, &v_first);
+                        if (!rc) rc = avk_compare_resident(my, db, &cfg, nullptr);
+                        avk_result_batch shifted = out_for(out, v_first);
+                        if (!rc) rc = avk_results_download(my, db, &shifted);
+                        if (!rc) rc = avk_label_tallies(my, db, n_labels, label_off.data(), label_idx.data(), w_strat[w].data());
+                        if (db) avk_batch_free(my, db);
+                    }
                 } else rc = compare_part(my, b, first + at, n, cfg, out);
                 if (rc) {
                     worker_err[w] = std::string("compare failed: ") + avk_last_error(my);
@@ -611,7 +632,17 @@ int main(int argc, char **argv) {
             out.seq_stride = seq_stride.data();
             out.seq_len = seq_len.data();
         }
-        if (device_labels) {
+        if (compact_labels) { /* one call: the lists go in with the batch, the sums come back with the results */
+            std::vector<uint64_t> label_off(n + 1, 0);
+            std::vector<uint32_t> label_idx;
+            int rc_labels = avf_strat_batch_labels(strat, genome, all, first + at, n, label_off.data(), nullptr);
+            if (!rc_labels) {
+                label_idx.resize(label_off[n] + 1);
+                rc_labels = avf_strat_batch_labels(strat, genome, all, first + at, n, label_off.data(), label_idx.data());
+            }
+            if (rc_labels) die(70, "cannot list the region labels", avf_last_error());
+            if (compare_part_labels(ctx, first + at, n, cfg, out, n_labels, label_off.data(), label_idx.data(), strat_total.data())) die(70, "compare failed", avk_last_error(ctx));
+        } else if (device_labels) {
             std::vector<uint64_t> label_off(n + 1, 0);
             std::vector<uint32_t> label_idx;
             int rc_labels = 0;

@@ -62,6 +62,27 @@ def shard_batch(batch, rank, world):
     return take_regions(batch, shard_indices(batch.region_id, rank, world))
 
 
+def shard_labels(lib, shard, n_labels, label_off, label_idx):
+    """avk_packed_shard_labels: the whole job's label lists (n_labels, label_off, label_idx) gathered for the regions of a packed shard (the handle
+    avk_packed_shard_make returned), in shard order -> (n_labels, shard_off, shard_idx): the labels= argument of the shard's solve_packed / submit_packed.
+    The ranks' [n_labels, TALLY_LEN] sums add up to the job's (allreduce_counts)."""
+    import ctypes as C
+    from ._abi import region_labels
+    lab, _keep = region_labels(n_labels, label_off, label_idx)
+    lib.avk_packed_shard_regions.restype = C.c_uint64
+    lib.avk_packed_shard_regions.argtypes = [C.c_void_p, C.c_void_p]
+    m = int(lib.avk_packed_shard_regions(shard, None))
+    off = np.zeros(m + 1, np.uint64)
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    lib.avk_packed_shard_labels.argtypes = [C.c_void_p, C.c_void_p, u64p, u32p]
+    if lib.avk_packed_shard_labels(shard, C.byref(lab), off.ctypes.data_as(u64p), None) != 0:
+        raise ValueError("avk_packed_shard_labels: the label lists do not fit the shard's job")
+    idx = np.zeros(max(int(off[m]), 1), np.uint32)
+    if lib.avk_packed_shard_labels(shard, C.byref(lab), off.ctypes.data_as(u64p), idx.ctypes.data_as(u32p)) != 0:
+        raise ValueError("avk_packed_shard_labels: the label lists do not fit the shard's job")
+    return n_labels, off, idx[:int(off[m])]
+
+
 def result_checksum(batch, res):
     """An order-independent 64-bit checksum of every per-region and per-variant output of `res` for the regions of `batch`: the sum, modulo
     2^64, of a hash per region (region_id, status, ed_h1, ed_h2, optima, types) and a hash per variant (region_id, index in the region,

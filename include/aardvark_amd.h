@@ -509,6 +509,32 @@ int  avk_debug_work_order(avk_ctx *ctx, avk_dev_batch *db, uint32_t *order, uint
  * ADDED to out[n_labels * AVK_TALLY_LEN] (a job sums over its batches); the per-region blocks never leave the GPU. */
 int  avk_label_tallies(avk_ctx *ctx, avk_dev_batch *db, uint32_t n_labels, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *out);
 
+/* The same sums WITHOUT per-region metric blocks (avk_labels.inl): a kernel rebuilds each solved region's block from what a run leaves on the device anyway — status,
+ * expected / observed per call, the calls as the caller sent them, Variant::alt_ed and the compact BASEPAIR groups (the rule of avk_group_metrics_from_compact) —
+ * and adds it straight into the sums of the region's labels.  emit_group_metrics may be 0; the run must write the BASEPAIR groups.  Semantics are those of
+ * avk_label_tallies: sums are ADDED to out[n_labels * AVK_TALLY_LEN], a label named twice in a list counts twice, words AVK_TALLY_SOLVED / AVK_TALLY_ERRORS of a
+ * label's block are not touched.  A launch holds the sums of avk_label_block(ctx) labels in LDS; more labels are more passes over the regions. */
+typedef struct avk_region_labels {
+    uint32_t n_labels;
+    const uint64_t *label_off; /* [n_regions + 1], not decreasing */
+    const uint32_t *label_idx; /* [label_off[n_regions]] each < n_labels (may be NULL when no region has a label) */
+} avk_region_labels;
+uint32_t avk_label_block(const avk_ctx *ctx);
+/* resident form: a device-packed batch (option device_pack, the default) after avk_compare_resident with the option emit_bp_groups set; otherwise AVK_E_STATE.
+ * Called after avk_results_download it also counts the regions the capacity retry repaired. */
+int  avk_label_tallies_compact(avk_ctx *ctx, avk_dev_batch *db, const avk_region_labels *labels, uint64_t *out);
+/* one-call forms: avk_compare_packed_esc / avk_compare_packed_submit_esc that also return the labels' sums (ADDED to label_tallies[n_labels * AVK_TALLY_LEN]; the
+ * submit form adds them in avk_wait, until which `labels`' arrays and label_tallies belong to the library).  The library switches the BASEPAIR groups on itself;
+ * regions the capacity retry repairs are counted.  labels == NULL or n_labels == 0: exactly the call without labels.  AVK_E_ARG, before anything is queued: a
+ * decreasing label_off, an index >= n_labels, label_off[n_regions] != 0 with a NULL label_idx, a NULL label_tallies. */
+int  avk_compare_packed_labels(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_region_labels *labels, const avk_compare_config *cfg,
+                               avk_result_batch *out, uint64_t *label_tallies);
+int  avk_compare_packed_submit_labels(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_region_labels *labels,
+                                      const avk_compare_config *cfg, avk_result_batch *out, uint64_t *label_tallies, avk_ticket **ticket);
+/* host only: the label lists of a shard's regions gathered from the whole job's, in shard order (avk_packed_shard_regions' index_in_whole).  shard_off gets
+ * regions + 1 offsets; shard_idx (NULL: offsets only, to size it) the indices.  Per-rank sums add up over the ranks (avk_counts_allreduce). */
+int  avk_packed_shard_labels(const avk_packed_shard *s, const avk_region_labels *whole, uint64_t *shard_off, uint32_t *shard_idx);
+
 /* Merge path (src/merge_solver.rs:137-143): for pair p, optimize_sequences(set a, set b) and
  * report all_opt_haps[0].is_exact_match().  Pair p compares variant ranges
  * [t_off,t_cnt) vs [q_off,q_cnt) of region p of `batch` exactly like a CompareRegion. */
