@@ -7,8 +7,8 @@ outputs (CompareBenchmark fields), same per-region error behaviour (a failed reg
 status instead of metrics and the batch continues, src/main.rs:255-265).
 """
 import ctypes as C
-import weakref
 import os
+import weakref
 
 import numpy as np
 
@@ -76,6 +76,15 @@ def load_library():
         lib.avk_compare_packed_labels.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, lab, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p]
         lib.avk_compare_packed_submit_labels.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, lab, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p, C.POINTER(vp)]
         lib.avk_packed_shard_labels.argtypes = [vp, lab, u64p, C.POINTER(C.c_uint32)]
+    if hasattr(lib, "avk_strata_upload"):  # stratification sets resident on the device, lists by kernel (avk_strata.inl)
+        lib.avk_strata_upload.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(vp)]
+        lib.avk_strata_free.argtypes = [vp, vp]
+        lib.avk_strata_free.restype = None
+        lib.avk_strata_n_labels.restype = C.c_uint32
+        lib.avk_strata_n_labels.argtypes = [vp]
+        lib.avk_strata_region_labels.argtypes = [vp, vp, vp, u64p, C.POINTER(C.c_uint32), C.c_uint64]
+        lib.avk_label_tallies_strata.argtypes = [vp, vp, vp, u64p]
+        lib.avk_compare_packed_strata.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, vp, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p]
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
     lib.avk_results_download.argtypes = [vp, vp, C.POINTER(AvkResultBatch)]
     lib.avk_batch_free.argtypes = [vp, vp]
@@ -131,12 +140,45 @@ class ResidentBatch:
             else:
                 ctx._check(ctx.lib.avk_batch_upload_packed_esc(ctx.handle, C.byref(cb), C.byref(esc), C.byref(self.handle)))
             return
+        if isinstance(batch, CompactBatch):
+            ctx._check(ctx.lib.avk_batch_upload_compact(ctx.handle, C.byref(cb), C.byref(self.handle)))
+            return
         ctx._check(ctx.lib.avk_batch_upload(ctx.handle, C.byref(cb), C.byref(self.handle)))
 
     def free(self):
         if self.handle:
             self.ctx.lib.avk_batch_free(self.ctx.handle, self.handle)
             self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Strata:
+    """The interval sets of a stratified job resident in HBM (avk_strata): uploaded once per context, then handed to solve_packed(strata=..),
+    label_tallies_strata and strata_region_labels in place of label lists."""
+
+    def __init__(self, ctx, n_labels, n_contigs, tree_off, start, end_max):
+        self.ctx = ctx
+        self.handle = C.c_void_p()
+        tree_off = np.ascontiguousarray(tree_off, np.uint64)
+        start, end_max = np.ascontiguousarray(start, np.uint32), np.ascontiguousarray(end_max, np.uint32)
+        if len(tree_off) != int(n_labels) * int(n_contigs) + 1 or len(start) != len(end_max) or (len(tree_off) and int(tree_off[-1]) > len(start)):
+            raise ValueError("strata arrays do not fit n_labels * n_contigs trees")
+        u32p = C.POINTER(C.c_uint32)
+        ctx._check(ctx.lib.avk_strata_upload(ctx.handle, int(n_labels), int(n_contigs), tree_off.ctypes.data_as(u64p), start.ctypes.data_as(u32p) if len(start) else None,
+                                             end_max.ctypes.data_as(u32p) if len(end_max) else None, C.byref(self.handle)))
+        self.n_labels = int(ctx.lib.avk_strata_n_labels(self.handle))
+        self.n_intervals = int(tree_off[-1]) - int(tree_off[0])
+        ctx.__dict__.setdefault("_strata", weakref.WeakSet()).add(self)  # (Context.close frees the handles it still has: a handle must not outlive its context)
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.avk_strata_free(self.ctx.handle, self.handle)
+        self.handle = C.c_void_p()
 
     def __del__(self):
         try:
@@ -195,10 +237,13 @@ class Context:
             raise AardvarkAmdError("avk_ctx_create(%d) failed (%d): %s" % (device, rc, self.lib.avk_last_error(None).decode()))
         self._contigs = None
         self._core = _ContextCore(self.lib, self.handle)
+        self._strata = weakref.WeakSet()  # Strata handles of this context
 
     def close(self):
         """No call may follow.  The native context goes at once, or — when arrays of host_array / pinned_* are still referenced — with the last of them."""
         if self.handle:
+            for s in list(getattr(self, "_strata", ())):
+                s.free()
             self._core.close()
             self.handle = C.c_void_p()
 
@@ -245,13 +290,22 @@ class Context:
         esc = None if pbatch.escapes is None else pbatch.escapes.pinned(self.host_array)
         return PackedBatch(escapes=esc, **{f: pin(getattr(pbatch, f)) for f in PackedBatch.FIELDS})
 
-    def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None):
+    def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None, strata=None):
         """avk_compare_packed: solve_compare_region for every region of a batch in the packed form -> ResultBatch (indexed like the packed arrays).
         labels=(n_labels, label_off, label_idx): avk_compare_packed_labels — the per-label sums come back as res.label_tallies, a [n_labels, TALLY_LEN] uint64
-        array (label_tallies: an array of that shape the sums are added to instead)"""
+        array (label_tallies: an array of that shape the sums are added to instead).
+        strata=a Strata handle (upload_strata): avk_compare_packed_strata — the same sums, the lists made on the device"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
         pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
+        if strata is not None:
+            if labels is not None:
+                raise ValueError("labels and strata exclude each other")
+            sums = np.zeros((strata.n_labels, TALLY_LEN), np.uint64) if label_tallies is None else label_tallies
+            self._check(self.lib.avk_compare_packed_strata(self.handle, C.byref(pb), None if esc is None else C.byref(esc), strata.handle, C.byref(cfg), C.byref(ro),
+                                                           sums.ctypes.data_as(u64p)))
+            res.label_tallies = sums
+            return res
         if labels is not None:
             lab, _keep = region_labels(*labels)
             sums = np.zeros((int(labels[0]), TALLY_LEN), np.uint64) if label_tallies is None else label_tallies
@@ -348,7 +402,7 @@ class Context:
 
     # --- resident form (benchmarks, pipelines that keep batches in HBM)
     def upload(self, batch):
-        """a RegionBatch, or a PackedBatch (with its escapes) -> ResidentBatch"""
+        """a RegionBatch, a CompactBatch, or a PackedBatch (with its escapes) -> ResidentBatch"""
         return ResidentBatch(self, batch)
 
     def compare_resident(self, rb, config=None, tally_dev_ptr=None):
@@ -385,6 +439,24 @@ class Context:
         out = np.zeros((n_labels, TALLY_LEN), np.uint64) if out is None else out
         lab, _keep = region_labels(n_labels, label_off, label_idx)
         self._check(self.lib.avk_label_tallies_compact(self.handle, rb.handle, C.byref(lab), out.ctypes.data_as(u64p)))
+        return out
+
+    def upload_strata(self, n_labels, n_contigs, tree_off, start, end_max):
+        """avk_strata_upload: the interval sets of a stratified job (Stratifications.export(genome) of the feeder) into HBM, once -> Strata"""
+        return Strata(self, n_labels, n_contigs, tree_off, start, end_max)
+
+    def strata_region_labels(self, rb, strata):
+        """avk_strata_region_labels: the containment lists of a resident batch, made on the device -> (label_off[n + 1], label_idx)"""
+        off = np.zeros(rb.batch.n_regions + 1, np.uint64)
+        self._check(self.lib.avk_strata_region_labels(self.handle, rb.handle, strata.handle, off.ctypes.data_as(u64p), None, 0))
+        idx = np.zeros(max(int(off[-1]), 1), np.uint32)
+        self._check(self.lib.avk_strata_region_labels(self.handle, rb.handle, strata.handle, off.ctypes.data_as(u64p), idx.ctypes.data_as(C.POINTER(C.c_uint32)), int(off[-1])))
+        return off, idx[:int(off[-1])]
+
+    def label_tallies_strata(self, rb, strata, out=None):
+        """avk_label_tallies_strata: label_tallies_compact with the lists made on the device from the resident sets; returns / adds to [n_labels, TALLY_LEN]"""
+        out = np.zeros((strata.n_labels, TALLY_LEN), np.uint64) if out is None else out
+        self._check(self.lib.avk_label_tallies_strata(self.handle, rb.handle, strata.handle, out.ctypes.data_as(u64p)))
         return out
 
     def synchronize(self):

@@ -863,6 +863,39 @@ static void release_pooled(avk_ctx *ctx, avk_dev_batch *db) {
 
 /* the arrays of an avk_packed_batch already in device memory (a staging slot of avk_compare_packed_submit, filled on the context's copy stream): nothing is copied,
  * the context's stream waits for `ready`; the block stays with the caller (the allele bytes and raw spaces are read until the batch's solve is over) */
+/* ---- the containment lists of a stratified batch, made on the device (avk_strata.inl) ------------------------------------------------------------------ */
+static avk::sx::SxTrees strata_trees(const avk_strata *st) {
+    avk::sx::SxTrees t;
+    t.tree_off = st->d_tree_off, t.start = st->d_start, t.end_max = st->d_end_max, t.n_labels = st->n_labels, t.n_contigs = st->n_contigs;
+    return t;
+}
+static inline uint32_t strata_words(const avk_strata *st) { return (st->n_labels + 31u) / 32u; }
+static inline uint32_t strata_blocks(uint64_t n) { return (uint32_t)((n + 255) / 256); }
+/* pass 1 and the scan of its workgroup sums: d_mask[strata_words * n], d_sums[strata_blocks(n) + 1] — the workgroups' bases, then the number of list entries */
+static hipError_t strata_count_launch(const avk_strata *st, const dpk::DpIn &in, uint64_t n, uint32_t *d_mask, uint64_t *d_sums, hipStream_t s) {
+    if (!n) return hipSuccess;
+    const uint32_t nb = strata_blocks(n);
+    hipLaunchKernelGGL(avk_strata_mask_kernel, dim3(nb), dim3(256), 0, s, in, strata_trees(st), (uint32_t)n, d_mask, (unsigned long long *)d_sums);
+    hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, s, d_sums, nb, d_sums + nb);
+    return hipGetLastError();
+}
+/* pass 2: the offsets, and with d_idx the indices (idx_cap entries of room) */
+static hipError_t strata_fill_launch(const avk_strata *st, uint64_t n, const uint32_t *d_mask, const uint64_t *d_sums, uint64_t *d_off, uint32_t *d_idx, uint64_t idx_cap, hipStream_t s) {
+    if (!n) return hipMemsetAsync(d_off, 0, 8, s);
+    hipLaunchKernelGGL(avk_strata_fill_kernel, dim3(strata_blocks(n)), dim3(256), 0, s, d_mask, (uint32_t)n, strata_words(st), (const unsigned long long *)d_sums, (unsigned long long *)d_off,
+                       d_idx, (unsigned long long)idx_cap);
+    return hipGetLastError();
+}
+/* avk_compare_packed_strata: pass 1 rides behind the packer's region passes, and the number of list entries comes back with the packer's state block — the
+ * call's one round trip — so the index array is sized without a round trip of its own */
+struct StrataJob {
+    const avk_strata *st;
+    uint32_t *d_mask;
+    uint64_t *d_sums;
+    uint64_t total = 0;
+    bool counted = false;
+};
+
 struct PackedOnDevice {
     uint8_t *t_cnt, *q_cnt, *a0_len, *a1_len, *var_type_zyg, *alleles;
     uint32_t *start, *raw;
@@ -1341,10 +1374,14 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             hipLaunchKernelGGL(avk_dp_scatter_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, s, a);
             x = hipGetLastError();
         }
+        StrataJob *sj = n && ctx->strata_job && !ctx->strata_job->counted ? ctx->strata_job : nullptr; /* (once: the lists do not depend on alt_ed, a second round of the passes leaves them) */
+        if (x == hipSuccess && sj) x = strata_count_launch(sj->st, a.in, n, sj->d_mask, sj->d_sums, s);
         mark(2);
         if (x == hipSuccess) x = hipMemcpyAsync(hs, a.st, sizeof(dpk::DpState), hipMemcpyDeviceToHost, s);
         if (x == hipSuccess && pk_totals) x = hipMemcpyAsync(hs + 1, pk_totals, has_esc ? 24 : 16, hipMemcpyDeviceToHost, s); /* (the packed forms' two sums ride along: 16 bytes behind the state block) */
+        if (x == hipSuccess && sj) x = hipMemcpyAsync((uint8_t *)(hs + 1) + 24, sj->d_sums + strata_blocks(n), 8, hipMemcpyDeviceToHost, s); /* (and the lists' size behind those) */
         if (x == hipSuccess) x = hipStreamSynchronize(s);
+        if (x == hipSuccess && sj) memcpy(&sj->total, (const uint8_t *)(hs + 1) + 24, 8), sj->counted = true;
         if (x == hipSuccess) engine_rate_check(ctx);
         return x;
     };

@@ -36,6 +36,7 @@
 #include "avk_dwfa_script.inl"
 #include "avk_devpack.inl"
 #include "avk_labels.inl"
+#include "avk_strata.inl"
 
 /* ---------------------------------------------------------------------------------- kernels */
 /* LDS passes: regions in the LDS slice of their wavefront (small slices at high occupancy first, then
@@ -365,6 +366,7 @@ struct avk_ctx {
     } stage[4];
     hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr; /* AVK_TIMING: around the label kernels */
     int64_t label_lds_bytes = 0;       /* LDS a launch of avk_label_tally_compact_kernel gets (0: not asked yet) */
+    struct StrataJob *strata_job = nullptr; /* set while avk_compare_packed_strata uploads its batch: the packer's region passes also count the batch's containment lists (avk_strata.inl) */
     struct LabelFix *label_fix = nullptr; /* set while a one-call form with labels downloads: the capacity retry adds the repaired regions' blocks to the labels' sums */
     /* options */
     int64_t lds_bytes_per_wave = 10 * 1024;
@@ -539,6 +541,15 @@ struct avk_dev_batch {
     int64_t big_bytes_eff = 0;            /* shared big slices of this batch's launches when the packer predicts regions beyond the largest bucket (0: the option big_ws_bytes) */
     int64_t ws_bytes_eff = 0;             /* per-wave HBM slice of this batch's launches when the packer's prediction asks for more than the option ws_bytes_per_wave (0: the option) */
     bool records_full = false; /* every region has its AvkDevRegion + blob (false: only the regions outside the lane classes, until a launch asks for more) */
+};
+
+/* the interval sets of a stratified job, resident in HBM (avk_strata_upload; the layout of avk_strata.inl) */
+struct avk_strata {
+    avk_ctx *ctx = nullptr;
+    uint32_t n_labels = 0, n_contigs = 0;
+    uint64_t n_intervals = 0;
+    uint64_t *d_tree_off = nullptr;
+    uint32_t *d_start = nullptr, *d_end_max = nullptr;
 };
 
 namespace {
@@ -2397,10 +2408,33 @@ static int rerun_capacity_regions(avk_ctx *ctx, avk_dev_batch *db, const std::ve
 /* a one-call form with labels (avk_compare_packed_labels, avk_wait of a submit with labels): its label kernel ran before the capacity retry, so the blocks of the
  * regions the retry repairs are added to the labels' sums here, on the host */
 struct LabelFix {
-    const avk_region_labels *lab;
+    const avk_region_labels *lab; /* NULL: the lists were made on the device (avk_compare_packed_strata) and a repaired region's few entries are fetched from there */
     uint64_t *out; /* [n_labels * AVK_TALLY_LEN] */
+    const uint64_t *d_off = nullptr;
+    const uint32_t *d_idx = nullptr;
+    uint64_t n = 0;               /* regions of the batch */
+    std::vector<uint64_t> h_off;  /* the device lists' offsets, fetched once, at the first repaired region */
+    hipError_t err = hipSuccess;  /* a failed fetch: the call that set the fix up fails with it */
 };
 static void label_fix_add(LabelFix *lf, uint64_t r, const uint32_t *block) {
+    if (!lf->lab) { /* (the list kernels finished before the solve whose results the retry has just read) */
+        if (lf->err != hipSuccess) return;
+        if (lf->h_off.empty()) {
+            lf->h_off.resize((size_t)lf->n + 1);
+            lf->err = hipMemcpy(lf->h_off.data(), lf->d_off, (size_t)(lf->n + 1) * 8, hipMemcpyDeviceToHost);
+            if (lf->err != hipSuccess) return;
+        }
+        const uint64_t be[2] = {lf->h_off[r], lf->h_off[r + 1]};
+        if (be[1] <= be[0]) return;
+        std::vector<uint32_t> idx((size_t)(be[1] - be[0]));
+        lf->err = hipMemcpy(idx.data(), lf->d_idx + be[0], idx.size() * 4, hipMemcpyDeviceToHost);
+        if (lf->err != hipSuccess) return;
+        for (const uint32_t l : idx) {
+            uint64_t *dst = lf->out + (size_t)l * AVK_TALLY_LEN;
+            for (int i = 0; i < AVK_N_GROUPS * AVK_N_FIELDS; ++i) dst[i] += block[i];
+        }
+        return;
+    }
     for (uint64_t q = lf->lab->label_off[r]; q < lf->lab->label_off[r + 1]; ++q) {
         uint64_t *dst = lf->out + (size_t)lf->lab->label_idx[q] * AVK_TALLY_LEN;
         for (int i = 0; i < AVK_N_GROUPS * AVK_N_FIELDS; ++i) dst[i] += block[i];
@@ -3618,6 +3652,213 @@ int avk_compare_packed_labels(avk_ctx *ctx, const avk_packed_batch *batch, const
 int avk_compare_packed_submit_labels(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_region_labels *lab, const avk_compare_config *cfg,
                                      avk_result_batch *out, uint64_t *label_tallies, avk_ticket **ticket) {
     return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr, esc, lab, label_tallies);
+}
+
+/* ---- stratification sets resident on the device, containment lists by kernel (avk_strata.inl) ------------------------------------------------------ */
+/* the refusals of avk_strata_upload, before any allocation (no device involved: with ctx == NULL the text is avk_last_error(NULL)'s) */
+static int strata_check(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs, const uint64_t *tree_off, const uint32_t *start, const uint32_t *end_max) {
+    const uint64_t n_trees = (uint64_t)n_labels * n_contigs;
+    if (n_trees && !tree_off) return fail(ctx, AVK_E_ARG, "strata: tree_off missing");
+    if (!n_trees) return 0;
+    for (uint64_t k = 0; k < n_trees; ++k)
+        if (tree_off[k + 1] < tree_off[k]) return fail(ctx, AVK_E_ARG, "strata: tree_off must not decrease (tree %llu)", (unsigned long long)k);
+    const uint64_t total = tree_off[n_trees];
+    if (total && (!start || !end_max)) return fail(ctx, AVK_E_ARG, "strata: start / end_max missing: tree_off names %llu intervals", (unsigned long long)total);
+    for (uint64_t k = 0; k < n_trees; ++k)
+        for (uint64_t i = tree_off[k] + 1; i < tree_off[k + 1]; ++i) {
+            if (start[i] < start[i - 1]) return fail(ctx, AVK_E_ARG, "strata: the starts of tree %llu are not sorted", (unsigned long long)k);
+            if (end_max[i] < end_max[i - 1]) return fail(ctx, AVK_E_ARG, "strata: end_max of tree %llu decreases", (unsigned long long)k);
+        }
+    return 0;
+}
+
+int avk_strata_upload(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs, const uint64_t *tree_off, const uint32_t *start, const uint32_t *end_max, avk_strata **out) {
+    if (!out) return fail(ctx, AVK_E_ARG, "strata: out missing");
+    *out = nullptr;
+    {
+        const int rc = strata_check(ctx, n_labels, n_contigs, tree_off, start, end_max);
+        if (rc) return rc;
+    }
+    if (!ctx) return fail(ctx, AVK_E_ARG, "strata: context missing");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n_trees = (uint64_t)n_labels * n_contigs, first = n_trees ? tree_off[0] : 0, total = n_trees ? tree_off[n_trees] : 0;
+    avk_strata *st = new avk_strata();
+    st->ctx = ctx, st->n_labels = n_labels, st->n_contigs = n_contigs, st->n_intervals = total - first;
+    int rc = dev_alloc(ctx, &st->d_tree_off, (size_t)n_trees + 1);
+    if (!rc) rc = dev_alloc(ctx, &st->d_start, (size_t)total);
+    if (!rc) rc = dev_alloc(ctx, &st->d_end_max, (size_t)total);
+    hipError_t e = hipSuccess;
+    if (!rc && n_trees) e = hipMemcpy(st->d_tree_off, tree_off, (size_t)(n_trees + 1) * 8, hipMemcpyHostToDevice);
+    if (!rc && !n_trees) e = hipMemset(st->d_tree_off, 0, 8);
+    if (!rc && e == hipSuccess && total) e = hipMemcpy(st->d_start, start, (size_t)total * 4, hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess && total) e = hipMemcpy(st->d_end_max, end_max, (size_t)total * 4, hipMemcpyHostToDevice);
+    if (!rc && e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata upload failed: %s", hipGetErrorString(e));
+    if (rc) {
+        avk_strata_free(ctx, st);
+        return rc;
+    }
+    *out = st;
+    return 0;
+}
+void avk_strata_free(avk_ctx *ctx, avk_strata *st) {
+    if (!st) return;
+    if (ctx) (void)hipSetDevice(ctx->device);
+    if (st->d_tree_off) (void)hipFree(st->d_tree_off);
+    if (st->d_start) (void)hipFree(st->d_start);
+    if (st->d_end_max) (void)hipFree(st->d_end_max);
+    delete st;
+}
+uint32_t avk_strata_n_labels(const avk_strata *st) { return st ? st->n_labels : 0; }
+
+/* the lists of a resident batch in pool buffers, on the context's stream; the number of entries is read back (the resident forms size the index array with it) */
+struct StrataLists {
+    void *d_mask = nullptr, *d_sums = nullptr, *d_off = nullptr, *d_idx = nullptr;
+    uint64_t total = 0;
+};
+static void strata_lists_release(avk_ctx *ctx, StrataLists &L) {
+    pool_release(ctx, L.d_mask), pool_release(ctx, L.d_sums), pool_release(ctx, L.d_off), pool_release(ctx, L.d_idx);
+    L = StrataLists();
+}
+static int strata_lists_alloc(avk_ctx *ctx, const avk_strata *st, uint64_t n, StrataLists &L) {
+    int rc = pool_alloc(ctx, &L.d_mask, (size_t)n * strata_words(st) * 4 + 16);
+    if (!rc) rc = pool_alloc(ctx, &L.d_sums, ((size_t)strata_blocks(n) + 1) * 8);
+    if (!rc) rc = pool_alloc(ctx, &L.d_off, (size_t)(n + 1) * 8);
+    return rc;
+}
+static int strata_lists_make(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *st, bool want_idx, StrataLists &L) {
+    const uint64_t n = db->n_regions;
+    int rc = strata_lists_alloc(ctx, st, n, L);
+    if (rc) return rc;
+    hipError_t e = strata_count_launch(st, db->dp_args.in, n, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums, ctx->stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(&L.total, (uint64_t *)L.d_sums + strata_blocks(n), 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "strata lists failed: %s", hipGetErrorString(e));
+    if (want_idx) rc = pool_alloc(ctx, &L.d_idx, (size_t)L.total * 4 + 16);
+    if (rc) return rc;
+    e = strata_fill_launch(st, n, (const uint32_t *)L.d_mask, (const uint64_t *)L.d_sums, (uint64_t *)L.d_off, want_idx ? (uint32_t *)L.d_idx : nullptr, L.total, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "strata lists failed: %s", hipGetErrorString(e));
+    return 0;
+}
+static int strata_handle_check(avk_ctx *ctx, const avk_strata *st) {
+    if (st->ctx != ctx) return fail(ctx, AVK_E_ARG, "strata: the handle was uploaded to another context");
+    return 0;
+}
+
+int avk_strata_region_labels(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *st, uint64_t *label_off, uint32_t *label_idx, uint64_t cap) {
+    if (!ctx || !db || !st || !label_off) return AVK_E_ARG;
+    if (strata_handle_check(ctx, st)) return AVK_E_ARG;
+    if (!db->dev_packed) return fail(ctx, AVK_E_STATE, "strata lists need a device-packed batch: the option device_pack was 0 at its upload");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = db->n_regions;
+    if (st->n_labels == 0) {
+        memset(label_off, 0, (size_t)(n + 1) * 8);
+        return 0;
+    }
+    StrataLists L;
+    const bool want_idx = label_idx != nullptr;
+    int rc = strata_lists_make(ctx, db, st, want_idx, L);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(label_off, L.d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const bool fits = L.total <= cap;
+    if (!rc && e == hipSuccess && want_idx && fits && L.total) e = hipMemcpyAsync(label_idx, L.d_idx, (size_t)L.total * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && e == hipSuccess) e = hipGetLastError();
+    strata_lists_release(ctx, L);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "strata lists failed: %s", hipGetErrorString(e));
+    if (want_idx && !fits) return fail(ctx, AVK_E_ARG, "strata lists: label_idx holds %llu entries, %llu are needed", (unsigned long long)cap, (unsigned long long)label_off[n]);
+    return 0;
+}
+
+int avk_label_tallies_strata(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *st, uint64_t *out) {
+    if (!ctx || !db || !st) return AVK_E_ARG;
+    if (!out) return fail(ctx, AVK_E_ARG, "label_tallies missing");
+    if (strata_handle_check(ctx, st)) return AVK_E_ARG;
+    if (st->n_labels == 0) return 0;
+    if (!db->dev_packed) return fail(ctx, AVK_E_STATE, "label sums from the compact results need a device-packed batch: the option device_pack was 0 at its upload");
+    if (!db->has_run || db->last_mode != 0) return fail(ctx, AVK_E_STATE, "label sums from the compact results need a batch that avk_compare_resident has solved");
+    if (!db->bp_valid) return fail(ctx, AVK_E_STATE, "the batch has no BASEPAIR groups on the device: set emit_bp_groups before avk_compare_resident");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = db->n_regions;
+    const size_t words = (size_t)st->n_labels * AVK_TALLY_LEN;
+    std::vector<uint64_t> host(words, 0);
+    StrataLists L;
+    void *d_out = nullptr;
+    int rc = strata_lists_make(ctx, db, st, true, L);
+    if (!rc) rc = pool_alloc(ctx, &d_out, words * 8);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
+    if (!rc && e == hipSuccess) rc = labels_launch(ctx, db, (const uint64_t *)L.d_off, (const uint32_t *)L.d_idx, st->n_labels, (uint64_t *)d_out, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && e == hipSuccess) e = hipGetLastError();
+    const uint64_t n_idx = L.total;
+    strata_lists_release(ctx, L);
+    pool_release(ctx, d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(e));
+    labels_timing_print(ctx, "resident, device lists", st->n_labels, n, n_idx);
+    for (size_t k = 0; k < words; ++k) out[k] += host[k];
+    return 0;
+}
+
+int avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg, avk_result_batch *out,
+                              uint64_t *label_tallies) {
+    if (!st || st->n_labels == 0) return avk_compare_packed_esc(ctx, batch, esc, cfg, out); /* the call without labels, launch for launch */
+    if (!batch) return AVK_E_ARG;
+    if (!label_tallies) return fail(ctx, AVK_E_ARG, "label_tallies missing");
+    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    if (strata_handle_check(ctx, st)) return AVK_E_ARG;
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->last_one_shot = 0;
+    if (!esc_present(esc)) esc = nullptr;
+    const uint64_t n = batch->n_regions;
+    const size_t words = (size_t)st->n_labels * AVK_TALLY_LEN;
+    avk_dev_batch *db = nullptr;
+    const int64_t keep_gm = ctx->emit_group_metrics, keep_bp = ctx->emit_bp_groups;
+    if (!out->group_metrics) ctx->emit_group_metrics = 0;
+    ctx->emit_bp_groups = 1; /* the groups are what the label kernel reads, whether the caller asked for them or not */
+    StrataLists L;
+    void *d_out = nullptr;
+    std::vector<uint64_t> host(words, 0);
+    int rc = strata_lists_alloc(ctx, st, n, L);
+    if (!rc) rc = pool_alloc(ctx, &d_out, words * 8);
+    if (!rc) { /* pass 1 of the lists runs inside the upload, behind the packer's region passes; their size comes back with the plan */
+        StrataJob job{st, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums};
+        ctx->strata_job = &job;
+        rc = avk_batch_upload_packed_esc(ctx, batch, esc, &db);
+        ctx->strata_job = nullptr;
+        if (!rc && n && !job.counted) rc = fail(ctx, AVK_E_STATE, "strata lists: the upload did not count them");
+        L.total = job.total;
+    }
+    if (!rc) rc = pool_alloc(ctx, &L.d_idx, (size_t)L.total * 4 + 16);
+    if (!rc) {
+        hipError_t e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
+        if (e == hipSuccess) e = strata_fill_launch(st, n, (const uint32_t *)L.d_mask, (const uint64_t *)L.d_sums, (uint64_t *)L.d_off, (uint32_t *)L.d_idx, L.total, ctx->stream);
+        if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata lists failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
+    if (!rc) rc = labels_launch(ctx, db, (const uint64_t *)L.d_off, (const uint32_t *)L.d_idx, st->n_labels, (uint64_t *)d_out, ctx->stream);
+    if (!rc && hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc) { /* (the download waits for the stream; a region its capacity retry repairs is added on the host, its list fetched from the device) */
+        LabelFix lf{nullptr, label_tallies, (const uint64_t *)L.d_off, (const uint32_t *)L.d_idx, n};
+        ctx->label_fix = &lf;
+        rc = avk_results_download(ctx, db, out);
+        ctx->label_fix = nullptr;
+        if (!rc && lf.err != hipSuccess) rc = fail(ctx, AVK_E_HIP, "label tallies: the lists of the regions the capacity retry repaired could not be fetched: %s", hipGetErrorString(lf.err));
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->emit_group_metrics = keep_gm, ctx->emit_bp_groups = keep_bp;
+    const uint64_t n_idx = L.total;
+    strata_lists_release(ctx, L);
+    pool_release(ctx, d_out);
+    if (db) {
+        ctx->last_one_shot = 1;
+        avk_batch_free(ctx, db);
+    }
+    if (rc) return rc;
+    labels_timing_print(ctx, "one call, device lists", st->n_labels, n, n_idx);
+    for (size_t k = 0; k < words; ++k) label_tallies[k] += host[k];
+    return 0;
 }
 
 /* solve_merge_region's pairwise test (merge_solver.rs:128-147) for every region of the batch: the "truth"

@@ -35,7 +35,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chr
 void usage() {
     fprintf(stderr,
             "usage: aardvark_amd_compare -r REF.fa[.gz] -t TRUTH.vcf[.gz] -q QUERY.vcf[.gz] -b REGIONS.bed[.gz] -o OUT_DIR\n"
-            "  [--truth-sample S] [--query-sample S] [--compare-label L] [--min-variant-gap 50] [--disable-variant-trimming]\n"
+            "  [--truth-sample S] [--query-sample S] [--compare-label L] [--strat-lists device|host] [--min-variant-gap 50] [--disable-variant-trimming]\n"
             "  [--reference-case upper|raw]  (default upper: soft-masked reference bases are compared as upper case)\n"
             "  [--max-branch-factor 50] [--enable-exact-shortcut] [--enable-haplotype-metrics] [--enable-weighted-haplotype-metrics]\n"
             "  [--enable-record-basepair-metrics] [-s STRAT.tsv] [--output-debug DIR] [--skip N] [--take N] [--device 0 | --devices 0,1,..] [--batch-regions 4000000] [--batch-form packed|wide]\n");
@@ -76,7 +76,7 @@ static void report_unsolved(const avk_region_batch &b, uint64_t r, int32_t statu
 int main(int argc, char **argv) {
     setenv("GPU_MAX_HW_QUEUES", "24", 0); /* before the first HIP call: the solver's six streams need hardware queues of their own (include/aardvark_amd.h, avk_ctx_create) */
     const auto t_start = std::chrono::steady_clock::now();
-    std::string ref, truth, query, bed, out_dir, truth_sample, query_sample, label = "compare", strat_tsv, debug_dir;
+    std::string ref, truth, query, bed, out_dir, truth_sample, query_sample, label = "compare", strat_tsv, debug_dir, strat_lists = "device";
     uint64_t gap = 50, branch = 50, skip = 0, take = 0, batch_regions = 4000000, threads = 1, max_ed = 5000, verbosity = 0;
     bool trimming = true, shortcut = false, hap = false, whap = false, rbp = false;
     bool ref_upper = true; /* --reference-case upper|raw (include/aardvark_feeder.h, avf_genome_load_case) */
@@ -136,6 +136,10 @@ int main(int argc, char **argv) {
         else if (a == "--max-edit-distance") max_ed = strtoull(val(), nullptr, 10); /* hidden in the reference as well, unused by it */
         else if (a == "-v" || a == "--verbose") verbosity += 1;
         else if (a == "-s" || a == "--stratification") strat_tsv = val();
+        else if (a == "--strat-lists") {
+            strat_lists = val();
+            if (strat_lists != "device" && strat_lists != "host") die(64, "--strat-lists takes device or host", strat_lists.c_str());
+        }
         else if (a == "--output-debug") debug_dir = val();
         else if (a == "-h" || a == "--help") {
             usage();
@@ -312,6 +316,15 @@ int main(int argc, char **argv) {
         lab.n_labels = n_lab, lab.label_off = label_off, lab.label_idx = label_idx;
         return avk_compare_packed_labels(c, &part, &part_esc, &lab, &cfg, &shifted, sums);
     };
+    /* ... and with the lists made on the device from the resident interval sets (avk_compare_packed_strata): nothing but the batch goes in */
+    auto compare_part_strata = [&](avk_ctx *c, uint64_t at_abs, uint64_t n, const avk_compare_config &cfg, const avk_result_batch &out, const avk_strata *sets, uint64_t *sums) -> int {
+        avk_packed_batch part;
+        avk_packed_escapes part_esc;
+        uint64_t v_first = 0;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, &v_first)) return AVK_E_ARG;
+        avk_result_batch shifted = out_for(out, v_first);
+        return avk_compare_packed_strata(c, &part, &part_esc, sets, &cfg, &shifted, sums);
+    };
     auto upload_part = [&](avk_ctx *c, const avk_region_batch &b, uint64_t at_abs, uint64_t n, avk_dev_batch **db, uint64_t *v_first) -> int {
         *v_first = 0;
         if (!packed) return avk_batch_upload(c, &b, db);
@@ -342,7 +355,38 @@ int main(int argc, char **argv) {
      * wide feed from per-region blocks that stay on the device (avk_label_tallies) */
     const bool device_labels = n_labels && !debug;
     const bool compact_labels = device_labels && packed;
+    /* --strat-lists device (the default: profiles/strata_device_ab.txt): the interval sets are uploaded once per context and the region -> label lists are made by
+     * kernel (avk_strata.inl); host: the feeder library lists them on host threads and they cross with the batch (A/B runs, and the fallback when the sets cannot be
+     * exported or uploaded).  The wide feed and the debug run keep their routes. */
+    bool strata_route = compact_labels && strat_lists == "device"; /* (falls back to the host route, with a note, when the sets cannot be exported or uploaded) */
+    std::vector<uint64_t> sx_tree_off;
+    std::vector<uint32_t> sx_start, sx_end_max;
+    const uint32_t sx_contigs = avf_genome_n_contigs(genome);
+    auto strata_upload = [&](avk_ctx *c, avk_strata **sets) -> int {
+        return avk_strata_upload(c, n_labels, sx_contigs, sx_tree_off.data(), sx_start.data(), sx_end_max.data(), sets);
+    };
+    avk_strata *strata = nullptr;
+    if (strata_route) {
+        sx_tree_off.assign((size_t)n_labels * sx_contigs + 1, 0);
+        std::string why;
+        if (avf_strat_export(strat, genome, sx_tree_off.data(), nullptr, nullptr)) why = std::string("cannot export the stratification sets: ") + avf_last_error();
+        if (why.empty()) {
+            sx_start.assign(sx_tree_off.back() + 1, 0), sx_end_max.assign(sx_tree_off.back() + 1, 0);
+            if (avf_strat_export(strat, genome, sx_tree_off.data(), sx_start.data(), sx_end_max.data())) why = std::string("cannot export the stratification sets: ") + avf_last_error();
+        }
+        if (why.empty() && strata_upload(ctx, &strata)) why = std::string("cannot upload the stratification sets: ") + avk_last_error(ctx);
+        if (!why.empty()) {
+            fprintf(stderr, "Warning: %s; the region labels are listed on the host instead (--strat-lists host).\n", why.c_str());
+            strata_route = false;
+        }
+    }
     (void)avk_ctx_set_option(ctx, "emit_group_metrics", (n_labels && !compact_labels) || debug ? 1 : 0);
+    if (verbosity && compact_labels) {
+        if (strata_route)
+            fprintf(stderr, "Region labels: listed on the GPU (--strat-lists device, avk_compare_packed_strata): %llu intervals of %u labels uploaded once per context.\n",
+                    (unsigned long long)sx_tree_off.back(), n_labels);
+        else fprintf(stderr, "Region labels: listed on the host (--strat-lists host, avf_strat_batch_labels) and copied with every batch.\n");
+    }
     if (verbosity && n_labels)
         fprintf(stderr, "Stratified sums: %s.\n", compact_labels ? "from the compact results on the GPU (avk_compare_packed_labels), no per-region metric blocks"
                                                      : device_labels ? "from per-region metric blocks on the GPU (avk_label_tallies)"
@@ -523,6 +567,12 @@ int main(int argc, char **argv) {
                 }
                 (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels && !compact_labels ? 1 : 0);
             }
+            avk_strata *my_sets = w > 0 ? nullptr : strata;
+            if (w > 0 && strata_route && strata_upload(my, &my_sets)) { /* this worker lists its batches' labels on the host */
+                std::lock_guard<std::mutex> lock(log_mutex);
+                fprintf(stderr, "Warning: cannot upload the stratification sets to context %zu: %s; its region labels are listed on the host.\n", w, avk_last_error(my));
+                my_sets = nullptr;
+            }
             std::vector<uint64_t> w_tally(AVK_TALLY_LEN);
             for (uint64_t bi = next_batch.fetch_add(1); bi < n_batches; bi = next_batch.fetch_add(1)) {
                 const uint64_t at = bi * batch_regions;
@@ -545,7 +595,8 @@ int main(int argc, char **argv) {
                 out.var_observed = var_observed.data();
                 out.var_class = var_class.data();
                 int rc = 0;
-                if (n_labels) {
+                if (strata_route && my_sets) rc = compare_part_strata(my, first + at, n, cfg, out, my_sets, w_strat[w].data());
+                else if (n_labels) {
                     std::vector<uint64_t> label_off(n + 1, 0);
                     std::vector<uint32_t> label_idx;
                     rc = avf_strat_batch_labels(strat, genome, all, first + at, n, label_off.data(), nullptr);
@@ -580,7 +631,10 @@ int main(int argc, char **argv) {
                         report_unsolved(b, r, out.status[r]);
                     }
             }
-            if (w > 0) avk_ctx_destroy(my);
+            if (w > 0) {
+                avk_strata_free(my, my_sets);
+                avk_ctx_destroy(my);
+            }
         };
         std::vector<std::thread> pool;
         for (size_t w = 1; w < n_workers; ++w) pool.emplace_back(worker, w);
@@ -632,7 +686,9 @@ int main(int argc, char **argv) {
             out.seq_stride = seq_stride.data();
             out.seq_len = seq_len.data();
         }
-        if (compact_labels) { /* one call: the lists go in with the batch, the sums come back with the results */
+        if (strata_route) { /* one call: the batch goes in, the sums come back with the results; the lists never exist on the host */
+            if (compare_part_strata(ctx, first + at, n, cfg, out, strata, strat_total.data())) die(70, "compare failed", avk_last_error(ctx));
+        } else if (compact_labels) { /* one call: the lists go in with the batch, the sums come back with the results */
             std::vector<uint64_t> label_off(n + 1, 0);
             std::vector<uint32_t> label_idx;
             int rc_labels = avf_strat_batch_labels(strat, genome, all, first + at, n, label_off.data(), nullptr);
@@ -716,6 +772,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Comparisons completed in %.3f seconds (%.2f M regions/s in the solve stage).\n", seconds_since(t_start),
             s_solve > 0 ? (double)count / s_solve / 1e6 : 0.0);
     th_free.join();
+    avk_strata_free(ctx, strata);
     avk_ctx_destroy(ctx);
     avf_feed_free(feed);
     avf_strat_free(strat);

@@ -197,6 +197,35 @@ int avf_strat_batch_labels(const avf_strat *s, const avf_genome *g, const avk_re
     });
     return 0;
 }
+/* The sets as the device keeps them (avk_strata_upload, include/aardvark_amd.h): tree (label l, contig c of the genome) = entries [tree_off[l * n_contigs + c],
+ * tree_off[l * n_contigs + c + 1]) of start[] and end_max[], 32-bit: negative starts become 0, intervals that start at 2^32 or beyond are dropped (no region
+ * starts behind them), the running maximum of the EXCLUSIVE ends is clamped to [0, 2^32 - 1] — "max_end >= last" is then "last < end_max".  The chromosome names
+ * are resolved to the genome's contig indices here, once; chromosomes the genome does not have are left out.  start == NULL: the sizes only.
+ * tree_off holds avf_strat_n_labels * avf_genome_n_contigs + 1 words; the other two tree_off[last] each. */
+int avf_strat_export(const avf_strat *s, const avf_genome *g, uint64_t *tree_off, uint32_t *start, uint32_t *end_max) {
+    if (!s || !g || !tree_off || (start && !end_max)) return avf_fail_(AVK_E_ARG, "null argument");
+    const uint32_t nc = avf_genome_n_contigs(g);
+    const int64_t top = 0xFFFFFFFFll;
+    uint64_t at = 0;
+    for (uint32_t l = 0; l < s->labels.size(); ++l)
+        for (uint32_t c = 0; c < nc; ++c) {
+            tree_off[(uint64_t)l * nc + c] = at;
+            const char *name = avf_genome_name(g, c);
+            const auto it = name ? s->trees[l].find(name) : s->trees[l].end();
+            if (it == s->trees[l].end()) continue;
+            const avf_strat::Tree &t = it->second;
+            for (size_t k = 0; k < t.start.size() && t.start[k] <= top; ++k, ++at) {
+                if (!start) continue;
+                const int64_t b = t.start[k] < 0 ? 0 : t.start[k];
+                /* max_end is inclusive: the exclusive end is one more (INT64_MAX cannot occur: atoll(e) - 1) */
+                const int64_t e = t.max_end[k] < 0 ? 0 : (t.max_end[k] >= top ? top : t.max_end[k] + 1);
+                start[at] = (uint32_t)b;
+                end_max[at] = (uint32_t)e;
+            }
+        }
+    tree_off[(uint64_t)s->labels.size() * nc] = at;
+    return 0;
+}
 void avf_strat_free(avf_strat *s) { delete s; }
 
 } /* extern "C" */

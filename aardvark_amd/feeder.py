@@ -68,6 +68,7 @@ def load_library():
     lib.avf_strat_region_labels.restype = C.c_uint32
     lib.avf_strat_region_labels.argtypes = [vp, vp, C.POINTER(AvkRegionBatch), C.c_uint64, u32p, C.c_uint32]
     lib.avf_strat_free.argtypes = [vp]
+    lib.avf_strat_export.argtypes = [vp, vp, C.POINTER(C.c_uint64), u32p, u32p]
     lib.avf_strat_batch_labels.argtypes = [vp, vp, C.POINTER(AvkRegionBatch), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), u32p]
     lib.avf_write_summary_stratified.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), vp, C.POINTER(C.c_uint64), C.c_uint32]
     lib.avf_region_summary_open.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(vp)]
@@ -371,6 +372,18 @@ class Stratifications:
         idx = np.zeros(int(off[n]) + 1, np.uint32)
         _check(self.lib, self.lib.avf_strat_batch_labels(self.handle, genome.handle, C.byref(cb), first, n, off.ctypes.data_as(u64p), idx.ctypes.data_as(u32p)))
         return off, idx[:int(off[n])]
+
+    def export(self, genome):
+        """avf_strat_export: the sets as avk_strata_upload takes them -> (n_labels, n_contigs, tree_off, start, end_max); tree (label l, contig c of `genome`) is
+        entries tree_off[l * n_contigs + c] .. tree_off[l * n_contigs + c + 1] of start (sorted) and end_max (running maximum of the exclusive ends), 32-bit"""
+        n_labels, n_contigs = len(self.labels), len(genome.names)
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        tree_off = np.zeros(n_labels * n_contigs + 1, np.uint64)
+        _check(self.lib, self.lib.avf_strat_export(self.handle, genome.handle, tree_off.ctypes.data_as(u64p), None, None))
+        total = int(tree_off[-1])
+        start, end_max = np.zeros(max(total, 1), np.uint32), np.zeros(max(total, 1), np.uint32)
+        _check(self.lib, self.lib.avf_strat_export(self.handle, genome.handle, tree_off.ctypes.data_as(u64p), start.ctypes.data_as(u32p), end_max.ctypes.data_as(u32p)))
+        return n_labels, n_contigs, tree_off, start[:total], end_max[:total]
 
     def close(self):
         if self.handle:

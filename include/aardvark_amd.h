@@ -535,6 +535,41 @@ int  avk_compare_packed_submit_labels(avk_ctx *ctx, const avk_packed_batch *batc
  * regions + 1 offsets; shard_idx (NULL: offsets only, to size it) the indices.  Per-rank sums add up over the ranks (avk_counts_allreduce). */
 int  avk_packed_shard_labels(const avk_packed_shard *s, const avk_region_labels *whole, uint64_t *shard_off, uint32_t *shard_idx);
 
+/* The stratification sets RESIDENT on the device and the containment lists made there (avk_strata.inl): a stratified job's interval sets are fixed, and what
+ * Stratifications::containments (src/parsing/stratifications.rs:189-199) asks of them for a region — CompareRegion::var_coordinates, compare_region.rs:54-66: the
+ * smaller of the sides' first call positions to the larger of the sides' LAST call's end — is on the device once the batch is packed.  avk_strata_upload copies
+ * the sets to HBM once per context; the calls below then make label_off / label_idx by kernel, in the layout and order of avf_strat_batch_labels, bit for bit,
+ * and no list is made on or copied from the host.
+ *   tree (label l, contig c) = entries [tree_off[l * n_contigs + c], tree_off[l * n_contigs + c + 1]) of start[] and end_max[]; start sorted within a tree,
+ *   end_max the running maximum of the intervals' EXCLUSIVE ends within a tree.  Coordinates are 32-bit (contigs are shorter than 4 Gbp by the packed form's own
+ *   limits); avf_strat_export of the feeder library writes the arrays and does the clamping.  A region is in label l when, with k = upper_bound(start, first),
+ *   k > 0 and last < end_max[k - 1] (first = the region's start, last = its end - 1).  Regions without calls, with start >= end, with call ranges outside the
+ *   batch or a contig >= n_contigs have no labels; a region's status plays no part.
+ * AVK_E_ARG, before any allocation: a decreasing tree_off, unsorted starts or a decreasing end_max inside a tree, NULL arrays with a non-zero total (these
+ * refusals need no device: with ctx == NULL avk_last_error(NULL) has their text).  n_labels == 0 is a valid, empty set.  A handle belongs to the context it was
+ * uploaded to (AVK_E_ARG with another one) and must be freed before that context is destroyed. */
+typedef struct avk_strata avk_strata;
+int  avk_strata_upload(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs,
+                       const uint64_t *tree_off,   /* [n_labels * n_contigs + 1], tree (l, c) at l * n_contigs + c */
+                       const uint32_t *start,      /* sorted per tree */
+                       const uint32_t *end_max,    /* running maximum of the EXCLUSIVE ends per tree */
+                       avk_strata **out);
+void avk_strata_free(avk_ctx *ctx, avk_strata *strata);
+uint32_t avk_strata_n_labels(const avk_strata *strata);
+/* the lists a resident, device-packed batch gets (wide, compact or packed upload, with or without escapes), downloaded: label_off[n_regions + 1], label_idx
+ * ascending within a region.  label_idx == NULL: the offsets only (label_off[n_regions] = entries needed).  A cap (entries of room in label_idx) that is too
+ * small: AVK_E_ARG with the needed size in label_off[n_regions].  Also how a caller gets lists to hand to avk_packed_shard_labels. */
+int  avk_strata_region_labels(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *strata, uint64_t *label_off, uint32_t *label_idx, uint64_t cap);
+/* avk_label_tallies_compact with the handle in place of the lists: same preconditions, refusals and semantics (sums ADDED to out[n_labels * AVK_TALLY_LEN], words
+ * AVK_TALLY_SOLVED / AVK_TALLY_ERRORS untouched, regions the capacity retry repaired counted when called after the download, more than avk_label_block labels
+ * are more passes) */
+int  avk_label_tallies_strata(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *strata, uint64_t *out);
+/* avk_compare_packed_labels with the handle in place of the lists: nothing but the batch goes in, the sums come back with the results.  The lists' count pass
+ * runs behind the packer's region passes and its total returns with the packer's plan, the call's one round trip.  strata == NULL or zero labels: exactly the
+ * call without labels, launch for launch.  An escaped batch takes the route it takes today. */
+int  avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata, const avk_compare_config *cfg,
+                               avk_result_batch *out, uint64_t *label_tallies);
+
 /* Merge path (src/merge_solver.rs:137-143): for pair p, optimize_sequences(set a, set b) and
  * report all_opt_haps[0].is_exact_match().  Pair p compares variant ranges
  * [t_off,t_cnt) vs [q_off,q_cnt) of region p of `batch` exactly like a CompareRegion. */

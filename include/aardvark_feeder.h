@@ -141,6 +141,11 @@ uint32_t avf_strat_region_labels(const avf_strat *s, const avf_genome *g, const 
  * (label_off[n] = entries needed), with room for that many entries the list itself.  This is what avk_label_tallies takes. */
 int avf_strat_batch_labels(const avf_strat *s, const avf_genome *g, const avk_region_batch *batch, uint64_t first, uint64_t n, uint64_t *label_off,
                            uint32_t *label_idx);
+/* the sets in the form avk_strata_upload takes (include/aardvark_amd.h): tree_off[avf_strat_n_labels * avf_genome_n_contigs + 1], tree (label l, contig c) at
+ * l * n_contigs + c; start[] sorted per tree and end_max[] the running maximum of the EXCLUSIVE ends, tree_off[last] entries each, clamped to 32 bits (negative
+ * starts 0, intervals starting at 2^32 or beyond dropped, ends in [0, 2^32 - 1]).  Chromosome names are resolved to the genome's contig indices once;
+ * chromosomes the genome lacks are left out.  start == NULL: tree_off only, to size the other two. */
+int avf_strat_export(const avf_strat *s, const avf_genome *g, uint64_t *tree_off, uint32_t *start, uint32_t *end_max);
 void avf_strat_free(avf_strat *s);
 /* avf_write_summary with the stratified blocks after the ALL block (summary.rs:203-222): strat_tallies holds
  * avf_strat_n_labels(s) blocks of AVK_TALLY_LEN words, block l = the sum over the regions label l contains */
