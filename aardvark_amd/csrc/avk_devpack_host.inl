@@ -1213,7 +1213,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
         uint64_t *m_start = (uint64_t *)tmp((nm + 1) * 8), *m_end = (uint64_t *)tmp((nm + 1) * 8);
         db->d_m_in_off = (uint64_t *)kept((nm * mk + 1) * 8);
         db->d_m_in_cnt = (uint32_t *)kept((nm * mk + 1) * 4);
-        db->d_in_zyg = d_zyg;
+        db->d_in_zyg = d_zyg, db->d_in_type = d_type;
         db->n_multi = nm, db->m_inputs = mk;
         if (rc) return bail(rc);
         if (pm) { /* the packed arrays as they are; in_off and a_off by prefix sums; one kernel writes the wide MultiRegion arrays the pair expansion reads */

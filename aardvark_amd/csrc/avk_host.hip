@@ -37,6 +37,7 @@
 #include "avk_devpack.inl"
 #include "avk_labels.inl"
 #include "avk_strata.inl"
+#include "avk_mergecount.inl"
 
 /* ---------------------------------------------------------------------------------- kernels */
 /* LDS passes: regions in the LDS slice of their wavefront (small slices at high occupancy first, then
@@ -366,6 +367,8 @@ struct avk_ctx {
     } stage[4];
     hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr; /* AVK_TIMING: around the label kernels */
     int64_t label_lds_bytes = 0;       /* LDS a launch of avk_label_tally_compact_kernel gets (0: not asked yet) */
+    int64_t mergecount_lds_bytes = 0;  /* ... and a launch of avk_merge_count_kernel */
+    int last_merge_counts_on_device = 0; /* the last avk_merge_packed_counts with counters made them by kernel */
     struct StrataJob *strata_job = nullptr; /* set while avk_compare_packed_strata uploads its batch: the packer's region passes also count the batch's containment lists (avk_strata.inl) */
     struct LabelFix *label_fix = nullptr; /* set while a one-call form with labels downloads: the capacity retry adds the repaired regions' blocks to the labels' sums */
     /* options */
@@ -534,6 +537,7 @@ struct avk_dev_batch {
     uint64_t *d_m_in_off = nullptr;       /* merge batches (avk_merge_batch): the MultiRegions' in_off / in_cnt and the calls' zygosities, for the classification kernel */
     uint32_t *d_m_in_cnt = nullptr;
     uint8_t *d_in_zyg = nullptr;
+    uint8_t *d_in_type = nullptr;         /* ... and their types, for the count kernel (avk_mergecount.inl) */
     uint64_t n_multi = 0;
     uint32_t m_inputs = 0;
     uint64_t v_lo = 0, v_hi = 0;          /* the calls the batch's regions own: results are copied back for this range of the caller's arrays only */
@@ -3923,13 +3927,53 @@ static bool merge_on_device(const avk_ctx *ctx, uint64_t n_regions, uint32_t k) 
     return ctx->device_pack && k >= 2 && k <= (uint32_t)avk::dp::DP_MERGE_KMAX && n_regions && n_regions * (uint64_t)(k * (k - 1) / 2) <= 0x7FFFFFFFull;
 }
 static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                uint64_t *members, const avk_packed_escapes *esc = nullptr);
+                                uint64_t *members, const avk_packed_escapes *esc = nullptr, uint64_t *counts = nullptr);
+static int merge_packed_internal(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
+                                 uint64_t *members, uint64_t *counts);
+/* the LDS a launch of the count kernel really gets (as for the label kernel: the whole CU's where the runtime grants it) */
+static int64_t mergecount_lds(avk_ctx *ctx) {
+    if (!ctx->mergecount_lds_bytes) {
+        int64_t b = 64 * 1024;
+        if (hipFuncSetAttribute((const void *)avk_merge_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) b = 160 * 1024;
+        else {
+            (void)hipGetLastError();
+            int attr = 0;
+            if (hipDeviceGetAttribute(&attr, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) == hipSuccess && attr > 0 && attr < b) b = attr;
+            else (void)hipGetLastError();
+        }
+        ctx->mergecount_lds_bytes = b;
+    }
+    return ctx->mergecount_lds_bytes;
+}
+int avk_merge_counts_in_lds(avk_ctx *ctx, uint32_t n_inputs) {
+    if (!ctx || avk_merge_counts_len(n_inputs) == 0) return 0;
+    (void)hipSetDevice(ctx->device);
+    return avk::mc::mc_fits_lds(n_inputs, (uint64_t)mergecount_lds(ctx)) ? 1 : 0;
+}
+int avk_last_merge_counts_on_device(avk_ctx *ctx) { return ctx ? ctx->last_merge_counts_on_device : 0; }
+
+/* The merge call with MergeSummaryWriter's counters: the batch's dense block is ADDED to counts[avk_merge_counts_len(k)].  On the device route the count kernel
+ * runs behind the classification kernel and its block comes back with the three result arrays; a batch without a device route is counted by
+ * avk_merge_counts_esc after the solve.  Either way a batch the host function refuses — or one with a call whose type nibble is no VariantType, in whatever
+ * region — is AVK_E_ARG with counts untouched (status / classification / members are then what the call without counters leaves). */
+int avk_merge_packed_counts(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
+                            uint64_t *members, uint64_t *counts) {
+    if (!counts) return avk_merge_packed_esc(ctx, pm, esc, cfg, status, classification, members);
+    if (!ctx || !pm || !cfg || !status || !classification || !members) return AVK_E_ARG;
+    ctx->last_merge_counts_on_device = 0;
+    if (avk_merge_counts_len(pm->n_inputs) == 0) return fail(ctx, AVK_E_ARG, "summary counters exist for 2 to %d inputs (n_inputs %u)", AVK_MERGE_COUNTS_MAX_INPUTS, pm->n_inputs);
+    return merge_packed_internal(ctx, pm, esc, cfg, status, classification, members, counts);
+}
 
 int avk_merge_packed(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification, uint64_t *members) {
     return avk_merge_packed_esc(ctx, pm, nullptr, cfg, status, classification, members);
 }
 int avk_merge_packed_esc(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
                          uint64_t *members) {
+    return merge_packed_internal(ctx, pm, esc, cfg, status, classification, members, nullptr);
+}
+static int merge_packed_internal(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
+                                 uint64_t *members, uint64_t *counts) {
     if (!ctx || !pm || !cfg || !status || !classification || !members) return AVK_E_ARG;
     if (!esc_present(esc)) esc = nullptr;
     const uint32_t k = pm->n_inputs;
@@ -3940,7 +3984,18 @@ int avk_merge_packed_esc(avk_ctx *ctx, const avk_packed_multi_batch *pm, const a
     avk_multi_batch mb;
     memset(&mb, 0, sizeof(mb));
     mb.n_regions = n, mb.n_inputs = k, mb.n_variants = nv, mb.allele_bytes = pm->allele_bytes, mb.allele_bytes_len = pm->allele_bytes_len;
-    if (merge_on_device(ctx, n, k)) return merge_batch_internal(ctx, &mb, pm, cfg, status, classification, members, esc);
+    if (merge_on_device(ctx, n, k)) return merge_batch_internal(ctx, &mb, pm, cfg, status, classification, members, esc, counts);
+    if (counts) { /* no device route: the solve as it is, then the host's count into a block of its own (nothing reaches counts[] of a batch that is refused) */
+        int rc = merge_packed_internal(ctx, pm, esc, cfg, status, classification, members, nullptr);
+        if (rc) return rc;
+        for (uint64_t v = 0; v < nv; ++v)
+            if ((pm->var_type_zyg[v] & 15u) >= AVK_N_VARIANT_TYPES) return fail(ctx, AVK_E_ARG, "summary counters: call %llu has the unknown type %u", (unsigned long long)v, pm->var_type_zyg[v] & 15u);
+        std::vector<uint64_t> block((size_t)avk_merge_counts_len(k), 0);
+        rc = avk_merge_counts_esc(pm, esc, status, classification, members, block.data());
+        if (rc) return fail(ctx, AVK_E_ARG, "summary counters: the batch and its results do not fit together (call counts, escape lists, classifications)");
+        for (size_t w = 0; w < block.size(); ++w) counts[w] += block[w];
+        return AVK_E_OK;
+    }
     PackedWideHost wh;
     if (!packed_widen_host(pm->len, n, pm->in_cnt, nullptr, n * k, pm->var_rel_pos, pm->a0_len, pm->a1_len, nv, esc, wh))
         return fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending, names an entry outside the batch, or lists an entry whose narrow field is not 0");
@@ -3976,7 +4031,7 @@ int avk_merge_batch(avk_ctx *ctx, const avk_multi_batch *mb, const avk_merge_con
 }
 
 static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                uint64_t *members, const avk_packed_escapes *esc) {
+                                uint64_t *members, const avk_packed_escapes *esc, uint64_t *counts) {
     if (!ctx || !mb || !cfg || !status || !classification || !members) return AVK_E_ARG;
     const uint32_t k = mb->n_inputs;
     if (k < 1 || k > 64) return fail(ctx, AVK_E_ARG, "n_inputs must be in [1, 64]");
@@ -4009,14 +4064,51 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "merge classification failed: %s", hipGetErrorString(e));
         }
+        /* the summary counters (avk_merge_packed_counts): a cleared block and its error word behind it, the count kernel behind the classification */
+        const size_t words = counts ? (size_t)avk::mc::merge_counts_words(k) : 0;
+        void *d_cnt = nullptr;
+        std::vector<uint64_t> h_cnt(counts ? words + 1 : 0);
+        if (!rc && counts) rc = pool_alloc(ctx, &d_cnt, (words + 1) * 8);
+        if (!rc && counts) {
+            const int64_t lds_max = mergecount_lds(ctx);
+            const bool in_lds = avk::mc::mc_fits_lds(k, (uint64_t)lds_max);
+            const size_t lds = in_lds ? words * 8 : 0;
+            avk::mc::McView v;
+            memset(&v, 0, sizeof(v));
+            v.status = (const int32_t *)d_st, v.classification = (const uint8_t *)d_cl, v.members = (const uint64_t *)d_mem, v.in_off = db->d_m_in_off, v.in_cnt = db->d_m_in_cnt,
+            v.var_type = db->d_in_type, v.n_regions = nm, v.n_variants = mb->n_variants, v.k = k;
+            /* a CU runs 2,048 work-items: two workgroups where their blocks fit beside each other (and where there are none) */
+            const uint32_t per_cu = lds * 2 <= (size_t)lds_max ? 2u : 1u;
+            uint64_t blocks = (nm * k + 1023) / 1024;
+            if (blocks > (uint64_t)ctx->n_cus * per_cu) blocks = (uint64_t)ctx->n_cus * per_cu;
+            hipError_t e = hipMemsetAsync(d_cnt, 0, (words + 1) * 8, ctx->stream);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(avk_merge_count_kernel, dim3((unsigned)blocks), dim3(1024), lds, ctx->stream, v, (uint32_t)(in_lds ? words : 0), (unsigned long long *)d_cnt,
+                                   (uint32_t *)((uint64_t *)d_cnt + words));
+                e = hipGetLastError();
+            }
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "merge counting failed: %s", hipGetErrorString(e));
+        }
         if (!rc) {
             std::vector<CopySeg> segs = {{status, d_st, nm * 4}, {classification, d_cl, nm}, {members, d_mem, nm * 8}};
+            if (counts) segs.push_back({h_cnt.data(), d_cnt, (words + 1) * 8});
             CopyOut co;
             rc = copy_out(ctx, segs, &co);
             if (!rc) rc = finish_copy_out(ctx, co);
         }
         (void)hipStreamSynchronize(ctx->stream);
-        pool_release(ctx, d_st), pool_release(ctx, d_cl), pool_release(ctx, d_mem);
+        pool_release(ctx, d_st), pool_release(ctx, d_cl), pool_release(ctx, d_mem), pool_release(ctx, d_cnt);
+        if (!rc && counts) { /* the error word first: nothing of a refused batch reaches counts[] */
+            const uint32_t err = (uint32_t)h_cnt[words];
+            if (err)
+                rc = fail(ctx, AVK_E_ARG, "summary counters: %s", err & avk::mc::MC_ERR_TYPE    ? "a call's type is none of the variant types"
+                                                                  : err & avk::mc::MC_ERR_RANGE ? "an input's calls are not inside the batch"
+                                                                                                : "a solved region's classification is not a merge classification");
+            else {
+                for (size_t w = 0; w < words; ++w) counts[w] += h_cnt[w];
+                ctx->last_merge_counts_on_device = 1;
+            }
+        }
         ctx->last_one_shot = rc == 0;
         avk_batch_free(ctx, db);
         return rc;

@@ -9,6 +9,8 @@
 
 #include <dlfcn.h>
 
+#include "avk_merge_reason.h"
+
 /* the escapes of a shard (avk_packed_escapes of the whole batch, gathered with the shard's regions and calls and rebased to the shard's indices) */
 struct ShardEscapes {
     avk_packed_escapes e;
@@ -275,20 +277,11 @@ void avk_packed_multi_shard_free(avk_packed_multi_shard *s) { delete s; }
  * lists (they compare lexicographically; the writer sorts, avf_write_merge_summary_counts).  Entry = ((reason * 12 + type) * k + input) * 2 + (0 pass | 1 fail). */
 uint64_t avk_merge_counts_len(uint32_t n_inputs) {
     if (n_inputs < 2 || n_inputs > AVK_MERGE_COUNTS_MAX_INPUTS) return 0;
-    const uint64_t reasons = 2 + 2 * (1ull << n_inputs) + n_inputs;
-    return reasons * AVK_N_VARIANT_TYPES * n_inputs * 2;
+    return avk::mc::merge_counts_words(n_inputs);
 }
 
-uint32_t avk_merge_counts_reason(uint32_t n_inputs, uint8_t classification, uint64_t members) {
-    const uint32_t masks = 1u << n_inputs;
-    switch (classification) {
-    case AVK_MERGE_DIFFERENT: return 0;
-    case AVK_MERGE_NO_CONFLICT: return 1 + (uint32_t)(members & (masks - 1));
-    case AVK_MERGE_MAJORITY_AGREE: return 1 + masks + (uint32_t)(members & (masks - 1));
-    case AVK_MERGE_CONFLICT_SELECTION: return 1 + 2 * masks + (uint32_t)(members < n_inputs ? members : 0);
-    default: return 1 + 2 * masks + n_inputs; /* AVK_MERGE_IDENTICAL */
-    }
-}
+/* (the numbering itself: avk_merge_reason.h, shared with the count kernel of avk_mergecount.inl) */
+uint32_t avk_merge_counts_reason(uint32_t n_inputs, uint8_t classification, uint64_t members) { return avk::mc::merge_reason(n_inputs, classification, members); }
 
 int avk_merge_counts(const avk_packed_multi_batch *b, const int32_t *status, const uint8_t *classification, const uint64_t *members, uint64_t *counts) {
     return avk_merge_counts_esc(b, nullptr, status, classification, members, counts);

@@ -36,7 +36,8 @@ void usage() {
             "  [-s SAMPLE ...] [-t TAG ...] [--output-summary SUMMARY.tsv|.csv] [--output-debug DIR]\n"
             "  [--min-variant-gap 50] [--disable-variant-trimming] [--merge-strategy exact|no_conflict|majority|all]\n"
             "  [--enable-no-conflict] [--enable-voting] [--conflict-select INDEX] [--max-branch-factor 50]\n"
-            "  [--skip N] [--take N] [--device 0 | --devices 0,1,..] [--batch-regions 1000000] [--contexts 2] [--batch-form packed|wide]\n");
+            "  [--skip N] [--take N] [--device 0 | --devices 0,1,..] [--batch-regions 1000000] [--contexts 2] [--batch-form packed|wide]\n"
+            "  [--summary-counts device|host (default host)]\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -72,6 +73,9 @@ int main(int argc, char **argv) {
     std::vector<std::string> vcfs, samples, tags;
     uint64_t gap = 50, branch = 50, skip = 0, take = 0, batch_regions = 1000000, threads = 1, verbosity = 0, contexts = 2;
     bool want_packed = true;
+    /* --summary-counts device: the summary counters come back with the merge call (avk_merge_packed_counts) | host (default): the host passes.  The default follows
+     * the measurement: `device` once the call with counters and the tool are measured no slower than the host route; no such measurement exists yet. */
+    bool counts_with_call = false;
     bool trimming = true, no_conflict = false, voting = false;
     bool ref_upper = true; /* --reference-case upper|raw (include/aardvark_feeder.h, avf_genome_load_case) */
     long long conflict_select = -1;
@@ -124,6 +128,11 @@ int main(int argc, char **argv) {
             const std::string v = val();
             if (v != "packed" && v != "wide") die(78, "--batch-form must be 'packed' or 'wide'", "");
             want_packed = v == "packed";
+        }
+        else if (a == "--summary-counts") {
+            const std::string v = val();
+            if (v != "device" && v != "host") die(78, "--summary-counts must be 'device' or 'host'", "");
+            counts_with_call = v == "device";
         }
         else if (a == "--threads") threads = strtoull(val(), nullptr, 10);
         else if (a == "-v" || a == "--verbose") verbosity += 1;
@@ -307,6 +316,23 @@ int main(int argc, char **argv) {
                 !packed ? "wide" : escaped ? "packed with escapes" : "packed", (unsigned long long)esc_all.n_esc_regions, (unsigned long long)esc_all.n_esc_slots,
                 (unsigned long long)esc_all.n_esc_calls, n_ranks, n_ranks == 1 ? " solves" : "s solve");
     std::vector<uint64_t> job_counts;
+    /* One solved batch: with `counts` its summary counters come back with the merge call; when that call fails where the plain call does not — an error from the
+     * counting alone — the batch is counted by the host function instead, with a warning.  2: the batch is solved, its counters are not. */
+    std::atomic<uint64_t> batches_by_kernel{0}, batches_by_host{0};
+    auto merge_and_count = [&](avk_ctx *my, const avk_packed_multi_batch *pb, const avk_packed_escapes *pe, int32_t *st, uint8_t *cl, uint64_t *mem, uint64_t *counts) -> int {
+        if (counts && counts_with_call) {
+            if (!avk_merge_packed_counts(my, pb, pe, &cfg, st, cl, mem, counts)) {
+                (avk_last_merge_counts_on_device(my) ? batches_by_kernel : batches_by_host) += 1;
+                return 0;
+            }
+            const std::string why = avk_last_error(my);
+            if (avk_merge_packed_esc(my, pb, pe, &cfg, st, cl, mem)) return 1;
+            fprintf(stderr, "warning: the summary counters did not come with the merge call (%s): this batch is counted on the host.\n", why.c_str());
+        } else if (avk_merge_packed_esc(my, pb, pe, &cfg, st, cl, mem)) return 1;
+        if (!counts) return 0;
+        batches_by_host += 1;
+        return avk_merge_counts_esc(pb, pe, st, cl, mem, counts) ? 2 : 0;
+    };
     if (n_ranks > 1) {
         avk_packed_multi_batch sel;
         avk_packed_escapes sel_esc;
@@ -358,11 +384,12 @@ int main(int argc, char **argv) {
             std::vector<uint8_t> s_cls(sb->n_regions + 1);
             std::vector<uint64_t> s_members(sb->n_regions + 1);
             const avk_packed_escapes *se = avk_packed_multi_shard_escapes(shard);
-            if (avk_merge_packed_esc(my, sb, se, &cfg, s_status.data(), s_cls.data(), s_members.data())) rank_err[w] = std::string("merge failed: ") + avk_last_error(my);
+            const int rc_shard = merge_and_count(my, sb, se, s_status.data(), s_cls.data(), s_members.data(), counts_len ? r_counts[w].data() : nullptr);
+            if (rc_shard == 1) rank_err[w] = std::string("merge failed: ") + avk_last_error(my);
             else {
                 (void)avk_packed_multi_shard_scatter(shard, s_status.data(), s_cls.data(), s_members.data(), status.data() + first, classification.data() + first,
                                                      members.data() + first);
-                if (counts_len && avk_merge_counts_esc(sb, se, s_status.data(), s_cls.data(), s_members.data(), r_counts[w].data())) rank_err[w] = "cannot count the shard's variants";
+                if (rc_shard == 2) rank_err[w] = "cannot count the shard's variants";
             }
             avk_packed_multi_shard_free(shard);
         };
@@ -416,6 +443,11 @@ int main(int argc, char **argv) {
     const int n_workers = n_ranks > 1 ? 0 : n_batches >= 2 && contexts >= 2 ? 2 : 1;
     std::atomic<uint64_t> next_batch{0};
     std::string worker_err[2];
+    /* the batches' summary counters, summed over the job per worker (packed feeds of at most AVK_MERGE_COUNTS_MAX_INPUTS call sets; --summary-counts host: the
+     * summary is made region by region by avf_write_merge_summary, as before) */
+    const bool job_counters = n_ranks == 1 && packed && counts_len != 0 && counts_with_call && !summary_path.empty();
+    std::vector<uint64_t> worker_counts[2];
+    std::atomic<bool> counters_whole{true};
     auto solve_batches = [&](int w) {
         avk_ctx *my = ctx;
         if (w > 0) {
@@ -453,7 +485,12 @@ int main(int argc, char **argv) {
                 avk_packed_multi_batch part;
                 avk_packed_escapes part_esc;
                 rc_merge = avf_packed_multi_slice_esc(feed, &packed_all, &esc_all, first + at, n, &part, &part_esc);
-                if (!rc_merge) rc_merge = avk_merge_packed_esc(my, &part, &part_esc, &cfg, status.data() + first + at, classification.data() + first + at, members.data() + first + at);
+                if (job_counters && worker_counts[w].empty()) worker_counts[w].assign(counts_len, 0);
+                if (!rc_merge) {
+                    rc_merge = merge_and_count(my, &part, &part_esc, status.data() + first + at, classification.data() + first + at, members.data() + first + at,
+                                               job_counters ? worker_counts[w].data() : nullptr);
+                    if (rc_merge == 2) counters_whole = false, rc_merge = 0; /* (the summary is then made from the per-region results) */
+                }
             } else
                 rc_merge = avk_merge_batch(my, &b, &cfg, status.data() + first + at, classification.data() + first + at, members.data() + first + at);
             if (rc_merge) {
@@ -470,6 +507,18 @@ int main(int argc, char **argv) {
         if (other.joinable()) other.join();
         for (int w = 0; w < 2; ++w)
             if (!worker_err[w].empty()) die(70, worker_err[w].c_str(), "");
+        if (job_counters && counters_whole) {
+            job_counts.assign(counts_len, 0);
+            for (int w = 0; w < 2; ++w)
+                for (size_t i = 0; i < worker_counts[w].size(); ++i) job_counts[i] += worker_counts[w][i];
+        }
+    }
+    if (verbosity) {
+        if (!job_counts.empty())
+            fprintf(stderr, "Summary counters: --summary-counts %s; %llu batch%s counted by kernel with the merge call, %llu by the host function.\n", counts_with_call ? "device" : "host",
+                    (unsigned long long)batches_by_kernel.load(), batches_by_kernel.load() == 1 ? "" : "es", (unsigned long long)batches_by_host.load());
+        else
+            fprintf(stderr, "Summary counters: --summary-counts %s; the summary is made region by region on the host (avf_write_merge_summary).\n", counts_with_call ? "device" : "host");
     }
     for (uint64_t r = first; r < first + count; ++r) {
         if (status[r] == 0) {

@@ -319,8 +319,10 @@ def pinned_multi_batch(ctx, mb):
     return type(mb)(mb.n_inputs, **arrays)
 
 
-def merge_multi_batch(ctx, mb, config=None):
-    """avk_merge_batch on a MultiBatch, avk_merge_packed on a PackedMultiBatch: all of solve_merge_region on the GPU -> MergeResult"""
+def merge_multi_batch(ctx, mb, config=None, counts=None):
+    """avk_merge_batch on a MultiBatch, avk_merge_packed on a PackedMultiBatch: all of solve_merge_region on the GPU -> MergeResult.
+    counts (a PackedMultiBatch only): a uint64 array of merge_counts_len(k) words that the batch's summary counters are ADDED to by the same call
+    (avk_merge_packed_counts: by kernel on the device route, by avk_merge_counts_esc otherwise; counts_on_device(ctx) says which it was)"""
     config = config or MergeConfig()
     n = mb.n_regions
     cfg = AvkMergeConfig(config.max_branch_factor, int(config.no_conflict_enabled), int(config.majority_voting_enabled),
@@ -332,6 +334,16 @@ def merge_multi_batch(ctx, mb, config=None):
     cb = mb.c_struct()
     packed = isinstance(mb, PackedMultiBatch)
     esc = mb.c_escapes() if packed else None
+    if counts is not None:
+        if not packed:
+            raise ValueError("summary counters come with the packed merge call (a PackedMultiBatch)")
+        assert counts.dtype == np.uint64 and counts.flags.c_contiguous and counts.size >= max(merge_counts_len(ctx.lib, mb.n_inputs), 1)
+        entry = ctx.lib.avk_merge_packed_counts
+        entry.argtypes = [C.c_void_p, C.POINTER(AvkPackedMultiBatch), C.POINTER(AvkPackedEscapes), C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
+                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        ctx._check(entry(ctx.handle, C.byref(cb), C.byref(esc) if esc is not None else None, C.byref(cfg), P(st, C.c_int32), P(cls, C.c_uint8), P(members, C.c_uint64),
+                         P(counts, C.c_uint64)))
+        return MergeResult(st[:n], cls[:n], members[:n], mb.n_inputs)
     if esc is not None:
         entry = ctx.lib.avk_merge_packed_esc
         entry.argtypes = [C.c_void_p, C.POINTER(AvkPackedMultiBatch), C.POINTER(AvkPackedEscapes), C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
@@ -342,6 +354,18 @@ def merge_multi_batch(ctx, mb, config=None):
     entry.argtypes = [C.c_void_p, C.POINTER(AvkPackedMultiBatch if packed else AvkMultiBatch), C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
     ctx._check(entry(ctx.handle, C.byref(cb), C.byref(cfg), P(st, C.c_int32), P(cls, C.c_uint8), P(members, C.c_uint64)))
     return MergeResult(st[:n], cls[:n], members[:n], mb.n_inputs)
+
+
+def counts_on_device(ctx):
+    """avk_last_merge_counts_on_device: the context's last merge call with counters made them by kernel"""
+    ctx.lib.avk_last_merge_counts_on_device.argtypes = [C.c_void_p]
+    return bool(ctx.lib.avk_last_merge_counts_on_device(ctx.handle))
+
+
+def counts_in_lds(ctx, n_inputs):
+    """avk_merge_counts_in_lds: the count kernel of this context keeps the dense block of n_inputs inputs in the workgroup's LDS (beyond: reduced within the wave)"""
+    ctx.lib.avk_merge_counts_in_lds.argtypes = [C.c_void_p, C.c_uint32]
+    return bool(ctx.lib.avk_merge_counts_in_lds(ctx.handle, n_inputs))
 
 
 def merge_batch(ctx, multi_regions, config=None):

@@ -651,7 +651,8 @@ int avk_merge_packed_esc(avk_ctx *ctx, const avk_packed_multi_batch *batch, cons
  * sums — entry ((reason * AVK_N_VARIANT_TYPES + type) * k + input) * 2 + (0 pass | 1 fail), reason = avk_merge_counts_reason() — which the ranks sum with one
  * avk_counts_allreduce (RCCL) or on the host, and avf_write_merge_summary_counts of the feeder library writes as the reference's table.  Dense blocks exist for
  * k <= AVK_MERGE_COUNTS_MAX_INPUTS inputs (the reasons carry a subset of the inputs: 2 + 2 * 2^k + k of them); avk_merge_counts_len is 0 beyond, and a job with
- * more inputs writes its summary from the scattered per-region arrays (avf_write_merge_summary). */
+ * more inputs writes its summary from the scattered per-region arrays (avf_write_merge_summary).  avk_merge_packed_counts (below) makes a batch's block with the
+ * merge call itself, by a kernel behind the classification: no pass over the results on the host. */
 typedef struct avk_packed_multi_shard avk_packed_multi_shard;
 int  avk_packed_multi_shard_make(const avk_packed_multi_batch *whole, const uint64_t *region_id, uint64_t first_id, uint32_t rank, uint32_t world,
                                  avk_packed_multi_shard **out);
@@ -670,6 +671,20 @@ int  avk_merge_counts(const avk_packed_multi_batch *batch, const int32_t *status
 /* the same for a batch with escapes (it reads in_cnt; NULL: avk_merge_counts) */
 int  avk_merge_counts_esc(const avk_packed_multi_batch *batch, const avk_packed_escapes *esc, const int32_t *status, const uint8_t *classification, const uint64_t *members,
                           uint64_t *counts);
+/* The counters WITH the merge call: avk_merge_packed_esc that also ADDS the batch's dense block to counts[avk_merge_counts_len(k)].  Everything
+ * avk_merge_counts_esc reads is on the device when the classification ends, so on the device route (device_pack on, k <= 8, a batch that is not empty) a kernel
+ * counts there — one lane per (region, input), sums kept in the workgroup's LDS where the block of k inputs fits it (avk_merge_counts_in_lds: k <= 6 with
+ * 160 KB) and reduced within the wave beyond — and the block comes back with status / classification / members; every other batch (k = 9 or 10,
+ * device_pack = 0, no regions) is solved as by avk_merge_packed_esc and counted by avk_merge_counts_esc here.  The sums are the host function's, word for word.
+ *   counts == NULL: avk_merge_packed_esc, launch for launch.
+ *   AVK_E_ARG before anything is queued: counts != NULL with n_inputs outside [2, AVK_MERGE_COUNTS_MAX_INPUTS].
+ *   AVK_E_ARG with counts untouched: a batch avk_merge_counts_esc refuses, and a call whose type nibble is >= AVK_N_VARIANT_TYPES in ANY region (the host
+ *   function looks at solved regions only; such a call leaves its region unsolved).  The three result arrays are then what the call without counters writes.
+ * avk_last_merge_counts_on_device: 1 when the context's last call with counters made them by kernel. */
+int  avk_merge_packed_counts(avk_ctx *ctx, const avk_packed_multi_batch *batch, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status,
+                             uint8_t *classification, uint64_t *members, uint64_t *counts /* [avk_merge_counts_len(k)], ADDED to */);
+int  avk_last_merge_counts_on_device(avk_ctx *ctx);
+int  avk_merge_counts_in_lds(avk_ctx *ctx, uint32_t n_inputs); /* 1: the count kernel of this context keeps the block of n_inputs inputs in LDS */
 
 /* Host utility (no GPU involved): unit-cost edit distance of two byte strings, the value of the reference's
  * wfa_ed (src/util/sequence_alignment.rs:9-13).  The batch packer uses it for Variant::alt_ed
