@@ -29,6 +29,7 @@
 
 #include "../../include/aardvark_amd.h"
 #include "avk_pack.h"
+#include "avk_counters.h"
 #include "avk_solver.inl"
 #include "avk_lane.inl"
 #include "avk_quad.inl"
@@ -323,8 +324,7 @@ struct PoolBlk { /* a device buffer of the context's pool (avk_devpack_host.inl)
 
 } // namespace
 
-#define AVK_N_COUNTERS 1408
-#define AVK_STREAM_ORDER_DEFAULT "stwxxabxxcd" /* profiles/r06_stream_order.txt */ /* words of avk_dev_batch::d_counters */
+#define AVK_STREAM_ORDER_DEFAULT "stwxxabxxcd" /* profiles/r06_stream_order.txt */
 
 struct avk_ctx {
     int device = 0;
@@ -505,7 +505,7 @@ struct avk_dev_batch {
     uint32_t *d_seqlen = nullptr;
     uint64_t *d_tally = nullptr;    /* [AVK_TALLY_STRIDE]: AVK_TALLY_LEN sums, 5 tier counters, 8 profiling words */
     uint64_t *d_partials = nullptr; /* [AVK_TALLY_COPIES][AVK_TALLY_STRIDE] */
-    uint32_t *d_counters = nullptr; /* [256*t + 32*s] claim counter of shard s in pass t, [1024 + 16*k] overflow counts, [1072] claim counter of the solo waves */
+    uint32_t *d_counters = nullptr; /* AVK_N_COUNTERS words the launches of a step coordinate through: avk_counters.h says which are whose */
     uint32_t *d_overflow = nullptr, *d_overflow2 = nullptr, *d_overflow3 = nullptr, *d_overflow4 = nullptr;
     uint32_t *d_notwide = nullptr;   /* [n + 1] class C records that are not avk_wide.inl's, then their number (avk_notwide_list_kernel, once per batch) */
     bool notwide_ready = false;
@@ -1555,7 +1555,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
     const bool timed = ctx->timing_events != 0;
     if (timed) AVK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     ctx->ev_lane_valid = false;
-    const uint32_t big_slots = use[2] && use[3] ? (uint32_t)(big_waves < 128 ? big_waves : 128) : 0u;
+    const uint32_t big_slots = use[2] && use[3] ? (uint32_t)(big_waves < (int64_t)AVK_CTR_BIG_BUSY_LEN ? big_waves : (int64_t)AVK_CTR_BIG_BUSY_LEN) : 0u;
     const uint32_t *list = nullptr, *count = nullptr; /* first launch: the records themselves are in work order */
     uint32_t *lists[4] = {db->d_overflow, db->d_overflow2, db->d_overflow3, db->d_overflow4};
     int nlist = 0;
@@ -1572,10 +1572,10 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
         a.work_list = list;
         a.work_base = 0;
         a.n_work_dev = count;
-        a.work_counter = db->d_counters + 256 * t;
+        a.work_counter = db->d_counters + avk_ctr_tier_cursors((uint32_t)t);
         if (t != last) {
             a.overflow_list = lists[nlist];
-            a.overflow_count = db->d_counters + 1024 + 16 * nlist;
+            a.overflow_count = db->d_counters + avk_ctr_overflow_count((uint32_t)nlist);
         } else {
             a.overflow_list = nullptr;
             a.overflow_count = nullptr;
@@ -1583,11 +1583,11 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
         const bool first_launch = list == nullptr; /* ev0 sits right before it */
         if (t >= 2) { /* the HBM launches read the list the LDS solo launch appends to; the tier-1 launch does not */
             if (deferred_pending && chains) { /* what the chains' launches of avk_wide.inl left: ahead of the waits for the long solo launches, which it does not depend on */
-        for (int k = 0; k < n_chain_join; ++k) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, chain_join[k], 0));
-        hipLaunchKernelGGL(avk_region_kernel_lds_lazy, dim3(chain_dblocks), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ctx->stream, chain_d);
-        AVK_HIP(ctx, hipGetLastError());
-    }
-    if (solo_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+                for (int k = 0; k < n_chain_join; ++k) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, chain_join[k], 0));
+                hipLaunchKernelGGL(avk_region_kernel_lds_lazy, dim3(chain_dblocks), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ctx->stream, chain_d);
+                AVK_HIP(ctx, hipGetLastError());
+            }
+            if (solo_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
             solo_pending = false;
             /* the tier-3 launch of its own (big_slots == 0) reads the list the HBM solo launch appends to */
             if (t == 3 && hbm_solo_pending) {
@@ -1647,7 +1647,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
             }
             bool wide_c = false, wide_x = false;
             if (hbm_solo) {
-                AvkKernelArgs s = a;
+                const uint32_t *c_list = nullptr, *c_left = nullptr; /* what the launches of avk_wide.inl leave of class C (without them: the class's records themselves) */
                 AVK_HIP(ctx, hipStreamWaitEvent(ctx->side_stream2, ctx->ev_fork, 0));
                 /* how many of them are not the wide kernel's by their own record (a long window, many calls on a side): none or few in a genome, all of them in a
                  * batch of large windows (--min-variant-gap 1000) — which then keeps the launches of round 3: every HBM wave on the whole list */
@@ -1658,9 +1658,9 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                     w.n_work_dev = nullptr;
                     w.work_base = 0;
                     w.n_work = n_c;
-                    w.work_counter = db->d_counters + 1240;
+                    w.work_counter = db->d_counters + AVK_CTR_WIDE_C_CURSOR;
                     w.overflow_list = db->d_overflow5;
-                    w.overflow_count = db->d_counters + 1244;
+                    w.overflow_count = db->d_counters + AVK_CTR_WIDE_C_LEFT;
                     /* (512 one-wave workgroups for a genome's 6,000-15,000 records; a merge job's 42,000 lasted 7.2 ms on them, the longest launch of its step: one
                      * workgroup per 32 records up to four times as many — profiles/r06_merge_step.txt) */
                     uint32_t wb = (uint32_t)ctx->wide_blocks;
@@ -1682,31 +1682,14 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                     AVK_HIP(ctx, hipGetLastError());
                     if (n_nw && xb) { /* the records of class C that are not for the wide kernel by what they say themselves (avk_wide_static_ok: a long window, many calls on a
                        * side) start at the same time, on the HBM-tier kernel and a stream of their own: they are few and each of them is long */
-                        AvkKernelArgs x = s;
-                        x.pass_tier = 2;
-                        x.only_not_wide = 1;
-                        x.work_list = nullptr;
-                        x.n_work_dev = nullptr;
-                        x.work_base = 0;
-                        x.n_work = n_c;
-                        x.work_counter = db->d_counters + 1256;
-                        x.static_pct = 0;
-                        x.n_shards = 1;
-                        x.n_waves = xb * waves_per_block;
                         /* a wave per record, one claim each, from a list made just ahead of the launch (walking the whole class in claims of four, a wave solved the
                          * records of a claim one after the other: 2.06 -> 1.91 ms for the genome's 27, 0.96 -> 0.90 for a shard's 7) */
-                        x.only_not_wide = 0;
-                        x.work_list = db->d_notwide;
-                        x.n_work_dev = db->d_notwide + n + 1;
-                        x.n_work = 0;
-                        x.claim = 1;
+                        AvkKernelArgs x = avk_list_reader_args(a, db->d_notwide, db->d_notwide + n + 1, db->d_counters + AVK_CTR_TEAM_CURSOR);
+                        x.pass_tier = 2;
                         x.high_priority = 1;
+                        x.n_waves = xb * waves_per_block;
                         x.hbm_ws = ctx->d_ws + (size_t)(n_waves + (hbm_solo_max - xb) * waves_per_block) * (size_t)ws_bytes; /* the last slices of the solo launch's share (that launch gets the others) */
-                        x.big_ws = ctx->d_big;
-                        x.big_busy = db->d_counters + 1088;
-                        x.big_slots = big_slots;
-                        x.overflow_list = nullptr;
-                        x.overflow_count = nullptr;
+                        avk_big_slice_args(x, ctx->d_big, db->d_counters, big_slots);
                         AVK_HIP(ctx, hipStreamWaitEvent(ctx->wide_stream, ctx->ev_fork, 0));
                         /* (a wave per region here: these long windows hold a handful of calls, their searches are short chains where a team's hand-overs cost more
                          * than its parallel pieces give — shard 1.19 -> 1.31 ms, dense mix 2.29 -> 2.53 with teams, profiles/r06_team.txt) */
@@ -1717,25 +1700,25 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                         if (hbm_solo > hbm_solo_max - xb) hbm_solo = hbm_solo_max - xb; /* (at least half of the share: xb <= hbm_solo_max / 2) */
                     }
                     wide_c = true;
-                    s.work_list = db->d_overflow5;
-                    s.n_work_dev = db->d_counters + 1244;
+                    c_list = db->d_overflow5;
+                    c_left = db->d_counters + AVK_CTR_WIDE_C_LEFT;
                     if (ctx->wide_retry_lds_bytes > ctx->wide_lds_bytes) {
                         /* what it hands over at run time is nearly always a search that outgrew the 16 KB (nodes, wavefront blocks): once more with the LDS of a
                          * whole workgroup, a few waves — the wave-per-region kernel needs 2 ms for such a region, at the end of this chain */
                         AvkKernelArgs w2 = w;
                         w2.work_list = db->d_overflow5;
-                        w2.n_work_dev = db->d_counters + 1244;
+                        w2.n_work_dev = db->d_counters + AVK_CTR_WIDE_C_LEFT;
                         w2.work_base = 0;
                         w2.n_work = 0;
-                        w2.work_counter = db->d_counters + 1268;
+                        w2.work_counter = db->d_counters + AVK_CTR_WIDE_RETRY_CURSOR;
                         w2.overflow_list = db->d_overflow8;
-                        w2.overflow_count = db->d_counters + 1272;
+                        w2.overflow_count = db->d_counters + AVK_CTR_WIDE_RETRY_LEFT;
                         avk::wide::WideArgs wb = wa;
                         wb.lds_words = (uint32_t)(ctx->wide_retry_lds_bytes / 4);
                         hipLaunchKernelGGL(avk_wide_kernel, dim3(32), dim3(64), (size_t)ctx->wide_retry_lds_bytes, ctx->side_stream2, w2, wb);
                         AVK_HIP(ctx, hipGetLastError());
-                        s.work_list = db->d_overflow8;
-                        s.n_work_dev = db->d_counters + 1272;
+                        c_list = db->d_overflow8;
+                        c_left = db->d_counters + AVK_CTR_WIDE_RETRY_LEFT;
                     }
                 }
                 uint32_t team_head = 0; /* records at the front of class C (most calls first) that a team launch takes */
@@ -1746,26 +1729,14 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                     uint32_t xb = n_c / 2u < (uint32_t)ctx->team_head_regions ? n_c / 2u : (uint32_t)ctx->team_head_regions;
                     if (xb > hbm_solo_max / 2u) xb = hbm_solo_max / 2u;
                     if (xb) {
-                        AvkKernelArgs x = s;
-                        x.pass_tier = 2;
-                        x.only_not_wide = 0;
-                        x.team = (uint32_t)ctx->team_long_windows;
-                        x.work_list = nullptr;
-                        x.n_work_dev = nullptr;
-                        x.work_base = 0;
+                        AvkKernelArgs x = avk_list_reader_args(a, nullptr, nullptr, db->d_counters + AVK_CTR_TEAM_CURSOR); /* (no list: the first xb records) */
                         x.n_work = xb;
-                        x.work_counter = db->d_counters + 1256;
-                        x.static_pct = 0;
-                        x.n_shards = 1;
-                        x.n_waves = xb * waves_per_block;
-                        x.claim = 1;
+                        x.pass_tier = 2;
+                        x.team = (uint32_t)ctx->team_long_windows;
                         x.high_priority = 1;
+                        x.n_waves = xb * waves_per_block;
                         x.hbm_ws = ctx->d_ws + (size_t)(n_waves + (hbm_solo_max - xb) * waves_per_block) * (size_t)ws_bytes; /* the last slices of the solo launch's share */
-                        x.big_ws = ctx->d_big;
-                        x.big_busy = db->d_counters + 1088;
-                        x.big_slots = big_slots;
-                        x.overflow_list = nullptr;
-                        x.overflow_count = nullptr;
+                        avk_big_slice_args(x, ctx->d_big, db->d_counters, big_slots);
                         AVK_HIP(ctx, hipStreamWaitEvent(ctx->wide_stream, ctx->ev_fork, 0));
                         hipLaunchKernelGGL(avk_region_kernel_team, dim3(xb), dim3(256), 0, ctx->wide_stream, x);
                         AVK_HIP(ctx, hipGetLastError());
@@ -1775,24 +1746,18 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                         if (hbm_solo > hbm_solo_max - xb) hbm_solo = hbm_solo_max - xb;
                     }
                 }
-                s.pass_tier = 2;
+                AvkKernelArgs s = avk_list_reader_args(a, c_list, c_left, db->d_counters + AVK_CTR_HBM_SOLO_TICKET);
                 s.work_base = team_head;
                 s.n_work = n_c - team_head;
-                s.work_counter = db->d_counters + 1076;
-                s.static_pct = 0;
-                s.n_shards = 1;
-                s.claim = 1;
-                s.n_waves = hbm_solo * waves_per_block;
+                s.pass_tier = 2;
                 s.high_priority = 1;
+                s.n_waves = hbm_solo * waves_per_block;
                 s.hbm_ws = ctx->d_ws + (size_t)n_waves * (size_t)ws_bytes; /* its own slices: the main stream's HBM launch may run beside it */
-                s.big_ws = ctx->d_big;
-                s.big_busy = db->d_counters + 1088;
-                s.big_slots = big_slots;
-                s.overflow_list = nullptr; /* same capacities as the last tier: what does not fit fails with CAPACITY */
-                s.overflow_count = nullptr;
+                avk_big_slice_args(s, ctx->d_big, db->d_counters, big_slots);
+                /* same capacities as the last tier: what does not fit fails with CAPACITY */
                 if (!big_slots && launch[3]) { /* the big tier has a launch of its own */
                     s.overflow_list = lists[launch[1] ? 2 : 1];
-                    s.overflow_count = db->d_counters + 1024 + 16 * (launch[1] ? 2 : 1);
+                    s.overflow_count = db->d_counters + avk_ctr_overflow_count(launch[1] ? 2 : 1);
                 }
                 hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(hbm_solo), dim3(256), 0, ctx->side_stream2, s);
                 AVK_HIP(ctx, hipGetLastError());
@@ -1807,14 +1772,14 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                 s.pass_tier = 1;
                 s.work_base = n_c;
                 s.n_work = solo_regions;
-                s.work_counter = db->d_counters + 1072;
+                s.work_counter = db->d_counters + AVK_CTR_LDS_SOLO_CURSOR;
                 s.static_pct = 0;
                 s.n_shards = 1;
                 s.claim = 1;
                 s.n_waves = solo;
                 s.high_priority = 1;
                 s.overflow_list = later ? lists[solo_list] : nullptr;
-                s.overflow_count = later ? db->d_counters + 1024 + 16 * solo_list : nullptr;
+                s.overflow_count = later ? db->d_counters + avk_ctr_overflow_count((uint32_t)solo_list) : nullptr;
                 AVK_HIP(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
                 hipLaunchKernelGGL(avk_region_kernel_lds, dim3(solo), dim3(64), (size_t)ctx->lds2_bytes_per_wave, ctx->side_stream, s);
                 AVK_HIP(ctx, hipGetLastError());
@@ -1836,13 +1801,13 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
             if (use_fast) {
                 if (!ctx->lane_attr_set) {
                     AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_lane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel_wide_regs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel_wide_regs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                     ctx->lane_attr_set = true;
                 }
                 AvkKernelArgs f = a;
                 f.overflow_list = lists[2];
-                f.overflow_count = db->d_counters + 1024 + 32;
+                f.overflow_count = db->d_counters + avk_ctr_overflow_count(AVK_CTR_DEFERRED_LIST);
                 AVK_HIP(ctx, hipEventRecord(ctx->ev_lane_fork, ctx->stream));
                 /* hand-backs per chain: the launches of a lane stream append to a list of the stream's own, a head launch to one of its own; a list is read by a launch
                  * of avk_wide.inl that follows its writers in stream order (the chain's list: on the chain's stream, no event; a head's: on the fourth lane stream,
@@ -1855,7 +1820,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                 uint32_t hb_off = 0;
                 int hb_n = 0, hb_heads = 0;
                 auto hb_new = [&](uint32_t cap) {
-                    HbSeg g = {lists[2] + hb_off, db->d_counters + 1296 + hb_n, db->d_counters + 1328 + hb_n};
+                    HbSeg g = {lists[2] + hb_off, db->d_counters + AVK_CTR_HB_COUNTS + hb_n, db->d_counters + AVK_CTR_HB_CURSORS + hb_n}; /* (hb_n < AVK_CTR_HB_SEGS: two chains, the staged heads, the pairs' list) */
                     hb_off += cap;
                     hb_n += 1;
                     return g;
@@ -1868,7 +1833,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                     w.n_work = 0;
                     w.work_counter = g.cursor;
                     w.overflow_list = db->d_overflow7;
-                    w.overflow_count = db->d_counters + 1264;
+                    w.overflow_count = db->d_counters + AVK_CTR_WIDE_LANES_LEFT;
                     hipLaunchKernelGGL(avk_wide_kernel_lazy, dim3((uint32_t)ctx->wide_lazy_blocks), dim3(64), (size_t)ctx->wide_lds_bytes, st, w, wa);
                     return hipGetLastError();
                 };
@@ -1902,7 +1867,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                         pa.n_tiles = db->fast_tiles[fc];
                         pa.gen_base = db->plan.fast_base[fc];
                         pa.tab = ctx->d_pair_tab;
-                        pa.tile_counter = db->d_counters + 1220 + fc;
+                        pa.tile_counter = db->d_counters + AVK_CTR_LANE_TILES + fc;
                         uint32_t pg = (uint32_t)ctx->n_cus * (uint32_t)(ctx->pair_blocks_per_cu > 0 ? ctx->pair_blocks_per_cu : 1);
                         const uint32_t claims = (pa.n_tiles + avk::pairs::PAIR_CLAIM - 1) / avk::pairs::PAIR_CLAIM;
                         if (pg > (claims + 3u) / 4u) pg = (claims + 3u) / 4u;
@@ -1921,7 +1886,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                     la.recs = db->d_fast + db->fast_word_base[fc];
                     la.rec_words = AVK_FAST_WORDS_OF(cl.maxv);
                     la.n_tiles = db->fast_tiles[fc];
-                    la.tile_counter = db->d_counters + 1220 + fc;
+                    la.tile_counter = db->d_counters + AVK_CTR_LANE_TILES + fc;
                     la.W = cl.W;
                     la.nm = 1u << cl.maxv;
                     la.ed_max = cl.ed_max;
@@ -1948,44 +1913,28 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                          * being solved while the other lane classes still run, not after them. */
                         AvkKernelArgs f3 = f;
                         f3.overflow_list = lists[3];
-                        f3.overflow_count = db->d_counters + 1104;
+                        f3.overflow_count = db->d_counters + AVK_CTR_HB3_COUNT;
                         hipStream_t es = lstream[li]; /* where the launch for the handed-back regions goes */
                         launch_lane_class(ctx, grid, lds, lstream[li], f3, la);
                         AVK_HIP(ctx, hipGetLastError());
                         /* the launch for what ALL lanes hand back waits for the lane launches only, not for the launch behind this class */
                         AVK_HIP(ctx, hipEventRecord(ljoin[li], lstream[li]));
                         ljoined[li] = true;
-                        AvkKernelArgs e = a;
+                        AvkKernelArgs e = avk_list_reader_args(a, lists[3], db->d_counters + AVK_CTR_HB3_COUNT, db->d_counters + AVK_CTR_HB3_CURSOR);
                         e.pass_tier = 2;
-                        e.work_list = lists[3];
-                        e.n_work_dev = db->d_counters + 1104;
-                        e.work_base = 0;
-                        e.n_work = 0;
-                        e.work_counter = db->d_counters + 1120;
-                        e.static_pct = 0;
-                        e.n_shards = 1;
-                        e.claim = 1;
-                        e.esc_bytes = 0;
-                        e.esc_enabled = 0;
                         e.high_priority = 0;
-                        e.extra_counter = nullptr;
-                        e.extra_n = 0;
-                        e.overflow_list = nullptr;
-                        e.overflow_count = nullptr;
                         e.hbm_ws = ctx->d_ws + (size_t)(n_waves + hbm_solo_max * waves_per_block) * (size_t)ws_bytes;
-                        e.big_ws = ctx->d_big;
-                        e.big_busy = db->d_counters + 1088;
-                        e.big_slots = big_slots;
+                        avk_big_slice_args(e, ctx->d_big, db->d_counters, big_slots);
                         uint32_t eb = hbm_blocks < hbm_early_max ? hbm_blocks : hbm_early_max;
                         if (use_wide) { /* large searches on small windows: avk_wide.inl first, the HBM-tier launch takes what is left */
                             AvkKernelArgs w = e;
-                            w.work_counter = db->d_counters + 1248;
+                            w.work_counter = db->d_counters + AVK_CTR_WIDE_HB3_CURSOR;
                             w.overflow_list = db->d_overflow6;
-                            w.overflow_count = db->d_counters + 1252;
+                            w.overflow_count = db->d_counters + AVK_CTR_WIDE_HB3_LEFT;
                             hipLaunchKernelGGL(avk_wide_kernel_lazy, dim3((uint32_t)ctx->wide_lazy_blocks), dim3(64), (size_t)ctx->wide_lds_bytes, es, w, wa);
                             AVK_HIP(ctx, hipGetLastError());
                             e.work_list = db->d_overflow6;
-                            e.n_work_dev = db->d_counters + 1252;
+                            e.n_work_dev = db->d_counters + AVK_CTR_WIDE_HB3_LEFT;
                         }
                         e.n_waves = eb * waves_per_block;
                         hipLaunchKernelGGL(avk_region_kernel_hbm_lazy, dim3(eb), dim3(256), 0, es, e);
@@ -2001,7 +1950,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                     if (head_tiles > 0 && head_tiles < la.n_tiles && (uint32_t)ctx->lane_head_width < (1u << la.lanes_log2)) {
                         avk::lane::LaneArgs hd = la;
                         hd.n_tiles = head_tiles;
-                        hd.tile_counter = db->d_counters + 1230 + fc;
+                        hd.tile_counter = db->d_counters + AVK_CTR_HEAD_TILES + fc;
                         hd.lanes_log2 = head_width_log2(ctx, db->plan.n_fast_heavy[fc]);
                         hd.pool = pool_heavy;
                         uint32_t hgrid = 0;
@@ -2013,7 +1962,8 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                         }
                         AvkKernelArgs fh = f;
                         HbSeg hseg = {nullptr, nullptr, nullptr};
-                        const bool staged = chains && hb_heads < 8 && (cl.maxv == 2 || getenv("AVK_STAGE_ALL_HEADS")); /* (the one-call heads are short: their hand-backs wait for the chain's end) */
+                        static_assert(sizeof(ctx->ev_hb) / sizeof(ctx->ev_hb[0]) == AVK_CTR_HB_HEADS, "an event per staged head");
+                        const bool staged = chains && hb_heads < (int)AVK_CTR_HB_HEADS && (cl.maxv == 2 || getenv("AVK_STAGE_ALL_HEADS")); /* (the one-call heads are short: their hand-backs wait for the chain's end) */
                         if (staged) {
                             hseg = hb_new(head_tiles * 64u);
                             fh.overflow_list = hseg.list, fh.overflow_count = hseg.count;
@@ -2085,24 +2035,24 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
                 }
                 AvkKernelArgs d = a;
                 d.work_list = chains ? db->d_overflow7 : lists[2];
-                d.n_work_dev = chains ? db->d_counters + 1264 : db->d_counters + 1024 + 32;
+                d.n_work_dev = db->d_counters + (chains ? AVK_CTR_WIDE_LANES_LEFT : avk_ctr_overflow_count(AVK_CTR_DEFERRED_LIST));
                 d.work_base = 0;
                 d.n_work = 0;
-                d.work_counter = db->d_counters + 768;
+                d.work_counter = db->d_counters + AVK_CTR_DEFERRED_CURSORS;
                 if (!chains && use_wide && ctx->wide_lane_handbacks) { /* small windows, whatever made the lanes give up: avk_wide.inl first, the LDS launch takes what is left */
                     AvkKernelArgs w = d;
-                    w.work_counter = db->d_counters + 1260;
+                    w.work_counter = db->d_counters + AVK_CTR_WIDE_LANES_CURSOR;
                     w.overflow_list = db->d_overflow7;
-                    w.overflow_count = db->d_counters + 1264;
+                    w.overflow_count = db->d_counters + AVK_CTR_WIDE_LANES_LEFT;
                     hipLaunchKernelGGL(avk_wide_kernel_lazy, dim3((uint32_t)ctx->wide_lazy_blocks), dim3(64), (size_t)ctx->wide_lds_bytes, ds, w, wa);
                     AVK_HIP(ctx, hipGetLastError());
                     d.work_list = db->d_overflow7;
-                    d.n_work_dev = db->d_counters + 1264;
+                    d.n_work_dev = db->d_counters + AVK_CTR_WIDE_LANES_LEFT;
                 }
                 uint32_t dblocks = bulk_unfit < (uint32_t)ctx->n_cus ? bulk_unfit : (uint32_t)ctx->n_cus; /* one workgroup per CU: the list is short */
                 d.n_waves = dblocks * waves_per_block;
                 d.overflow_list = lists[1];
-                d.overflow_count = db->d_counters + 1024 + 16;
+                d.overflow_count = db->d_counters + avk_ctr_overflow_count(1);
                 if (chains) {
                     chain_d = d;
                     chain_dblocks = dblocks;
@@ -2122,12 +2072,10 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
             hipLaunchKernelGGL(avk_region_kernel_lds, dim3(b2), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds2_bytes_per_wave, ctx->stream, a);
         } else if (t == 2) {
             a.hbm_ws = ctx->d_ws;
-            a.big_ws = ctx->d_big;
-            a.big_busy = db->d_counters + 1088;
-            a.big_slots = big_slots;
+            avk_big_slice_args(a, ctx->d_big, db->d_counters, big_slots);
             a.n_waves = hbm_blocks * waves_per_block;
             if (hbm_solo_pending && hbm_shared) { /* class C records the solo launch has not started yet: every wave of this launch helps (same ticket counter) */
-                a.extra_counter = db->d_counters + 1076;
+                a.extra_counter = db->d_counters + AVK_CTR_HBM_SOLO_TICKET;
                 a.extra_base = hbm_shared_base;
                 a.extra_n = db->plan.n_hbm - hbm_shared_base;
             }
@@ -2145,7 +2093,7 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
 
         if (t != last) {
             list = lists[nlist];
-            count = db->d_counters + 1024 + 16 * nlist;
+            count = db->d_counters + avk_ctr_overflow_count((uint32_t)nlist);
             nlist += 1;
         }
     }
@@ -2155,27 +2103,11 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
     if (deferred_pending) { /* the lane streams (lane launches, then the handed-back regions) join here; what even the escalation could not hold */
         if (!chains) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_lane_done, 0));
         if (early_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_lane_early, 0));
-        AvkKernelArgs h = a;
+        AvkKernelArgs h = avk_list_reader_args(a, lists[1], db->d_counters + avk_ctr_overflow_count(1), db->d_counters + AVK_CTR_LAST_CURSOR);
         h.pass_tier = 2;
-        h.work_list = lists[1];
-        h.n_work_dev = db->d_counters + 1024 + 16;
-        h.work_base = 0;
-        h.n_work = 0;
-        h.work_counter = db->d_counters + 256; /* the claim counters of the (unused) tier-1 launch */
-        h.static_pct = 0;
-        h.n_shards = 1;
-        h.claim = 1;
-        h.esc_bytes = 0;
-        h.esc_enabled = 0;
         h.high_priority = 0;
-        h.extra_counter = nullptr;
-        h.extra_n = 0;
-        h.overflow_list = nullptr;
-        h.overflow_count = nullptr;
         h.hbm_ws = ctx->d_ws;
-        h.big_ws = ctx->d_big;
-        h.big_busy = db->d_counters + 1088;
-        h.big_slots = big_slots;
+        avk_big_slice_args(h, ctx->d_big, db->d_counters, big_slots);
         const uint32_t hb = hbm_blocks < 64 ? hbm_blocks : 64;
         h.n_waves = hb * waves_per_block;
         hipLaunchKernelGGL(avk_region_kernel_hbm_lazy, dim3(hb), dim3(256), 0, ctx->stream, h);
@@ -3092,7 +3024,6 @@ static void warm_kernels(int device) {
                                                                                                           would predict, and this context allocate, tens of GB of slices) */
     for (const char *o : opts) (void)avk_ctx_set_option(t, o, 0);
     (void)avk_ctx_set_option(t, "big_ws_bytes", 8 << 20);
-    (void)avk_ctx_set_option(t, "big_waves", 4);
     (void)avk_ctx_set_option(t, "ws_bytes_per_wave", 256 << 10); /* (the warm-up's regions are tiny: 0.4 GB of slices instead of 1.7 — what this context frees at its end is
                                                                    memory the caller's first call may be handed next, and has to wait for while it is scrubbed) */
     (void)avk_ctx_set_option(t, "class_c_nodes_x2", 1000); /* every region the lanes do not take is planned as class C: the wide kernel, the HBM launches */

@@ -30,6 +30,7 @@
 #define AVK_SOLVER_INL
 
 #include "avk_dev_types.h"
+#include "avk_counters.h"
 #include "avk_wave.h"
 #include "avk_devpack.inl" /* dp_region_record: region records of device-packed batches are written on demand */
 
@@ -2359,7 +2360,7 @@ template <bool PASS_LDS, bool LAZY = false, bool TEAM = false> AVK_DEV void regi
                     if (sh >= n_shards) sh -= n_shards;
                     const u32 lo = sh * shard_len < n_dyn ? sh * shard_len : n_dyn;
                     const u32 hi = lo + shard_len < n_dyn ? lo + shard_len : n_dyn;
-                    u32 *ctr = a.work_counter + 32u * sh;
+                    u32 *ctr = a.work_counter + AVK_CTR_SHARD_STRIDE * sh;
                     u32 b = 0xFFFFFFFFu;
                     if (lane == 0) {
                         const u32 seen = *(volatile u32 *)ctr;
@@ -2416,7 +2417,7 @@ template <bool PASS_LDS, bool LAZY = false, bool TEAM = false> AVK_DEV void regi
         c.team_scratch_bytes = TEAM ? ws_bytes : 0;
         c.team_mode = a.team;
         c.team_waves = TEAM && team && a.team == 1 ? 4u : 1u;
-        c.team_dbg = a.work_counter ? a.work_counter + 17 : (u32 *)0; /* (the team launch's claim counter is word 1256 of the batch's counters: these are 1273..1279) */
+        c.team_dbg = a.work_counter ? a.work_counter + AVK_CTR_TEAM_PROGRESS_REL : (u32 *)0; /* (only a team writes them: behind the team launch's cursor these are AVK_CTR_TEAM_PROGRESS, avk_counters.h) */
 #ifdef AVK_PHASE_TIMING
         for (int k = 0; k < 16; ++k) c.tphase[k] = 0;
         const u64 t_region0 = avk_clock();

@@ -212,6 +212,7 @@ static void run_wave(Wave *w, void (*fn)(void *, int), void *arg) {
 } // namespace avk_emu
 
 #include "../../aardvark_amd/csrc/avk_pack.h"
+#include "../../aardvark_amd/csrc/avk_counters.h"
 #include "../../aardvark_amd/csrc/avk_solver.inl"
 #ifdef AVK_LANE_STATS
 namespace avk { namespace lane { uint64_t g_lane_stats[32]; int g_lane_phase; uint32_t *g_lane_work; uint32_t *g_lane_comp; } }
@@ -484,11 +485,12 @@ extern "C" {
 /* Mirrors avk_compare_batch on emulated wavefronts.  lds_bytes / lds2_bytes / ws_bytes / big_ws_bytes
  * are the per-wave workspace sizes of the four tiers (0 disables a tier), *_ed_cap the wavefront caps
  * of the LDS tiers, n_waves the number of persistent waves, threads the OS threads running them.
- * tier_counts[5] receives how many regions each tier finished, then the capacity failures. */
+ * tier_counts[5] receives how many regions each tier finished, then the capacity failures.
+ * n_big_slots: the shared big slices the HBM-tier launches escalate into (run_internal: 8, or 64 with large adaptive slices). */
 static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *const *refs, const uint64_t *ref_lens, uint32_t n_contigs,
                       const avk_compare_config *cfg, avk_result_batch *out, uint64_t lds_bytes, uint32_t lds_ed_cap, uint64_t lds2_bytes,
                       uint32_t lds2_ed_cap, uint64_t ws_bytes, uint64_t big_ws_bytes, uint32_t n_waves, int threads, uint64_t *tier_counts,
-                      uint32_t solo_min_variants, uint32_t lds2_overflow_pass, uint32_t lds_escalation) {
+                      uint32_t solo_min_variants, uint32_t lds2_overflow_pass, uint32_t lds_escalation, uint32_t n_big_slots = 2) {
     std::vector<uint64_t> base(n_contigs), lens(n_contigs);
     uint64_t total = 0;
     for (uint32_t c = 0; c < n_contigs; ++c) {
@@ -522,7 +524,7 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
     std::vector<uint32_t> gm(out->group_metrics ? n * AVK_N_GROUPS * AVK_N_FIELDS : 0);
     std::vector<uint64_t> partials((size_t)AVK_TALLY_STRIDE * AVK_TALLY_COPIES, 0), tally(AVK_TALLY_STRIDE, 0);
     std::vector<uint32_t> lists[4] = {std::vector<uint32_t>(n + 1), std::vector<uint32_t>(n + 1), std::vector<uint32_t>(n + 1), std::vector<uint32_t>(n + 1)};
-    std::vector<uint32_t> counters_v(1280, 0);
+    std::vector<uint32_t> counters_v(AVK_N_COUNTERS, 0);
     uint32_t *counters = counters_v.data();
 
     AvkKernelArgs a;
@@ -694,8 +696,9 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
     for (int t = 0; t < 4; ++t)
         if (launch[t]) last = t;
     if (last < 0) return AVK_E_ARG;
-    const uint32_t big_slots = use[2] && use[3] ? 2u : 0u;
+    const uint32_t big_slots = use[2] && use[3] ? (n_big_slots < AVK_CTR_BIG_BUSY_LEN ? n_big_slots : AVK_CTR_BIG_BUSY_LEN) : 0u;
     std::vector<uint8_t> big_slices(big_slots ? (size_t)big_slots * big_ws_bytes : 0);
+    uint8_t *const big_ws = big_slots ? big_slices.data() : nullptr;
     /* work order and solo waves as in upload_internal / run_internal (aardvark_amd/csrc/avk_host.hip) */
     std::vector<uint32_t> order;
     avk::WorkPlan plan;
@@ -735,7 +738,7 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
             fast = avk::build_fast_records(pb, order, plan, word_base, n_tiles);
         AvkKernelArgs f = a;
         f.overflow_list = lists[2].data(); /* the DEFERRED list: an LDS pass of the wave-per-region code after the bulk */
-        f.overflow_count = counters + 1024 + 32;
+        f.overflow_count = counters + avk_ctr_overflow_count(AVK_CTR_DEFERRED_LIST);
         for (int fc = AVK_FAST_CLASSES - 1; fc >= 0; --fc) {
             if (!n_tiles[fc]) continue;
             if (fc == AVK_FAST_PAIR && mode == 0 && g_lane_pairs) { /* run_internal: the table (ensure_pair_table), then the lookups */
@@ -769,7 +772,7 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
                     avk_emu::run_wave(&w, lane_kernel_main, &t);
                 }
                 pr::PairArgs pa;
-                pa.recs = fast.data() + word_base[fc], pa.n_tiles = n_tiles[fc], pa.gen_base = plan.fast_base[fc], pa.tab = &tab, pa.tile_counter = counters + 1220 + fc;
+                pa.recs = fast.data() + word_base[fc], pa.n_tiles = n_tiles[fc], pa.gen_base = plan.fast_base[fc], pa.tab = &tab, pa.tile_counter = counters + AVK_CTR_LANE_TILES + fc;
                 const int nthr = threads < 1 ? 1 : threads;
                 std::vector<uint64_t> sums((size_t)nthr * AVK_TALLY_STRIDE, 0);
                 auto worker = [&](int tid) {
@@ -794,7 +797,7 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
             la.recs = fast.data() + word_base[fc];
             la.rec_words = AVK_FAST_WORDS_OF(cl.maxv);
             la.n_tiles = n_tiles[fc];
-            la.tile_counter = counters + 1220 + fc;
+            la.tile_counter = counters + AVK_CTR_LANE_TILES + fc;
             la.W = cl.W;
             la.nm = 1u << cl.maxv;
             la.ed_max = cl.ed_max;
@@ -807,7 +810,7 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
             la.pool = g_lane_pool < 0 ? (cl.maxv > 2 ? pool_heavy : 0u) : (uint32_t)g_lane_pool;
             AvkKernelArgs f3 = f; /* run_internal: the three-call class hands back to a list of its own, solved by an HBM-tier launch right behind it */
             f3.overflow_list = lists[3].data();
-            f3.overflow_count = counters + 1104;
+            f3.overflow_count = counters + AVK_CTR_HB3_COUNT;
             auto launch = [&](const avk::lane::LaneArgs &la) {
                 const bool quad = g_lane_quad && la.lanes_log2 <= 4; /* run_internal's rule */
                 const uint32_t rows = quad ? avk::quad::quad_rows(la.W, la.nm, la.ed_max, la.qcap, la.pool) : avk::lane::lane_rows(la.W, la.nm, la.ed_max, la.qcap, la.pool);
@@ -852,7 +855,7 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
             if (head_tiles > 0 && head_tiles < la.n_tiles && g_lane_head_width < (1u << la.lanes_log2)) {
                 avk::lane::LaneArgs hd = la;
                 hd.n_tiles = head_tiles;
-                hd.tile_counter = counters + 1230 + fc;
+                hd.tile_counter = counters + AVK_CTR_HEAD_TILES + fc;
                 hd.lanes_log2 = g_lane_head_width <= 4 ? 2u : (g_lane_head_width <= 8 ? 3u : (g_lane_head_width <= 16 ? 4u : 5u));
                 hd.pool = pool_heavy;
                 launch(hd);
@@ -861,34 +864,21 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
                 la.gen_base += head_tiles * 64u;
             }
             launch(la);
-            if (cl.maxv > 2 && counters[1104]) { /* run_internal: the HBM-tier launch behind the three-call class */
+            if (cl.maxv > 2 && counters[AVK_CTR_HB3_COUNT]) { /* run_internal: the HBM-tier launch behind the three-call class */
                 AvkKernelArgs keep = a;
                 a.pass_tier = 2;
                 a.work_list = lists[3].data();
-                a.n_work_dev = counters + 1104;
+                a.n_work_dev = counters + AVK_CTR_HB3_COUNT;
                 if (use_wide) { /* ... and the launch of avk_wide.inl ahead of it */
                     AvkKernelArgs w = a;
-                    w.work_base = 0, w.n_work = 0, w.work_counter = counters + 1248, w.overflow_list = wide_left_3.data(), w.overflow_count = counters + 1252;
+                    w.work_base = 0, w.n_work = 0, w.work_counter = counters + AVK_CTR_WIDE_HB3_CURSOR, w.overflow_list = wide_left_3.data(), w.overflow_count = counters + AVK_CTR_WIDE_HB3_LEFT;
                     run_wide(w, n_waves ? n_waves : 1);
                     a.work_list = wide_left_3.data();
-                    a.n_work_dev = counters + 1252;
+                    a.n_work_dev = counters + AVK_CTR_WIDE_HB3_LEFT;
                 }
-                a.work_base = 0;
-                a.n_work = 0;
-                a.work_counter = counters + 1120;
-                a.static_pct = 0;
-                a.n_shards = 1;
-                a.claim = 1;
-                a.esc_bytes = 0;
-                a.esc_enabled = 0;
+                a = avk_list_reader_args(a, a.work_list, a.n_work_dev, counters + AVK_CTR_HB3_CURSOR);
                 a.high_priority = 0;
-                a.extra_counter = nullptr;
-                a.extra_n = 0;
-                a.overflow_list = nullptr;
-                a.overflow_count = nullptr;
-                a.big_ws = big_slots ? big_slices.data() : nullptr;
-                a.big_busy = counters + 1088;
-                a.big_slots = big_slots;
+                avk_big_slice_args(a, big_ws, counters, big_slots);
                 run_pass(n_waves ? n_waves : 1, ws_bytes, 0);
                 a = keep;
             }
@@ -911,10 +901,10 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
         a.static_pct = AVK_STATIC_PCT;
         a.n_shards = 8;
         a.claim = AVK_CLAIM;
-        a.work_counter = counters + 256 * t;
+        a.work_counter = counters + avk_ctr_tier_cursors((uint32_t)t);
         if (t != last) {
             a.overflow_list = lists[nlist].data();
-            a.overflow_count = counters + 1024 + 16 * nlist;
+            a.overflow_count = counters + avk_ctr_overflow_count((uint32_t)nlist);
         } else {
             a.overflow_list = nullptr;
             a.overflow_count = nullptr;
@@ -936,45 +926,38 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
                     AvkKernelArgs keep = a;
                     if (use_wide) { /* run_internal: class C through avk_wide.inl first, the HBM solo launch takes what is left */
                         AvkKernelArgs w = a;
-                        w.work_list = nullptr, w.n_work_dev = nullptr, w.work_base = 0, w.n_work = n_c, w.work_counter = counters + 1240;
-                        w.overflow_list = wide_left_c.data(), w.overflow_count = counters + 1244;
+                        w.work_list = nullptr, w.n_work_dev = nullptr, w.work_base = 0, w.n_work = n_c, w.work_counter = counters + AVK_CTR_WIDE_C_CURSOR;
+                        w.overflow_list = wide_left_c.data(), w.overflow_count = counters + AVK_CTR_WIDE_C_LEFT;
                         run_wide(w, n_waves ? n_waves : 1, 1);
                         { /* ... beside the HBM-tier launch for the records that are not the wide kernel's by what they say themselves (AvkKernelArgs::only_not_wide) */
                             AvkKernelArgs keep2 = a;
-                            a.pass_tier = 2, a.only_not_wide = 1, a.work_list = nullptr, a.n_work_dev = nullptr, a.work_base = 0, a.n_work = n_c, a.work_counter = counters + 1256;
-                            a.static_pct = 0, a.n_shards = 1, a.claim = 4, a.high_priority = 1, a.overflow_list = nullptr, a.overflow_count = nullptr;
-                            a.big_ws = big_slots ? big_slices.data() : nullptr, a.big_busy = counters + 1088, a.big_slots = big_slots;
+                            a = avk_list_reader_args(a, nullptr, nullptr, counters + AVK_CTR_TEAM_CURSOR); /* (no list here: the whole class in claims of four, the launch skips the wide kernel's records) */
+                            a.n_work = n_c, a.claim = 4, a.only_not_wide = 1;
+                            a.pass_tier = 2, a.high_priority = 1;
+                            avk_big_slice_args(a, big_ws, counters, big_slots);
                             run_pass(n_waves / 4 ? n_waves / 4 : 1, ws_bytes, 0);
                             a = keep2;
                         }
                         a.work_list = wide_left_c.data();
-                        a.n_work_dev = counters + 1244;
+                        a.n_work_dev = counters + AVK_CTR_WIDE_C_LEFT;
                         if (g_wide_lds_bytes < 64u * 1024u) { /* run_internal: what it handed over once more with the LDS of a whole workgroup (option wide_retry_lds_bytes) */
                             AvkKernelArgs w2 = w;
-                            w2.work_list = wide_left_c.data(), w2.n_work_dev = counters + 1244, w2.work_base = 0, w2.n_work = 0, w2.work_counter = counters + 1268;
-                            w2.overflow_list = wide_left_c2.data(), w2.overflow_count = counters + 1272;
+                            w2.work_list = wide_left_c.data(), w2.n_work_dev = counters + AVK_CTR_WIDE_C_LEFT, w2.work_base = 0, w2.n_work = 0, w2.work_counter = counters + AVK_CTR_WIDE_RETRY_CURSOR;
+                            w2.overflow_list = wide_left_c2.data(), w2.overflow_count = counters + AVK_CTR_WIDE_RETRY_LEFT;
                             run_wide(w2, 2, 0, 64u * 1024u);
                             a.work_list = wide_left_c2.data();
-                            a.n_work_dev = counters + 1272;
+                            a.n_work_dev = counters + AVK_CTR_WIDE_RETRY_LEFT;
                         }
                         hbm_shared = 0;
                     }
-                    a.pass_tier = 2;
-                    a.work_base = 0;
+                    a = avk_list_reader_args(a, a.work_list, a.n_work_dev, counters + AVK_CTR_HBM_SOLO_TICKET); /* (what the wide launches left, or the class's records themselves) */
                     a.n_work = n_c;
-                    a.work_counter = counters + 1076;
-                    a.static_pct = 0;
-                    a.n_shards = 1;
-                    a.claim = 1;
+                    a.pass_tier = 2;
                     a.high_priority = 1;
-                    a.big_ws = big_slots ? big_slices.data() : nullptr;
-                    a.big_busy = counters + 1088;
-                    a.big_slots = big_slots;
-                    a.overflow_list = nullptr;
-                    a.overflow_count = nullptr;
+                    avk_big_slice_args(a, big_ws, counters, big_slots);
                     if (!big_slots && launch[3]) {
                         a.overflow_list = lists[launch[1] ? 2 : 1].data();
-                        a.overflow_count = counters + 1024 + 16 * (launch[1] ? 2 : 1);
+                        a.overflow_count = counters + avk_ctr_overflow_count(launch[1] ? 2 : 1);
                     }
                     run_pass(n_waves / 2 ? n_waves / 2 : 1, ws_bytes, 0);
                     a = keep;
@@ -987,14 +970,14 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
                     a_solo.pass_tier = 1;
                     a_solo.work_base = n_c;
                     a_solo.n_work = solo;
-                    a_solo.work_counter = counters + 1072;
+                    a_solo.work_counter = counters + AVK_CTR_LDS_SOLO_CURSOR;
                     a_solo.static_pct = 0;
                     a_solo.n_shards = 1;
                     a_solo.claim = 1;
                     a_solo.n_waves = solo;
                     a_solo.high_priority = 1;
                     a_solo.overflow_list = later ? lists[solo_list].data() : nullptr;
-                    a_solo.overflow_count = later ? counters + 1024 + 16 * solo_list : nullptr;
+                    a_solo.overflow_count = later ? counters + avk_ctr_overflow_count((uint32_t)solo_list) : nullptr;
                 }
                 a.work_base = n_c + solo;
                 a.n_work = (uint32_t)n - n_fast - n_c - solo;
@@ -1004,22 +987,22 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
                     a.esc_enabled = lds_escalation ? 1u : 0u;
                 }
                 run_pass(n_waves ? n_waves : 1, 0, lds_bytes, solo);
-                if (use_fast && counters[1024 + 32]) { /* what the lanes handed over (run_internal: the deferred LDS launch) */
+                if (use_fast && counters[avk_ctr_overflow_count(AVK_CTR_DEFERRED_LIST)]) { /* what the lanes handed over (run_internal: the deferred LDS launch) */
                     AvkKernelArgs keep = a;
                     a.work_list = lists[2].data();
-                    a.n_work_dev = counters + 1024 + 32;
+                    a.n_work_dev = counters + avk_ctr_overflow_count(AVK_CTR_DEFERRED_LIST);
                     a.work_base = 0;
                     a.n_work = 0;
                     if (use_wide) { /* run_internal: avk_wide.inl first */
                         AvkKernelArgs w = a;
-                        w.work_counter = counters + 1260, w.overflow_list = wide_left_l.data(), w.overflow_count = counters + 1264;
+                        w.work_counter = counters + AVK_CTR_WIDE_LANES_CURSOR, w.overflow_list = wide_left_l.data(), w.overflow_count = counters + AVK_CTR_WIDE_LANES_LEFT;
                         run_wide(w, n_waves ? n_waves : 1);
                         a.work_list = wide_left_l.data();
-                        a.n_work_dev = counters + 1264;
+                        a.n_work_dev = counters + AVK_CTR_WIDE_LANES_LEFT;
                     }
-                    a.work_counter = counters + 768;
+                    a.work_counter = counters + AVK_CTR_DEFERRED_CURSORS;
                     a.overflow_list = lists[1].data(); /* its own overflow list: one more HBM pass at the very end */
-                    a.overflow_count = counters + 1024 + 16;
+                    a.overflow_count = counters + avk_ctr_overflow_count(1);
                     run_pass(n_waves ? n_waves : 1, 0, lds_bytes, 0);
                     a = keep;
                 }
@@ -1029,11 +1012,9 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
             }
             else if (t == 1) run_pass(n_waves ? n_waves : 1, 0, lds2_bytes);
             else if (t == 2) {
-                a.big_ws = big_slots ? big_slices.data() : nullptr;
-                a.big_busy = counters + 1088;
-                a.big_slots = big_slots;
+                avk_big_slice_args(a, big_ws, counters, big_slots);
                 if (hbm_shared) { /* run_internal: the class C list is shared with the HBM solo launch through its ticket counter */
-                    a.extra_counter = counters + 1076;
+                    a.extra_counter = counters + AVK_CTR_HBM_SOLO_TICKET;
                     a.extra_base = 0;
                     a.extra_n = hbm_shared;
                 }
@@ -1045,31 +1026,16 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
         }
         if (t != last) {
             list = lists[nlist].data();
-            count = counters + 1024 + 16 * nlist;
+            count = counters + avk_ctr_overflow_count((uint32_t)nlist);
             nlist += 1;
         }
     }
 
-    if (use_fast && counters[1024 + 16]) { /* run_internal: what the handed-back regions' LDS pass could not hold */
+    if (use_fast && counters[avk_ctr_overflow_count(1)]) { /* run_internal: what the handed-back regions' LDS pass could not hold */
+        a = avk_list_reader_args(a, lists[1].data(), counters + avk_ctr_overflow_count(1), counters + AVK_CTR_LAST_CURSOR);
         a.pass_tier = 2;
-        a.work_list = lists[1].data();
-        a.n_work_dev = counters + 1024 + 16;
-        a.work_base = 0;
-        a.n_work = 0;
-        a.work_counter = counters + 256;
-        a.static_pct = 0;
-        a.n_shards = 1;
-        a.claim = 1;
-        a.esc_bytes = 0;
-        a.esc_enabled = 0;
         a.high_priority = 0;
-        a.extra_counter = nullptr;
-        a.extra_n = 0;
-        a.overflow_list = nullptr;
-        a.overflow_count = nullptr;
-        a.big_ws = big_slots ? big_slices.data() : nullptr;
-        a.big_busy = counters + 1088;
-        a.big_slots = big_slots;
+        avk_big_slice_args(a, big_ws, counters, big_slots);
         run_pass(n_waves ? n_waves : 1, ws_bytes, 0);
     }
     for (int c = 0; c < AVK_TALLY_COPIES; ++c) /* avk_tally_reduce */
@@ -1396,9 +1362,9 @@ void emu_set_lane_width_three(int three) { g_lane_width_log2[2] = width_log2(thr
 int emu_compare_batch(const avk_region_batch *batch, const uint8_t *const *refs, const uint64_t *ref_lens, uint32_t n_contigs,
                       const avk_compare_config *cfg, avk_result_batch *out, uint64_t lds_bytes, uint32_t lds_ed_cap, uint64_t lds2_bytes,
                       uint32_t lds2_ed_cap, uint64_t ws_bytes, uint64_t big_ws_bytes, uint32_t n_waves, int threads, uint64_t *tier_counts,
-                      uint32_t solo_min_variants, uint32_t lds2_overflow_pass, uint32_t lds_escalation) {
+                      uint32_t solo_min_variants, uint32_t lds2_overflow_pass, uint32_t lds_escalation, uint32_t n_big_slots) {
     return emu_run(0, batch, refs, ref_lens, n_contigs, cfg, out, lds_bytes, lds_ed_cap, lds2_bytes, lds2_ed_cap, ws_bytes, big_ws_bytes, n_waves,
-                   threads, tier_counts, solo_min_variants, lds2_overflow_pass, lds_escalation);
+                   threads, tier_counts, solo_min_variants, lds2_overflow_pass, lds_escalation, n_big_slots);
 }
 
 /* avk_optimize_pairs_batch on emulated wavefronts (default tier sizes) */

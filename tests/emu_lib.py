@@ -21,7 +21,7 @@ def load():
         lib = C.CDLL(os.path.join(EMU_DIR, "libavk_emu.so"))
         lib.emu_compare_batch.argtypes = [C.POINTER(AvkRegionBatch), C.POINTER(u8p), u64p, C.c_uint32, C.POINTER(AvkCompareConfig),
                                           C.POINTER(AvkResultBatch), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
-                                          C.c_uint32, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_uint32]
+                                          C.c_uint32, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.emu_optimize_pairs_batch.argtypes = [C.POINTER(AvkRegionBatch), C.POINTER(u8p), u64p, C.c_uint32, C.c_uint32,
                                                  C.POINTER(C.c_int32), u8p, C.c_int]
         lib.emu_set_lane_kernel.argtypes = [C.c_int]
@@ -92,11 +92,12 @@ def esc_lower(lst, key):
 def compare_batch(batch, contigs, max_branch_factor=50, sequences=False, exact_shortcut=False,
                   lds_bytes=10 * 1024, lds_ed_cap=48, lds2_bytes=40 * 1024, lds2_ed_cap=48, ws_bytes=1 << 20, big_ws_bytes=64 << 20,
                   n_waves=8, threads=8, solo_min_variants=5, lds2_overflow_pass=0, lds_escalation=1, group_metrics=True, lane_kernel=True, bp_groups=False,
-                  wide_kernel=True, wide_lds_bytes=16 * 1024, class_c_all=False, packed=False, lane_pool=-1, lane_quad=True):
+                  wide_kernel=True, wide_lds_bytes=16 * 1024, class_c_all=False, packed=False, lane_pool=-1, lane_quad=True, big_slots=2):
     """lane_kernel: small regions go through the lane-per-region code (avk_lane.inl), the rest through the wave-per-region code, as
     avk_compare_resident does; False = everything through the wave-per-region code.  res.lane_solved = regions the lane code finished.
     wide_kernel: class C and what the three-call lane class hands back go through the wave-cooperative code of avk_wide.inl first
-    (res.wide_solved = regions it finished); class_c_all = every region outside the lane classes is planned as class C."""
+    (res.wide_solved = regions it finished); class_c_all = every region outside the lane classes is planned as class C.
+    big_slots: the shared big slices an HBM-tier wave escalates into when its own slice (ws_bytes) overflows."""
     lib = load()
     lib.emu_set_lane_kernel(1 if lane_kernel else 0)
     lib.emu_set_wide_kernel(1 if wide_kernel else 0)
@@ -112,7 +113,7 @@ def compare_batch(batch, contigs, max_branch_factor=50, sequences=False, exact_s
     cb, ro = batch.c_struct(), res.c_struct()
     tiers = (C.c_uint64 * 5)()
     rc = lib.emu_compare_batch(C.byref(cb), cs.ptrs, cs.lens, cs.n, C.byref(cfg), C.byref(ro), lds_bytes, lds_ed_cap, lds2_bytes, lds2_ed_cap,
-                               ws_bytes, big_ws_bytes, n_waves, threads, tiers, solo_min_variants, lds2_overflow_pass, lds_escalation)
+                               ws_bytes, big_ws_bytes, n_waves, threads, tiers, solo_min_variants, lds2_overflow_pass, lds_escalation, big_slots)
     assert rc == 0
     res.tier_counts = [int(x) for x in tiers]
     res.lane_solved = int(lib.emu_last_lane_solved())

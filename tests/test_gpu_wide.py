@@ -120,3 +120,38 @@ def test_small_slice_shares_do_not_overlap(oracle):
             assert ctx.last_wide_solved() > 5000 and ctx.last_tier_counts()[2] > 1000
     finally:
         ctx.close()
+
+
+def test_lane_hand_backs_beside_sixty_four_shared_slices(oracle):
+    """A batch whose predicted per-wave slice exceeds the option (adaptive_ws: large windows) gets 64 shared big slices instead of 8, and their busy flags are
+    64 words of the step's device counters (AVK_CTR_BIG_BUSY, avk_counters.h).  The length of the three-call lane class's hand-back list and the cursor of the
+    launch that reads it once sat at flags 16 and 32: a wave that overflowed its own slice there could claim a list length as a slot.  Here both happen in one
+    step — the three-call class hands back (lane_node_cap 8) while long windows outgrow their slices — a few times on one context."""
+    import aardvark_amd
+    from aardvark_amd import CompareConfig, synth
+    contig, bed, truth, query = synth.contig_calls(5, 3_000_000, 3_800 / 3_000_000, seed_ref=905, seed_query=906, str_frac=0.15, multi_frac=0.05)
+    long_windows = synth.cluster_regions_v(contig, bed, truth, query, 1000)
+    contigs2, small = scenarios.fuzz_regions(411004, 20000, max_vars=9, span=(40, 200))  # (enough of them that the slice the packer picks for 98 % of class C is too small for some long windows)
+    small.contig_idx[:] = 1
+    contigs, batch = [contig, contigs2[0]], synth.concat_batches([long_windows, small])
+    want = oracle_lib.compare_batch(oracle, batch, contigs, threads=CPUS, group_metrics=False)
+    ctx = aardvark_amd.Context(0)
+    try:
+        for k, v in dict(lane_min_regions=0, lane_min_batch=0, lane_node_cap=8, emit_group_metrics=0,
+                         ws_bytes_per_wave=1 << 18,  # (the packer predicts 1 MB or more for the long windows: the batch's slices are its, and the step takes 64 shared ones)
+                         big_ws_bytes=64 << 20).items():
+            ctx.set_option(k, v)
+        ctx.upload_reference(contigs)
+        rb = ctx.upload(batch)
+        lanes = ctx.work_order(rb, want_order=False)[1]["lanes"]
+        for _ in range(4):
+            ctx.compare_resident(rb, CompareConfig(enable_sequences=False))
+            got = ctx.download(rb, group_metrics=False)
+            assert got.diff(want) == []
+            tiers, handed_back = ctx.last_tier_counts(), lanes - ctx.last_lane_solved()
+            print("tiers %s, lane regions %d, handed back %d, wide %d" % (tiers, lanes, handed_back, ctx.last_wide_solved()))
+            # observed on the parent commit, every step: 13 regions in the shared slices, 2070 of the 4003 lane regions handed back, 11067 regions through avk_wide.inl
+            assert tiers[3] >= 8 and handed_back >= 1500 and ctx.last_wide_solved() >= 8000
+        rb.free()
+    finally:
+        ctx.close()

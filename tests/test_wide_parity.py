@@ -159,6 +159,28 @@ def test_hand_backs_of_the_three_call_lane_class(oracle):
         lib.emu_set_lane_node_cap(32)
 
 
+def test_hand_backs_beside_more_than_sixteen_shared_big_slices(oracle):
+    """The busy flags of the shared big slices and the words of the three-call class's hand-back list are separate ranges of the step's counters
+    (aardvark_amd/csrc/avk_counters.h): the list's length once sat where the flag of slice 16 is, so that a wave looking for a free slice could take an empty
+    list's length for one, and give it back as 0.  Long windows that outgrow small per-wave slices (40 waves, 40 shared slices) beside a three-call class that
+    hands back.  (The emulator runs its launches one after the other: this pins the wiring with many slices; the launches meet on the GPU, test_gpu_wide.py.)"""
+    lib = emu_lib.load()
+    contig, bed, truth, query = synth.contig_calls(5, 400_000, 600 / 400_000, seed_ref=905, seed_query=906, str_frac=0.15, multi_frac=0.05)
+    long_windows = synth.cluster_regions_v(contig, bed, truth, query, 1000)
+    contigs2, small = het_cluster_regions(61, 300, n_sites=(2, 3), drop=0.0)
+    small.contig_idx[:] = 1
+    contigs, batch = [contig, contigs2[0]], synth.concat_batches([long_windows, small])
+    want = oracle_lib.compare_batch(oracle, batch, contigs, threads=4)
+    lib.emu_set_lane_node_cap(8)
+    try:
+        got = emu_lib.compare_batch(batch, contigs, threads=THREADS, n_waves=40, ws_bytes=64 * 1024, big_slots=40)
+    finally:
+        lib.emu_set_lane_node_cap(32)
+    assert got.diff(want) == []
+    assert got.tier_counts[3] > 16 and got.tier_counts[2] > 0, got.tier_counts  # long windows in the shared slices, and in the waves' own
+    assert 10 < got.lane_solved < small.n_regions and got.wide_solved > 10       # the lanes handed regions back, the wide code took some
+
+
 def test_merge_pairs(oracle):
     """optimize_sequences(..)[0].is_exact_match() per pair (merge_solver.rs:137-143): pair batches have no class C, the wide code sees what the
     three-call lane class hands back"""
