@@ -493,6 +493,14 @@ class Context:
         self._check(self.lib.avk_last_wide_solved(self.handle, C.byref(out)))
         return int(out.value)
 
+    def last_region_launches(self):
+        """launches of the packer's region pass the last device-packed upload queued (avk_last_region_launches): 1, 2 when calls were left to the host's edit
+        distance; N + 1 (N + 2) on the chunked route of the option pack_chunks = N"""
+        out = C.c_uint64(0)
+        self.lib.avk_last_region_launches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self._check(self.lib.avk_last_region_launches(self.handle, C.byref(out)))
+        return int(out.value)
+
     def last_tier_counts(self):
         out = (C.c_uint64 * 5)()
         self._check(self.lib.avk_last_tier_counts(self.handle, out))

@@ -127,13 +127,14 @@ __global__ void __launch_bounds__(256) avk_dp_variant_kernel(dpk::DpArgs a) { dp
  * column-major block_sums[quantity][block]: no global atomics (56,000 waves adding to the one counter of the modal class took 1.3 ms of this kernel's 1.6) */
 #define AVK_DP_NS 4 /* scanned quantities: per-call output words, blob words, sequence bytes, compact BASEPAIR groups */
 #define AVK_DP_BS (AVK_DP_NS + AVK_FAST_CLASSES + avk::dp::DP_NEED_BUCKETS)
-__global__ void __launch_bounds__(256) avk_dp_region_kernel(dpk::DpArgs a, uint64_t *block_sums) {
+/* (block: the workgroup's 256 regions; n_blocks: the batch's workgroups, the stride of a column — the launches of the chunked route cover a part of them each) */
+__device__ inline void avk_dp_region_block(const dpk::DpArgs &a, uint64_t *block_sums, uint32_t block, uint32_t n_blocks) {
     __shared__ unsigned long long sums[AVK_DP_BS];
     if (threadIdx.x < AVK_DP_BS) sums[threadIdx.x] = 0;
     __syncthreads();
     uint32_t nc = 0, bw = 0, fc = 0, nb = 0xFFu, ng = 0;
     uint64_t sq = 0;
-    dpk::dp_region(a, (uint64_t)blockIdx.x * 256u + threadIdx.x, nc, bw, sq, fc, nb, ng);
+    dpk::dp_region(a, (uint64_t)block * 256u + threadIdx.x, nc, bw, sq, fc, nb, ng);
     if (__ballot(nb != 0xFFu)) /* class C regions: rare on a small-window genome */
         for (uint32_t c = 0; c < dpk::DP_NEED_BUCKETS; ++c) {
             const unsigned long long m = __ballot(nb == c);
@@ -156,7 +157,22 @@ __global__ void __launch_bounds__(256) avk_dp_region_kernel(dpk::DpArgs a, uint6
         if (sq_w) atomicAdd(&sums[2], sq_w);
     }
     __syncthreads();
-    if (threadIdx.x < AVK_DP_BS) block_sums[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = sums[threadIdx.x]; /* one column per quantity */
+    if (threadIdx.x < AVK_DP_BS) block_sums[(size_t)threadIdx.x * n_blocks + block] = sums[threadIdx.x]; /* one column per quantity */
+}
+__global__ void __launch_bounds__(256) avk_dp_region_kernel(dpk::DpArgs a, uint64_t *block_sums) { avk_dp_region_block(a, block_sums, blockIdx.x, gridDim.x); }
+
+/* The region pass of a packed batch whose copies are cut into groups (avk_pack_chunks.h): launch j runs behind the copies of group j and covers the blocks of the
+ * region ranges 0 .. j.  A workgroup runs here iff pc_launch_of_block names this launch — the same answer for all its lanes, from the running sum of the counts at the
+ * block's end (p_voff has no entry behind the last region: the last block adds that region's two counts).  launch == p.k is the catch-all behind the last group: the
+ * blocks the rule gives to no group (their calls end beyond n_variants).  The rule is a function of the block alone, so every block has exactly one launch and no
+ * state is kept between the launches. */
+__global__ void __launch_bounds__(256) avk_dp_region_chunk_kernel(dpk::DpArgs a, uint64_t *block_sums, avk::pc::ChunkPlan p, uint32_t launch, uint32_t n_blocks) {
+    const uint32_t b = blockIdx.x;
+    if (b >= n_blocks) return;
+    const uint64_t r_end = ((uint64_t)b + 1u) * 256u, n = a.in.n_regions;
+    const uint64_t calls_end = r_end < n ? a.in.pk_voff[r_end] : a.in.pk_voff[n - 1] + a.in.pk_tc[n - 1] + a.in.pk_qc[n - 1];
+    if (avk::pc::pc_launch_of_block(p, b, calls_end) != launch) return;
+    avk_dp_region_block(a, block_sums, b, n_blocks);
 }
 
 /* one workgroup per column of the block sums: the scanned quantities get their exclusive scan in place and their total, the class and
@@ -646,6 +662,9 @@ struct CopySeg {
     size_t bytes;
     hipStream_t stream = nullptr;     /* uploads: a stream other than the context's for this array */
     hipEvent_t then_record = nullptr; /* uploads: recorded on that stream behind this array's copy */
+    bool direct = false;              /* uploads: the caller has established that the array is pinned (copy_in does not look it up again) */
+    std::function<void()> then_call;  /* uploads: called on the queueing thread right behind that record — work that waits for the event is queued HERE, in front of the
+                                         copies that follow (upload_device_packed's chunked route says why) */
 };
 
 /* Copies between PINNED host arrays and HBM by a kernel instead of a DMA engine (round 6).  hipMemcpyAsync hands such a copy to an SDMA engine, and which engine a
@@ -704,6 +723,7 @@ static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs) {
         hipStream_t stream;
         hipEvent_t then_record; /* after this piece (the last of its segment) */
         bool direct;            /* pinned source: no staging */
+        const std::function<void()> *then_call;
     };
     std::vector<Piece> pieces;
     size_t staged = 0;
@@ -711,16 +731,17 @@ static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs) {
     for (const CopySeg &s : segs) {
         hipStream_t stream = s.stream ? s.stream : ctx->stream;
         if (!s.bytes || !s.host) {
-            if (s.then_record) pieces.push_back({nullptr, nullptr, 0, 0, stream, s.then_record, true});
+            if (s.then_record) pieces.push_back({nullptr, nullptr, 0, 0, stream, s.then_record, true, &s.then_call});
             continue;
         }
-        if (is_pinned(s.host, s.bytes)) {
-            pieces.push_back({(const uint8_t *)s.host, (uint8_t *)s.dev, 0, s.bytes, stream, s.then_record, true});
+        if (s.direct || is_pinned(s.host, s.bytes)) {
+            pieces.push_back({(const uint8_t *)s.host, (uint8_t *)s.dev, 0, s.bytes, stream, s.then_record, true, &s.then_call});
             continue;
         }
         for (size_t o = 0; o < s.bytes; o += piece_bytes) {
             const size_t nb = s.bytes - o < piece_bytes ? s.bytes - o : piece_bytes;
-            pieces.push_back({(const uint8_t *)s.host + o, (uint8_t *)s.dev + o, staged, nb, stream, o + nb == s.bytes ? s.then_record : (hipEvent_t) nullptr, false});
+            pieces.push_back({(const uint8_t *)s.host + o, (uint8_t *)s.dev + o, staged, nb, stream, o + nb == s.bytes ? s.then_record : (hipEvent_t) nullptr, false,
+                              o + nb == s.bytes ? &s.then_call : nullptr});
             staged += (nb + 63) & ~(size_t)63;
         }
     }
@@ -736,6 +757,7 @@ static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs) {
     const bool timed_engine = !ctx->up_stream && !by_kernel && ctx->kernel_copies == 1 && direct_bytes >= (8u << 20) && staged == 0 && ctx->ev_cp0 && ctx->ev_cp1;
     if (timed_engine) (void)hipEventRecord(ctx->ev_cp0, ctx->stream);
     ctx->cp_timed_bytes = 0;
+    bool cp1_recorded = false;
     auto issue = [&](const Piece &p) -> hipError_t { /* pieces are queued in segment order, whatever their source */
         const auto t0 = std::chrono::steady_clock::now();
         hipError_t e = hipSuccess;
@@ -743,6 +765,10 @@ static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs) {
         else if (p.bytes) e = hipMemcpyAsync(p.dev, p.direct ? p.src : ctx->h_bounce + p.off, p.bytes, hipMemcpyHostToDevice, p.stream);
         const auto t1 = std::chrono::steady_clock::now();
         if (e == hipSuccess && p.then_record) e = hipEventRecord(p.then_record, p.stream);
+        /* the engine's rate is that of the copies alone: behind the last piece the closing event goes in FRONT of whatever the piece's hook queues (kernels that wait for
+         * this very copy would stand between the copy and the event where the streams share a hardware queue; what earlier hooks queued is over long before) */
+        if (e == hipSuccess && timed_engine && &p == &pieces.back()) cp1_recorded = hipEventRecord(ctx->ev_cp1, ctx->stream) == hipSuccess;
+        if (e == hipSuccess && p.then_record && p.then_call && *p.then_call) (*p.then_call)();
         if (timing) {
             const double a = std::chrono::duration<double, std::milli>(t1 - t0).count(), b = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
             if (a > 0.5 || b > 0.5)
@@ -780,7 +806,7 @@ static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs) {
         });
     }
     if (herr != hipSuccess) return fail(ctx, AVK_E_HIP, "host to device copy failed: %s", hipGetErrorString(herr));
-    if (timed_engine && hipEventRecord(ctx->ev_cp1, ctx->stream) == hipSuccess) ctx->cp_timed_bytes = direct_bytes; /* (read by engine_rate_check once the stream has been waited for) */
+    if (timed_engine && cp1_recorded) ctx->cp_timed_bytes = direct_bytes; /* (read by engine_rate_check once the stream has been waited for) */
     return 0;
 }
 /* behind a host synchronisation with the context's stream: how fast the engine moved the arrays of the copy_in before it */
@@ -790,8 +816,15 @@ static void engine_rate_check(avk_ctx *ctx) {
     if (hipEventElapsedTime(&ms, ctx->ev_cp0, ctx->ev_cp1) == hipSuccess && ms > 0) {
         ctx->engine_in_gbs = ctx->cp_timed_bytes / (ms * 1e-3) / 1e9;
         if (ms > ctx->cp_timed_bytes / 36e9 * 1e3 + 0.15) { /* below 36 GB/s, with 0.15 ms for the dozen copies' own latencies (a rank's shard is 10 MB) */
-            ctx->engines_fast = false;
-            if (getenv("AVK_TIMING")) fprintf(stderr, "avk copies: the DMA engine moved this call's arrays at %.1f GB/s: synchronous calls copy by kernel from now on\n", ctx->engine_in_gbs);
+            /* two timed calls in a row: a half-rate engine is slow in every call, one slow measurement (another process on the link, the region pass beside the
+             * copies) is not a reason to give the engine up for the life of the context */
+            if (++ctx->engine_slow_calls >= 2) ctx->engines_fast = false;
+            if (getenv("AVK_TIMING"))
+                fprintf(stderr, "avk copies: the DMA engine moved this call's arrays at %.1f GB/s: %s\n", ctx->engine_in_gbs,
+                        ctx->engines_fast ? "one slow call, the next one decides" : "synchronous calls copy by kernel from now on");
+        } else {
+            ctx->engine_slow_calls = 0;
+            if (getenv("AVK_TIMING")) fprintf(stderr, "avk copies: the DMA engine moved this call's arrays at %.1f GB/s\n", ctx->engine_in_gbs);
         }
     } else
         (void)hipGetLastError();
@@ -1034,6 +1067,10 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     /* a compare batch in the packed form is read from the packed arrays themselves (DpIn::pk_*, round 6): no wide arrays, no widening pass */
     const bool packed_src = pk != nullptr && ctx->packed_source && !has_esc; /* (a batch with escapes is widened first: dp_widen_packed_esc) */
     bool early_variant = false, variant_done = false; /* dp_variant queued on the side stream of a packed upload, under its copies */
+    avk::pc::ChunkPlan chunk_plan = avk::pc::plan_chunks(0, 0, 0, 0); /* k > 0: the chunked route (option pack_chunks): the region pass runs on the side stream, group by group */
+    bool region_done = false;     /* ... and has been queued there: the first round of region_passes launches none */
+    bool queue_early = false;     /* the side stream's steps are queued from inside copy_in (option pack_queue_early, and always on the chunked route) */
+    ctx->last_region_launches = 0, ctx->tl_region_valid = false;
     auto tmp_or_kept = [&](size_t bytes) -> void * { return kept(bytes); };
     auto wide = [&](size_t bytes) -> void * { return packed_src ? nullptr : kept(bytes); };
     uint64_t *d_start = (uint64_t *)wide((n + 1) * 8), *d_end = (uint64_t *)wide((n + 1) * 8);
@@ -1107,6 +1144,22 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
         hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.region, (const uint32_t *)nullptr, (const uint32_t *)nullptr, de.n_regions, de.first_region,
                            de.first_region + n_regions_all, z_region, (uint64_t *)nullptr, (uint64_t *)nullptr, totals + 2);
     };
+    auto fill_args = [&] { /* the caller's arrays (the wide ones: NULL for a batch read from its packed source) and the context's options, as the packing kernels take them */
+        a.in.contig_idx = d_contig, a.in.start = d_start, a.in.end = d_end, a.in.t_off = db->d_in_t_off, a.in.q_off = db->d_in_q_off, a.in.t_cnt = db->d_in_t_cnt,
+        a.in.q_cnt = db->d_in_q_cnt, a.in.var_pos = d_pos, a.in.var_type = d_type, a.in.var_zyg = d_zyg, a.in.var_raw = d_raw, a.in.a0_off = d_a0o, a.in.a1_off = d_a1o,
+        a.in.a0_len = d_a0l, a.in.a1_len = d_a1l, a.in.alleles = d_alleles, a.in.n_regions = n, a.in.n_variants = nv, a.in.alleles_len = alen,
+        a.in.contig_base = ctx->d_contig_tab, a.in.contig_len = ctx->d_contig_tab + ctx->contig_len.size(), a.in.n_contigs = (uint32_t)ctx->contig_len.size(),
+        a.in.pairs_mode = pairs_mode ? 1u : 0u;
+        const bool lanes = ctx->lane_kernel && ctx->use_packed_reference && ctx->d_ref2b;
+        a.opt.tier0_bytes = avk::bulk_slice_bytes((uint64_t)ctx->lds_bytes_per_wave), a.opt.tier0_ed_cap = (uint32_t)ctx->lds_ed_cap, a.opt.tier1_bytes = (uint64_t)ctx->lds2_bytes_per_wave,
+        a.opt.tier1_ed_cap = (uint32_t)ctx->lds2_ed_cap, a.opt.solo_min_variants = pairs_mode && !ctx->pair_classes ? 0u : (uint32_t)ctx->solo_min_variants, a.opt.max_branch = 50,
+        a.opt.class_c_nodes_x2 = (uint32_t)ctx->class_c_nodes_x2, a.opt.lane_min_regions = lanes ? (uint64_t)ctx->lane_min_regions : 0xFFFFFFFFull,
+        a.opt.lane_max_calls = (uint32_t)ctx->lane_max_calls, a.opt.lane_min_batch = (uint64_t)ctx->lane_min_batch, a.opt.lane_max_est = (uint32_t)ctx->lane_max_est;
+        a.opt.stripe_w = ctx->lane_stripe ? (uint32_t)ctx->lane_head_width : 0u;
+        a.opt.lane_pairs = ctx->lane_pairs ? 1u : 0u;
+        a.opt.head_est = (uint32_t)ctx->lane_head_est, a.opt.het_min = (uint32_t)ctx->het_search_min;
+        a.opt.class_c_below = (uint64_t)ctx->class_c_below;
+    };
     if (pk) { /* the packed arrays as they are, two prefix sums for the offsets they leave out, one kernel that writes the wide arrays */
         /* (the packed arrays stay with the batch when they are what the packer and the later record writers read; a staging slot's stay with its ticket) */
         auto src = [&](size_t bytes) -> void * { return packed_src ? kept(bytes) : tmp(bytes); };
@@ -1127,6 +1180,81 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             (void)hipStreamSynchronize(side);
             return bail(code);
         };
+        /* The chunked route (option pack_chunks) is for the synchronous call on pinned arrays that is read from its packed source and copies by engine: a staging slot's
+         * arrays are there already, a batch with escapes is widened first, pageable arrays cross piece by piece through the bounce buffer, and avk_copy_kernel occupies
+         * the compute units the region pass would run on.  Everything else keeps the old order, launch for launch. */
+        auto all_pinned = [&] {
+            return is_pinned(pk->t_cnt, n) && is_pinned(pk->q_cnt, n) && is_pinned(pk->a0_len, nv) && is_pinned(pk->a1_len, nv) && is_pinned(pk->allele_bytes, alen) &&
+                   is_pinned(pk->start, n * 4) && is_pinned(pk->len, n * 2) && is_pinned(pk->contig_idx, n * 2) && is_pinned(pk->var_rel_pos, nv * 2) &&
+                   is_pinned(pk->var_type_zyg, nv) && is_pinned(pk->var_raw_space, nv * 4);
+        };
+        const bool eligible = (ctx->pack_chunks > 0 || ctx->pack_queue_early) && packed_src && nv && !pre && !ctx->up_stream && !copies_by_kernel(ctx) && all_pinned();
+        queue_early = eligible;
+        if (eligible && ctx->pack_chunks > 0) {
+            chunk_plan = avk::pc::plan_chunks(n, nv, ctx->pack_chunks, (uint64_t)ctx->pack_chunk_floor);
+            for (uint32_t j = 0; j + 1 < chunk_plan.k && !rc; ++j)
+                if (!ctx->ev_pack_group[j] && hipEventCreateWithFlags(&ctx->ev_pack_group[j], hipEventDisableTiming) != hipSuccess) {
+                    ctx->ev_pack_group[j] = nullptr;
+                    rc = fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(hipGetLastError()));
+                }
+            if (rc) return bail(rc);
+        }
+        auto queue_sums = [&]() -> hipError_t { /* the two prefix sums, on the side stream behind the counts and lengths */
+            hipError_t ec = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0); /* (also orders the side stream behind everything queued on the context's stream before) */
+            if (ec != hipSuccess) return ec;
+            if (has_esc && hipMemsetAsync(p_sums + nb_r + nb_v, 0, 32, side) != hipSuccess) return hipGetLastError();
+            if (n) {
+                hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_tc, (const uint8_t *)p_qc, n, p_sums);
+                hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums, nb_r, p_sums + nb_r + nb_v);
+                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_tc, (const uint8_t *)p_qc, n, (const uint64_t *)p_sums, p_voff);
+            }
+            if (nv) {
+                hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, p_sums + nb_r);
+                hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums + nb_r, nb_v, p_sums + nb_r + nb_v + 1);
+                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, (const uint64_t *)(p_sums + nb_r), p_aoff);
+            }
+            return hipGetLastError();
+        };
+        /* Variant::alt_ed for every call, on the side stream behind the prefix sums and the allele bytes, while the region arrays still cross the bus: the state
+         * block is cleared here (dp_variant counts the calls it leaves to the host); the context's stream waits for ev_copy_join below as before */
+        auto queue_variant = [&]() -> hipError_t {
+            a.in.pk_a0 = p_a0, a.in.pk_a1 = p_a1, a.in.pk_aoff = p_aoff, a.in.pk_start = p_start; /* (what dp_variant reads of the packed source; the rest follows below) */
+            a.in.alleles = d_alleles, a.in.n_variants = nv, a.in.alleles_len = alen, a.in.n_regions = n;
+            hipError_t ev = hipMemsetAsync(a.st, 0, sizeof(dpk::DpState), side);
+            if (ev == hipSuccess) ev = hipStreamWaitEvent(side, ctx->ev_copy_alleles, 0);
+            if (ev == hipSuccess) {
+                hipLaunchKernelGGL(avk_dp_variant_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, side, a);
+                ev = hipGetLastError();
+            }
+            return ev;
+        };
+        /* The chunked route's region pass: launch j on the side stream behind dp_variant, the prefix sums and the event of group j; each block is run by exactly one
+         * launch (pc_launch_of_block), the catch-all behind the last group runs what none took.  block_sums and the region info are what the one launch writes.
+         *
+         * WHEN these are queued matters as much as what they wait for.  The runtime maps the context's streams onto a few hardware queues, a queue takes its packets in
+         * order, and every event recorded behind a copy is a packet that holds its queue until that copy is done.  Queued after copy_in has returned, the side stream's
+         * kernels sit — where the side stream shares the copy stream's queue — behind the packet of the LAST copy and start when it ends: a kernel trace of the old
+         * order shows the prefix sums and dp_variant starting 18 us after the last copy, whatever their events say (profiles/pack_chunks_ab.txt).  So each step is queued
+         * from copy_in itself, right behind the record of the event it waits for (CopySeg::then_call): in a shared queue it then stands in front of the later copies'
+         * packets, in a queue of its own nothing changes. */
+        hipError_t hook_err = hipSuccess;
+        auto queue_chunk = [&](uint32_t j) {
+            if (hook_err != hipSuccess) return;
+            hook_err = hipStreamWaitEvent(side, j + 1 == chunk_plan.k ? ctx->ev_copy_mid : ctx->ev_pack_group[j], 0);
+            for (uint32_t l = j; l <= (j + 1 == chunk_plan.k ? j + 1 : j) && hook_err == hipSuccess; ++l) { /* (behind the last group: the catch-all, l = k) */
+                const uint32_t grid = l < chunk_plan.k ? chunk_plan.block_cut[l + 1] : n_blocks;
+                hipLaunchKernelGGL(avk_dp_region_chunk_kernel, dim3(grid ? grid : 1u), dim3(256), 0, side, a, d_block_sums, chunk_plan, l, n_blocks);
+                hook_err = hipGetLastError();
+                ctx->last_region_launches += 1;
+            }
+            if (j + 1 != chunk_plan.k || hook_err != hipSuccess) return;
+            if (timing) {
+                if (!ctx->ev_tl[5] && hipEventCreate(&ctx->ev_tl[5]) != hipSuccess) ctx->ev_tl[5] = nullptr, (void)hipGetLastError();
+                if (ctx->ev_tl[5] && hipEventRecord(ctx->ev_tl[5], side) == hipSuccess) ctx->tl_region_valid = true;
+            }
+            hook_err = hipEventRecord(ctx->ev_copy_join, side);
+            region_done = hook_err == hipSuccess;
+        };
         if (pre) { /* the arrays are in a staging slot already (or on their way there on the copy stream) */
             hipError_t ep = hipStreamWaitEvent(s, pre->ready, 0);
             if (ep == hipSuccess) ep = hipEventRecord(ctx->ev_copy_fork, s);
@@ -1135,6 +1263,32 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             if (ep != hipSuccess) rc = fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ep));
         } else
         /* (round 6: the allele bytes cross right behind the lengths — dp_variant needs nothing else, and runs on the side stream under the copies that follow) */
+        if (chunk_plan.k) { /* the chunked route: counts, lengths and allele bytes as below, then group by group: region range j of the per-region arrays, call chunk j of the
+                             * per-call arrays, an event; the last group's event is ev_copy_mid */
+            fill_args(); /* (the launches are queued from inside copy_in: everything dp_region reads is named now) */
+            a.in.pk_start = p_start, a.in.pk_len = p_len, a.in.pk_contig = p_contig, a.in.pk_rel = p_rel, a.in.pk_tc = p_tc, a.in.pk_qc = p_qc, a.in.pk_tz = p_tz, a.in.pk_a0 = p_a0,
+            a.in.pk_a1 = p_a1, a.in.pk_voff = p_voff, a.in.pk_aoff = p_aoff, a.in.v_lo = 0, a.in.v_hi = nv;
+            std::vector<CopySeg> segs = {{pk->t_cnt, p_tc, n}, {pk->q_cnt, p_qc, n}, {pk->a0_len, p_a0, nv}, {pk->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork},
+                                         {pk->allele_bytes, d_alleles, alen, nullptr, ctx->ev_copy_alleles}};
+            segs[3].then_call = [&] { hook_err = queue_sums(); };
+            segs[4].then_call = [&] {
+                if (hook_err == hipSuccess) hook_err = queue_variant();
+                variant_done = hook_err == hipSuccess;
+            };
+            for (uint32_t j = 0; j < chunk_plan.k; ++j) {
+                const avk::pc::Range rr = avk::pc::pc_region_range(chunk_plan, j), cr = avk::pc::pc_call_range(chunk_plan, j);
+                segs.push_back({pk->start + rr.first, p_start + rr.first, rr.count * 4});
+                segs.push_back({pk->len + rr.first, p_len + rr.first, rr.count * 2});
+                segs.push_back({has_contig ? pk->contig_idx + rr.first : nullptr, has_contig ? p_contig + rr.first : nullptr, has_contig ? rr.count * 2 : 0});
+                segs.push_back({pk->var_rel_pos + cr.first, p_rel + cr.first, cr.count * 2});
+                segs.push_back({pk->var_type_zyg + cr.first, p_tz + cr.first, cr.count});
+                segs.push_back({has_raw ? pk->var_raw_space + cr.first : nullptr, has_raw ? d_raw + cr.first : nullptr, has_raw ? cr.count * 4 : 0, nullptr,
+                                j + 1 == chunk_plan.k ? ctx->ev_copy_mid : ctx->ev_pack_group[j]});
+                segs.back().then_call = [&queue_chunk, j] { queue_chunk(j); };
+            }
+            for (CopySeg &sg : segs) sg.direct = true;
+            rc = copy_in(ctx, segs);
+        } else
         { /* (the escape lists, when there are any, in front of the array whose event releases the widening; none: the order of the copies is what it was) */
             std::vector<CopySeg> segs = {{pk->t_cnt, p_tc, n}, {pk->q_cnt, p_qc, n}, {pk->a0_len, p_a0, nv}, {pk->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork},
                                          {pk->allele_bytes, d_alleles, alen, nullptr, ctx->ev_copy_alleles}, {pk->start, p_start, n * 4}, {pk->len, p_len, n * 2},
@@ -1142,24 +1296,21 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             segs.insert(segs.end(), esc_segs.begin(), esc_segs.end());
             segs.push_back({pk->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid});
             segs.push_back({pk->var_raw_space, d_raw, has_raw ? nv * 4 : 0});
+            if (queue_early) { /* the old order of the copies, the prefix sums and dp_variant queued behind their events as on the chunked route */
+                segs[3].then_call = [&] { hook_err = queue_sums(); };
+                segs[4].then_call = [&] {
+                    if (hook_err == hipSuccess) hook_err = queue_variant();
+                    variant_done = hook_err == hipSuccess;
+                };
+                for (CopySeg &sg : segs) sg.direct = true;
+            }
             rc = copy_in(ctx, segs);
         }
         early_variant = packed_src && nv != 0;
         mark(1);
-        if (rc) return bail(rc);
-        hipError_t ec = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0); /* (also orders the side stream behind everything queued on the context's stream before) */
-        if (ec != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ec)));
-        if (has_esc && hipMemsetAsync(p_sums + nb_r + nb_v, 0, 32, side) != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(hipGetLastError())));
-        if (n) {
-            hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_tc, (const uint8_t *)p_qc, n, p_sums);
-            hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums, nb_r, p_sums + nb_r + nb_v);
-            hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_tc, (const uint8_t *)p_qc, n, (const uint64_t *)p_sums, p_voff);
-        }
-        if (nv) {
-            hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, p_sums + nb_r);
-            hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums + nb_r, nb_v, p_sums + nb_r + nb_v + 1);
-            hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, (const uint64_t *)(p_sums + nb_r), p_aoff);
-        }
+        if (rc) return side_fail(rc);
+        hipError_t ec = queue_early ? hook_err : queue_sums(); /* (queued early: they stand behind the lengths' copy already) */
+        if (ec != hipSuccess) return side_fail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ec)));
         /* the totals must be what the caller said: n_variants calls, allele_bytes_len bytes (two words back, with the packer's state block) */
         pk_totals = p_sums + nb_r + nb_v;
         dpk::DpPacked c;
@@ -1170,20 +1321,12 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
         c.w_t_off = db->d_in_t_off, c.w_q_off = db->d_in_q_off, c.w_pos = d_pos, c.w_a0_off = d_a0o, c.w_a1_off = d_a1o, c.w_type = d_type, c.w_zyg = d_zyg;
         const uint64_t m = n > nv ? n : nv;
         hipError_t ew = hipSuccess;
-        if (early_variant) {
-            /* Variant::alt_ed for every call, on the side stream behind the prefix sums and the allele bytes, while the region arrays still cross the bus: the state
-             * block is cleared here (dp_variant counts the calls it leaves to the host); the context's stream waits for ev_copy_join below as before */
-            a.in.pk_a0 = p_a0, a.in.pk_a1 = p_a1, a.in.pk_aoff = p_aoff, a.in.pk_start = p_start; /* (what dp_variant reads of the packed source; the rest follows below) */
-            a.in.alleles = d_alleles, a.in.n_variants = nv, a.in.alleles_len = alen, a.in.n_regions = n;
-            ew = hipMemsetAsync(a.st, 0, sizeof(dpk::DpState), side);
-            if (ew == hipSuccess) ew = hipStreamWaitEvent(side, ctx->ev_copy_alleles, 0);
-            if (ew == hipSuccess) {
-                hipLaunchKernelGGL(avk_dp_variant_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, side, a);
-                ew = hipGetLastError();
-            }
+        if (early_variant && !queue_early) {
+            ew = queue_variant();
             variant_done = ew == hipSuccess;
         }
-        if (ew == hipSuccess) ew = hipStreamWaitEvent(side, ctx->ev_copy_mid, 0);
+        if (queue_early && !(variant_done && (region_done || !chunk_plan.k)) && ew == hipSuccess) ew = hipErrorUnknown; /* (dp_variant and the chunked region launches were queued from copy_in) */
+        if (ew == hipSuccess && !chunk_plan.k) ew = hipStreamWaitEvent(side, ctx->ev_copy_mid, 0); /* (chunked: the side stream waits group by group, below) */
         if (packed_src) { /* the packer reads these as they are */
             a.in.pk_start = p_start, a.in.pk_len = p_len, a.in.pk_contig = p_contig, a.in.pk_rel = p_rel, a.in.pk_tc = p_tc, a.in.pk_qc = p_qc, a.in.pk_tz = p_tz, a.in.pk_a0 = p_a0,
             a.in.pk_a1 = p_a1, a.in.pk_voff = p_voff, a.in.pk_aoff = p_aoff;
@@ -1196,7 +1339,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             hipLaunchKernelGGL(avk_dp_widen_packed_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, side, c);
             ew = hipGetLastError();
         }
-        if (ew == hipSuccess) ew = hipEventRecord(ctx->ev_copy_join, side);
+        if (ew == hipSuccess && !chunk_plan.k) ew = hipEventRecord(ctx->ev_copy_join, side); /* (chunked: recorded behind the catch-all launch) */
         if (ew == hipSuccess) ew = hipStreamWaitEvent(s, ctx->ev_copy_join, 0); /* from here on the context's stream has the wide arrays (and, being behind its own copies, the allele bytes) */
         if (ew != hipSuccess) return side_fail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(ew)));
     } else if (b) {
@@ -1316,11 +1459,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
         }
     }
     const auto t_copy = now();
-    a.in.contig_idx = d_contig, a.in.start = d_start, a.in.end = d_end, a.in.t_off = db->d_in_t_off, a.in.q_off = db->d_in_q_off, a.in.t_cnt = db->d_in_t_cnt,
-    a.in.q_cnt = db->d_in_q_cnt, a.in.var_pos = d_pos, a.in.var_type = d_type, a.in.var_zyg = d_zyg, a.in.var_raw = d_raw, a.in.a0_off = d_a0o, a.in.a1_off = d_a1o,
-    a.in.a0_len = d_a0l, a.in.a1_len = d_a1l, a.in.alleles = d_alleles, a.in.n_regions = n, a.in.n_variants = nv, a.in.alleles_len = alen,
-    a.in.contig_base = ctx->d_contig_tab, a.in.contig_len = ctx->d_contig_tab + ctx->contig_len.size(), a.in.n_contigs = (uint32_t)ctx->contig_len.size(),
-    a.in.pairs_mode = pairs_mode ? 1u : 0u;
+    fill_args();
     { /* the calls this batch owns, guessed from its first and last region (batches of one job may share the call arrays: compare_main.cpp);
        * dp_region notes any region outside the guess */
         uint64_t lo = 0, hi = 0;
@@ -1345,15 +1484,6 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             if (hipMemsetAsync(a.in.owned, 0, hi - lo, s) != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(hipGetLastError())));
         }
     }
-    const bool lanes = ctx->lane_kernel && ctx->use_packed_reference && ctx->d_ref2b;
-    a.opt.tier0_bytes = avk::bulk_slice_bytes((uint64_t)ctx->lds_bytes_per_wave), a.opt.tier0_ed_cap = (uint32_t)ctx->lds_ed_cap, a.opt.tier1_bytes = (uint64_t)ctx->lds2_bytes_per_wave,
-    a.opt.tier1_ed_cap = (uint32_t)ctx->lds2_ed_cap, a.opt.solo_min_variants = pairs_mode && !ctx->pair_classes ? 0u : (uint32_t)ctx->solo_min_variants, a.opt.max_branch = 50,
-    a.opt.class_c_nodes_x2 = (uint32_t)ctx->class_c_nodes_x2, a.opt.lane_min_regions = lanes ? (uint64_t)ctx->lane_min_regions : 0xFFFFFFFFull,
-    a.opt.lane_max_calls = (uint32_t)ctx->lane_max_calls, a.opt.lane_min_batch = (uint64_t)ctx->lane_min_batch, a.opt.lane_max_est = (uint32_t)ctx->lane_max_est;
-    a.opt.stripe_w = ctx->lane_stripe ? (uint32_t)ctx->lane_head_width : 0u;
-    a.opt.lane_pairs = ctx->lane_pairs ? 1u : 0u;
-    a.opt.head_est = (uint32_t)ctx->lane_head_est, a.opt.het_min = (uint32_t)ctx->het_search_min;
-    a.opt.class_c_below = (uint64_t)ctx->class_c_below;
     hipError_t e = variant_done ? hipSuccess : hipMemsetAsync(a.st, 0, sizeof(dpk::DpState), s);
     if (e == hipSuccess && nv && !variant_done) {
         hipLaunchKernelGGL(avk_dp_variant_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, a);
@@ -1363,7 +1493,15 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     auto region_passes = [&]() -> hipError_t { /* everything that depends on alt_ed, up to the state block on the host */
         hipError_t x = hipSuccess;
         if (n) {
-            hipLaunchKernelGGL(avk_dp_region_kernel, dim3(n_blocks), dim3(256), 0, s, a, d_block_sums);
+            if (!region_done) {
+                hipLaunchKernelGGL(avk_dp_region_kernel, dim3(n_blocks), dim3(256), 0, s, a, d_block_sums);
+                ctx->last_region_launches += 1;
+                if (timing) {
+                    if (!ctx->ev_tl[5] && hipEventCreate(&ctx->ev_tl[5]) != hipSuccess) ctx->ev_tl[5] = nullptr, (void)hipGetLastError();
+                    if (ctx->ev_tl[5] && hipEventRecord(ctx->ev_tl[5], s) == hipSuccess) ctx->tl_region_valid = true;
+                }
+            }
+            region_done = false; /* (a second round, behind the host's edit distances, runs the whole range in one launch) */
             if (a.in.owned && a.in.v_hi > a.in.v_lo)
                 hipLaunchKernelGGL(avk_dp_count_owned_kernel, dim3((unsigned)((a.in.v_hi - a.in.v_lo + 4095) / 4096)), dim3(256), 0, s, (const uint8_t *)a.in.owned, a.in.v_hi - a.in.v_lo, a.st);
             hipLaunchKernelGGL(avk_dp_scan_blocks_kernel, dim3(AVK_DP_BS), dim3(1024), 0, s, d_block_sums, n_blocks, a.st);

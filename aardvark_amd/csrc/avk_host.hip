@@ -29,6 +29,7 @@
 
 #include "../../include/aardvark_amd.h"
 #include "avk_pack.h"
+#include "avk_pack_chunks.h"
 #include "avk_counters.h"
 #include "avk_solver.inl"
 #include "avk_lane.inl"
@@ -403,10 +404,20 @@ struct avk_ctx {
     int64_t copy_blocks_per_cu = 8; /* workgroups of avk_copy_kernel per CU (AVK_COPY_BLOCKS in the environment overrides: a tuning aid) */
     int64_t kernel_copies = 1;  /* the pinned arrays of a synchronous call cross the bus 0: by the DMA engine the process drew, 2: by a copy kernel, 1: by whichever a measurement of
                                    the engine says (avk_devpack_host.inl: copies_by_kernel) */
-    bool engines_fast = true;   /* no call of this context has seen its arrays cross below 36 GB/s on the engine */
+    bool engines_fast = true;   /* no two consecutive timed calls of this context have seen their arrays cross below 36 GB/s on the engine */
+    int engine_slow_calls = 0;  /* timed calls in a row below that rate (engine_rate_check: one noisy measurement does not switch the context for good) */
     double engine_in_gbs = 0;
     size_t cp_timed_bytes = 0;  /* bytes between ev_cp0 and ev_cp1 of the last engine-timed copy_in (0: none pending) */
     hipEvent_t ev_cp0 = nullptr, ev_cp1 = nullptr;
+    int64_t pack_chunks = 0;    /* N = 2 .. 8: a synchronous packed compare call's per-region and per-call arrays cross in N groups and the region pass runs group by group under
+                                   the copies (avk_pack_chunks.h, upload_device_packed); 0: one region launch behind the last copy.  Off: two groups gain
+                                   0.09 ms of a whole-genome call over pack_queue_early alone, with four hardware queues and with 24 — inside the spread of the
+                                   four-queue runs (profiles/pack_chunks_ab.txt) */
+    int64_t pack_queue_early = 1; /* 1: such a call queues the side stream's steps (prefix sums, dp_variant) from inside copy_in, each right behind the event it waits for, so
+                                     that they run under the copies also where the side stream shares the copy stream's hardware queue; 0: after the copies are queued */
+    int64_t pack_chunk_floor = 1 << 20; /* a batch whose groups would copy less than this many bytes of some array keeps the old order (tests lower it so that small batches chunk) */
+    hipEvent_t ev_pack_group[avk::pc::PC_MAX_GROUPS] = {nullptr}; /* behind the copies of group j (made when first used; the last group records ev_copy_mid) */
+    uint64_t last_region_launches = 0; /* launches of the region pass the last device-packed upload queued (avk_last_region_launches) */
     int64_t packed_source = 1;  /* 1: a batch in the packed form is packed from the packed arrays themselves (no wide copy of the caller's arrays in HBM); 0: round 5's widening pass */
     int64_t emit_bp_groups = 0; /* kernels write the compact per-region BASEPAIR groups (avk_result_batch::bp_groups) */
     int64_t capacity_retry = 1; /* avk_results_download solves regions that exhausted the last workspace tier again with larger slices */
@@ -476,7 +487,9 @@ struct avk_ctx {
     hipStream_t lane_stream4 = nullptr; /* the head launches of the two-call classes (long: beside the rest of their class, not ahead of it) */
     hipEvent_t ev_lane_join4 = nullptr, ev_lane_early = nullptr;
     hipEvent_t ev_hb[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; /* ends of the lane classes' head launches (handback_chains) */
-    hipEvent_t ev_tl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; /* AVK_TIMING only: marks of a boundary call on the context's stream (first copy, last copy, work order, writers, results) */
+    hipEvent_t ev_tl[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; /* AVK_TIMING only: marks of a boundary call on the context's stream (first copy, last copy, work order, writers, results)
+                                                                                     and, [5], behind the region pass on whichever stream it ran */
+    bool tl_region_valid = false; /* ev_tl[5] was recorded by the last upload */
     hipEvent_t ev_copy_alleles = nullptr; /* packed upload: behind the allele bytes' copy (dp_variant starts there) */
     hipEvent_t ev_copy_fork = nullptr, ev_copy_mid = nullptr, ev_copy_join = nullptr; /* packed upload: all but the counts cross on lane_stream4 beside the offset kernels */
     hipStream_t side_stream = nullptr, side_stream2 = nullptr; /* solo launches (LDS, HBM): one stream each, they run side by side */
@@ -752,6 +765,8 @@ void avk_ctx_destroy(avk_ctx *ctx) {
     if (ctx->d_big) (void)hipFree(ctx->d_big);
     for (hipEvent_t &t : ctx->ev_tl)
         if (t) (void)hipEventDestroy(t);
+    for (hipEvent_t &t : ctx->ev_pack_group)
+        if (t) (void)hipEventDestroy(t);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev_lab0) (void)hipEventDestroy(ctx->ev_lab0);
     if (ctx->ev_lab1) (void)hipEventDestroy(ctx->ev_lab1);
@@ -887,6 +902,14 @@ int avk_ctx_set_option(avk_ctx *ctx, const char *name, int64_t value) {
         ctx->kernel_copies = value;
     } else if (n == "packed_source") {
         ctx->packed_source = value ? 1 : 0;
+    } else if (n == "pack_chunks") {
+        if (value != 0 && (value < 2 || value > avk::pc::PC_MAX_GROUPS)) return fail(ctx, AVK_E_ARG, "pack_chunks must be 0 (one region launch behind the copies) or 2..8 groups");
+        ctx->pack_chunks = value;
+    } else if (n == "pack_queue_early") {
+        ctx->pack_queue_early = value ? 1 : 0;
+    } else if (n == "pack_chunk_floor") {
+        if (value < 0) return fail(ctx, AVK_E_ARG, "pack_chunk_floor must not be negative");
+        ctx->pack_chunk_floor = value;
     } else if (n == "emit_bp_groups") {
         ctx->emit_bp_groups = value ? 1 : 0;
     } else if (n == "emit_group_metrics") {
@@ -2170,6 +2193,12 @@ int avk_last_lane_solved(avk_ctx *ctx, uint64_t *count) {
     return 0;
 }
 
+int avk_last_region_launches(avk_ctx *ctx, uint64_t *count) {
+    if (!ctx || !count) return AVK_E_ARG;
+    *count = ctx->last_region_launches;
+    return 0;
+}
+
 int avk_last_wide_solved(avk_ctx *ctx, uint64_t *count) {
     if (!ctx || !count) return AVK_E_ARG;
     *count = ctx->last_wide_solved;
@@ -3316,12 +3345,13 @@ int avk_compare_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const av
         fprintf(stderr, "avk compare packed: upload %.3f ms, launches %.3f ms, download %.3f ms, free %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3),
                 ms(t3, std::chrono::steady_clock::now()));
         if (!rc && ctx->ev_tl[4] && ctx->ev_valid) { /* the same call on the device's clock, free-running (no profiler): events on the context's stream */
-            float c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0;
+            float c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, c7 = 0;
+            if (!ctx->tl_region_valid || !ctx->ev_tl[5] || hipEventElapsedTime(&c7, ctx->ev_tl[0], ctx->ev_tl[5]) != hipSuccess) c7 = -1.f, (void)hipGetLastError(); /* (-1: this call recorded none) */
             if (hipEventElapsedTime(&c1, ctx->ev_tl[0], ctx->ev_tl[1]) == hipSuccess && hipEventElapsedTime(&c2, ctx->ev_tl[0], ctx->ev_tl[2]) == hipSuccess &&
                 hipEventElapsedTime(&c3, ctx->ev_tl[0], ctx->ev_tl[3]) == hipSuccess && hipEventElapsedTime(&c4, ctx->ev_tl[0], ctx->ev0) == hipSuccess &&
                 hipEventElapsedTime(&c5, ctx->ev_tl[0], ctx->ev1) == hipSuccess && hipEventElapsedTime(&c6, ctx->ev_tl[0], ctx->ev_tl[4]) == hipSuccess)
-                fprintf(stderr, "avk compare packed, device clock from the first copy: copies in done %.3f ms, work order done %.3f, record writers done %.3f, solver launches %.3f .. %.3f, results out %.3f\n",
-                        c1, c2, c3, c4, c5, c6);
+                fprintf(stderr, "avk compare packed, device clock from the first copy: copies in done %.3f ms, region pass done %.3f, work order done %.3f, record writers done %.3f, solver launches %.3f .. %.3f, results out %.3f\n",
+                        c1, c7, c2, c3, c4, c5, c6);
             else
                 (void)hipGetLastError();
             /* where each chain of the launch graph ended, from the first solver launch (events of this call only when the batch used the chain) */

@@ -347,6 +347,11 @@ int  avk_ctx_set_stream(avk_ctx *ctx, void *hip_stream);
  *                    bytes at a time from / to the pinned pages: profiles/r06_copy_engines.txt; 0: always hipMemcpyAsync; 2: always the kernel),
  *                    "split_parts" (1; 2..4: an avk_compare_packed call of pinned arrays runs as that many batches in flight,
  *                    compare_packed_split — slower than the whole call today, profiles/r06_split_call.txt)
+ *                    "pack_queue_early" (1: a synchronous avk_compare_packed call on pinned arrays queues the packer's prefix sums and dp_variant from inside its copy
+ *                    loop, each right behind the event it waits for, so that they run under the copies also where the streams share a hardware queue; 0: after the
+ *                    copies are queued), "pack_chunks" (0; 2..8: such a call also copies its per-region and per-call arrays in that many groups and runs the region
+ *                    pass group by group under them, avk_pack_chunks.h, DESIGN section 5 — byte-identical results), "pack_chunk_floor" (1048576: a batch whose
+ *                    groups would copy fewer bytes of some array keeps the old order; tests lower it)
  *   outputs          "emit_group_metrics" (0 = kernels skip the per-region 13 x 22 block; the batch tally is always produced), "emit_bp_groups" (1 = kernels write the
  *                    compact per-region BASEPAIR groups; the one-call entry points switch it on when the caller hands the arrays in), "accumulate_tally" (1 =
  *                    avk_compare_resident ADDS the batch tally to tally_dev)
@@ -459,6 +464,8 @@ int  avk_last_compare_was_one_shot(avk_ctx *ctx);  /* 1: the batch of the last a
 int  avk_last_lane_ms(avk_ctx *ctx, float *ms);    /* start of the call to the end of its lane-per-region launches (0: it had none) */
 int  avk_last_lane_solved(avk_ctx *ctx, uint64_t *count); /* regions the lane-per-region kernel finished (last downloaded step);
                                                              they are not counted in any workspace tier */
+int  avk_last_region_launches(avk_ctx *ctx, uint64_t *count); /* launches of the packer's region pass the last device-packed upload queued: 1, one more when calls were left
+                                                                 to the host's edit distance; with the option pack_chunks = N on a batch that takes the chunked route, N + 1 (the groups and the catch-all) */
 int  avk_last_wide_solved(avk_ctx *ctx, uint64_t *count); /* the same for the wave-cooperative kernel of the large searches on small windows (option wide_kernel) */
 /* Host utility (no GPU involved): the full GroupTypeMetrics block of region r (13 groups x 22 counters, the layout of group_metrics) from the batch, the
  * per-call outputs var_expected / var_observed of `res` and the region's compact BASEPAIR groups: the GT / HAP / WEIGHTED_HAP counters follow from
