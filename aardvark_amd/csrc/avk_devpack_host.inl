@@ -714,8 +714,9 @@ static hipError_t kernel_copy(avk_ctx *ctx, void *dst, const void *src, size_t b
 }
 
 /* host -> device on the context's stream (or the segment's): straight from pinned arrays; pageable ones through the bounce buffer, piece by piece — the host threads
- * fill pieces while this thread queues the copy of every piece that is ready */
-static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs) {
+ * fill pieces while this thread queues the copy of every piece that is ready.  on_pack_stream: the upload of a submitted batch, whose copies run beside the kernels of
+ * the batch before: always the engines, and not timed */
+static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs, bool on_pack_stream) {
     struct Piece {
         const uint8_t *src;
         uint8_t *dev;
@@ -753,8 +754,8 @@ static int copy_in(avk_ctx *ctx, const std::vector<CopySeg> &segs) {
     const bool timing = getenv("AVK_TIMING") != nullptr;
     size_t direct_bytes = 0;
     for (const Piece &p : pieces) direct_bytes += p.direct ? p.bytes : 0;
-    const bool by_kernel = !ctx->up_stream && direct_bytes >= (8u << 20) && copies_by_kernel(ctx); /* (small batches: the engines' latency is what counts) */
-    const bool timed_engine = !ctx->up_stream && !by_kernel && ctx->kernel_copies == 1 && direct_bytes >= (8u << 20) && staged == 0 && ctx->ev_cp0 && ctx->ev_cp1;
+    const bool by_kernel = !on_pack_stream && direct_bytes >= (8u << 20) && copies_by_kernel(ctx); /* (small batches: the engines' latency is what counts) */
+    const bool timed_engine = !on_pack_stream && !by_kernel && ctx->kernel_copies == 1 && direct_bytes >= (8u << 20) && staged == 0 && ctx->ev_cp0 && ctx->ev_cp1;
     if (timed_engine) (void)hipEventRecord(ctx->ev_cp0, ctx->stream);
     ctx->cp_timed_bytes = 0;
     bool cp1_recorded = false;
@@ -1005,7 +1006,7 @@ static void packed_host_alleles(const uint8_t *l0, const uint8_t *l1, uint64_t n
 /* b: the batch in the wide form, or NULL and cb: the batch in the compact form (avk_compact_batch: half the bytes over PCIe, widened on the device) */
 /* mb: a batch of MultiRegions (the merge path): one region per input pair is made on the device (dp_expand_pairs) */
 /* (pm: the packed form of a multi batch; `mb` then only carries n_regions, n_inputs, n_variants, allele_bytes and allele_bytes_len) */
-static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const avk_compact_batch *cb, bool pairs_mode, avk_dev_batch **out, const avk_multi_batch *mb = nullptr,
+static int upload_device_packed(avk_ctx *ctx, const CallSpec &spec, const avk_region_batch *b, const avk_compact_batch *cb, bool pairs_mode, avk_dev_batch **out, const avk_multi_batch *mb = nullptr,
                                 const avk_packed_batch *pk = nullptr, const avk_packed_multi_batch *pm = nullptr, const PackedOnDevice *pre = nullptr,
                                 const avk_packed_escapes *esc = nullptr) {
     const bool has_esc = (pk || pm) && esc_present(esc);
@@ -1032,7 +1033,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
     const auto t_start = now();
-    hipStream_t s = ctx->up_stream ? ctx->up_stream : ctx->stream; /* (the asynchronous boundary packs on a stream of its own, beside the solve of the batch before) */
+    hipStream_t s = spec.up_stream ? spec.up_stream : ctx->stream; /* (the asynchronous boundary packs on a stream of its own, beside the solve of the batch before) */
     uint64_t *pk_totals = nullptr; /* packed form: device words {sum of the call counts, sum of the allele lengths} */
     avk_dev_batch *db = new avk_dev_batch();
     db->dev_packed = true;
@@ -1054,7 +1055,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     };
     auto bail = [&](int code) {
         (void)hipStreamSynchronize(s);
-        (void)hipStreamSynchronize((ctx->up_side ? ctx->up_side : ctx->lane_stream4)); /* (the side stream of the upload: prefix sums, widening, the cleared scratch) */
+        (void)hipStreamSynchronize((spec.up_side ? spec.up_side : ctx->lane_stream4)); /* (the side stream of the upload: prefix sums, widening, the cleared scratch) */
         for (void *p : temps) pool_release(ctx, p);
         release_pooled(ctx, db);
         delete db;
@@ -1175,7 +1176,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
          * allele bytes) run on a stream of their own beside the copies that follow: dp_variant, the first kernel that needs every byte, starts 0.24 ms earlier.
          * (The copies themselves stay on ONE stream: a large copy queued on a second stream now and then blocks the host for 7 to 9 ms inside hipMemcpyAsync —
          * the runtime bringing up another copy engine — which made one call in fifty 16 ms long.) */
-        hipStream_t side = (ctx->up_side ? ctx->up_side : ctx->lane_stream4);
+        hipStream_t side = (spec.up_side ? spec.up_side : ctx->lane_stream4);
         auto side_fail = [&](int code) { /* nothing of this call may still be in flight on the side stream when its buffers go back */
             (void)hipStreamSynchronize(side);
             return bail(code);
@@ -1188,7 +1189,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
                    is_pinned(pk->start, n * 4) && is_pinned(pk->len, n * 2) && is_pinned(pk->contig_idx, n * 2) && is_pinned(pk->var_rel_pos, nv * 2) &&
                    is_pinned(pk->var_type_zyg, nv) && is_pinned(pk->var_raw_space, nv * 4);
         };
-        const bool eligible = (ctx->pack_chunks > 0 || ctx->pack_queue_early) && packed_src && nv && !pre && !ctx->up_stream && !copies_by_kernel(ctx) && all_pinned();
+        const bool eligible = (ctx->pack_chunks > 0 || ctx->pack_queue_early) && packed_src && nv && !pre && !spec.up_stream && !copies_by_kernel(ctx) && all_pinned();
         queue_early = eligible;
         if (eligible && ctx->pack_chunks > 0) {
             chunk_plan = avk::pc::plan_chunks(n, nv, ctx->pack_chunks, (uint64_t)ctx->pack_chunk_floor);
@@ -1287,7 +1288,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
                 segs.back().then_call = [&queue_chunk, j] { queue_chunk(j); };
             }
             for (CopySeg &sg : segs) sg.direct = true;
-            rc = copy_in(ctx, segs);
+            rc = copy_in(ctx, segs, spec.up_stream != nullptr);
         } else
         { /* (the escape lists, when there are any, in front of the array whose event releases the widening; none: the order of the copies is what it was) */
             std::vector<CopySeg> segs = {{pk->t_cnt, p_tc, n}, {pk->q_cnt, p_qc, n}, {pk->a0_len, p_a0, nv}, {pk->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork},
@@ -1304,7 +1305,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
                 };
                 for (CopySeg &sg : segs) sg.direct = true;
             }
-            rc = copy_in(ctx, segs);
+            rc = copy_in(ctx, segs, spec.up_stream != nullptr);
         }
         early_variant = packed_src && nv != 0;
         mark(1);
@@ -1348,7 +1349,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             {b->t_cnt, db->d_in_t_cnt, n * 4}, {b->q_cnt, db->d_in_q_cnt, n * 4}, {b->contig_idx, d_contig, b->contig_idx ? n * 4 : 0},
             {b->var_pos, d_pos, nv * 8}, {b->a0_off, d_a0o, nv * 8}, {b->a1_off, d_a1o, nv * 8}, {b->a0_len, d_a0l, nv * 4}, {b->a1_len, d_a1l, nv * 4},
             {b->var_raw_space, d_raw, b->var_raw_space ? nv * 4 : 0}, {b->var_type, d_type, nv}, {b->var_zyg, d_zyg, nv}, {b->allele_bytes, d_alleles, alen}};
-        rc = copy_in(ctx, segs);
+        rc = copy_in(ctx, segs, spec.up_stream != nullptr);
         if (rc) return bail(rc);
     } else if (mb) { /* the MultiRegions as they are, one kernel that writes a region per input pair; the call arrays are shared by all pairs */
         const uint64_t nm = mb->n_regions;
@@ -1368,7 +1369,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             uint64_t *p_aoff = (uint64_t *)tmp((nv + 1) * 8), *p_sums = (uint64_t *)tmp(((size_t)nb_r + nb_v + 4) * 8);
             uint64_t *p_ioff = has_esc ? (uint64_t *)tmp((ni + 1) * 8) : db->d_m_in_off; /* (with escapes: the sums over the narrow counts; the widening writes the true offsets) */
             if (rc) return bail(rc);
-            hipStream_t side = (ctx->up_side ? ctx->up_side : ctx->lane_stream4); /* as for avk_packed_batch: copies on the context's stream, counts first; prefix sums and widening beside them */
+            hipStream_t side = (spec.up_side ? spec.up_side : ctx->lane_stream4); /* as for avk_packed_batch: copies on the context's stream, counts first; prefix sums and widening beside them */
             auto side_fail = [&](int code) {
                 (void)hipStreamSynchronize(side);
                 return bail(code);
@@ -1380,7 +1381,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
                 segs.push_back({pm->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid});
                 segs.push_back({pm->var_raw_space, d_raw, has_raw ? nv * 4 : 0});
                 segs.push_back({pm->allele_bytes, d_alleles, alen});
-                rc = copy_in(ctx, segs);
+                rc = copy_in(ctx, segs, spec.up_stream != nullptr);
             }
             if (rc) return bail(rc);
             hipError_t ec = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0);
@@ -1421,7 +1422,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
                                      {mb->contig_idx, m_contig, has_contig ? nm * 4 : 0}, {mb->var_pos, d_pos, nv * 8}, {mb->a0_off, d_a0o, nv * 8}, {mb->a1_off, d_a1o, nv * 8},
                                      {mb->a0_len, d_a0l, nv * 4}, {mb->a1_len, d_a1l, nv * 4}, {mb->var_raw_space, d_raw, has_raw ? nv * 4 : 0}, {mb->var_type, d_type, nv},
                                      {mb->var_zyg, d_zyg, nv}, {mb->allele_bytes, d_alleles, alen}};
-        rc = copy_in(ctx, segs);
+        rc = copy_in(ctx, segs, spec.up_stream != nullptr);
         if (rc) return bail(rc);
         }
         dpk::DpPairs c;
@@ -1445,7 +1446,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
         std::vector<CopySeg> segs = {{cb->start, c_start, n * 4}, {cb->len, c_len, n * 4}, {cb->v_off, c_voff, n * 4}, {cb->t_cnt, c_tc, n * 2}, {cb->q_cnt, c_qc, n * 2},
                                      {cb->contig_idx, c_contig, has_contig ? n * 4 : 0}, {cb->var_pos, c_pos, nv * 4}, {cb->a_off, c_aoff, nv * 4}, {cb->var_type_zyg, c_tz, nv},
                                      {cb->a0_len, d_a0l, nv * 4}, {cb->a1_len, d_a1l, nv * 4}, {cb->var_raw_space, d_raw, has_raw ? nv * 4 : 0}, {cb->allele_bytes, d_alleles, alen}};
-        rc = copy_in(ctx, segs);
+        rc = copy_in(ctx, segs, spec.up_stream != nullptr);
         if (rc) return bail(rc);
         c.contig_idx = c_contig, c.start = c_start, c.len = c_len, c.v_off = c_voff, c.t_cnt = c_tc, c.q_cnt = c_qc, c.var_pos = c_pos, c.a_off = c_aoff, c.a0_len = d_a0l, c.a1_len = d_a1l,
         c.var_raw = nullptr, c.var_type_zyg = c_tz, c.n_regions = n, c.n_variants = nv;
@@ -1512,7 +1513,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
             hipLaunchKernelGGL(avk_dp_scatter_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, s, a);
             x = hipGetLastError();
         }
-        StrataJob *sj = n && ctx->strata_job && !ctx->strata_job->counted ? ctx->strata_job : nullptr; /* (once: the lists do not depend on alt_ed, a second round of the passes leaves them) */
+        StrataJob *sj = n && spec.strata && !spec.strata->counted ? spec.strata : nullptr; /* (once: the lists do not depend on alt_ed, a second round of the passes leaves them) */
         if (x == hipSuccess && sj) x = strata_count_launch(sj->st, a.in, n, sj->d_mask, sj->d_sums, s);
         mark(2);
         if (x == hipSuccess) x = hipMemcpyAsync(hs, a.st, sizeof(dpk::DpState), hipMemcpyDeviceToHost, s);
@@ -1632,7 +1633,7 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     db->dp_args = a;
     const bool clear_beside = n >= 262144; /* (a small batch: the two events between the streams cost more than the fills, 1.16 instead of 0.98 ms per 46,000-region call) */
     if (clear_beside) { /* the batch's partial tallies and counters are cleared beside the writers, on a side stream (in front of the solver launches the two fills took 55 us) */
-        hipStream_t side = (ctx->up_side ? ctx->up_side : ctx->lane_stream4);
+        hipStream_t side = (spec.up_side ? spec.up_side : ctx->lane_stream4);
         hipError_t ez = hipEventRecord(ctx->ev_copy_fork, s); /* the buffers may have been another batch's until here */
         if (ez == hipSuccess) ez = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0);
         if (ez == hipSuccess && db->d_dp_args) ez = hipMemcpyAsync(db->d_dp_args, &db->dp_args, sizeof(dpk::DpArgs), hipMemcpyHostToDevice, side); /* (behind the writers it was
@@ -1662,12 +1663,12 @@ static int upload_device_packed(avk_ctx *ctx, const avk_region_batch *b, const a
     e = hipGetLastError();
     if (e == hipSuccess && clear_beside) e = hipStreamWaitEvent(s, ctx->ev_copy_join, 0); /* the cleared scratch, before anything that follows on this stream */
     if (e != hipSuccess) {
-        (void)hipStreamSynchronize((ctx->up_side ? ctx->up_side : ctx->lane_stream4));
+        (void)hipStreamSynchronize((spec.up_side ? spec.up_side : ctx->lane_stream4));
         return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(e)));
     }
     mark(3);
     for (void *p : temps) pool_release(ctx, p); /* in stream order: the writers above run before anything that is handed these buffers next */
-    if (!ctx->up_stream && ctx->ev_pool_fence) { /* ... which an upload on the packing stream of the asynchronous boundary is not, by itself: it waits for this point once */
+    if (!spec.up_stream && ctx->ev_pool_fence) { /* ... which an upload on the packing stream of the asynchronous boundary is not, by itself: it waits for this point once */
         if (hipEventRecord(ctx->ev_pool_fence, s) == hipSuccess) ctx->pool_fence_pending = true;
         else (void)hipGetLastError();
     }
@@ -1694,7 +1695,7 @@ struct DownloadLater {
     void *lab_host = nullptr;
     size_t lab_bytes = 0;
 };
-static int download_device_packed(avk_ctx *ctx, avk_dev_batch *db, avk_result_batch *out, uint8_t *pair_exact, uint64_t *tally_words /* [AVK_TALLY_STRIDE] */,
+static int download_device_packed(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, avk_result_batch *out, uint8_t *pair_exact, uint64_t *tally_words /* [AVK_TALLY_STRIDE] */,
                                   DownloadLater *later = nullptr) {
     const uint64_t n = db->n_regions, nv = db->n_variants_host;
     hipStream_t s = ctx->stream;
@@ -1758,7 +1759,7 @@ static int download_device_packed(avk_ctx *ctx, avk_dev_batch *db, avk_result_ba
                                     {out->var_class ? out->var_class + db->v_lo : nullptr, o.var_class, out->var_class ? nvr : 0},
                                     {out->var_zyg ? out->var_zyg + db->v_lo : nullptr, o.var_zyg, out->var_zyg ? nvr : 0},
                                     {out->var_packed ? out->var_packed + db->v_lo : nullptr, o.var_packed, out->var_packed ? nvr : 0}};
-        rc = copy_in(ctx, pre);
+        rc = copy_in(ctx, pre, false);
         if (rc) return done(rc);
     }
     if (e == hipSuccess && n) {
@@ -1776,7 +1777,7 @@ static int download_device_packed(avk_ctx *ctx, avk_dev_batch *db, avk_result_ba
         segs.push_back({out->var_zyg ? out->var_zyg + db->v_lo : nullptr, o.var_zyg, out->var_zyg ? nvr : 0});
         segs.push_back({out->var_packed ? out->var_packed + db->v_lo : nullptr, o.var_packed, out->var_packed ? nvr : 0});
     }
-    if (out->group_metrics && ctx->emit_group_metrics && db->d_gm) segs.push_back({out->group_metrics, db->d_gm, n * AVK_N_GROUPS * AVK_N_FIELDS * sizeof(uint32_t)});
+    if (out->group_metrics && spec.emit_gm && db->d_gm) segs.push_back({out->group_metrics, db->d_gm, n * AVK_N_GROUPS * AVK_N_FIELDS * sizeof(uint32_t)});
     if (want_bp_packed) segs.push_back({out->bp_packed, o.bp_packed, n * sizeof(uint32_t)}); /* (the spilled groups and their count: below, behind the other copies — or the split call's, once) */
     else if (out->bp_off && out->bp_groups && db->d_bp && db->d_bp_off && db->last_mode == 0) {
         segs.push_back({out->bp_off, db->d_bp_off, (n + 1) * sizeof(uint32_t)});

@@ -353,7 +353,6 @@ struct avk_ctx {
      * packed arrays of batch k + 1 cross the bus while batch k is being solved, the results of batch k while batch k + 1 is being packed */
     hipStream_t copy_in_stream = nullptr, copy_out_stream = nullptr;
     hipStream_t pack_stream = nullptr, pack_side_stream = nullptr; /* the packing kernels of a submitted batch, beside the solver launches of the batch before */
-    hipStream_t up_stream = nullptr, up_side = nullptr;            /* set while avk_compare_packed_submit runs upload_device_packed */
     hipEvent_t ev_packed = nullptr, ev_pool_fence = nullptr;
     bool pool_fence_pending = false; /* buffers went back to the pool in the order of the context's stream since the packing stream last waited for it */
     int64_t async_pack_stream = 1;                                 /* option: 0 = a submitted batch is packed on the context's stream, behind the solve of the batch before */
@@ -370,8 +369,6 @@ struct avk_ctx {
     int64_t label_lds_bytes = 0;       /* LDS a launch of avk_label_tally_compact_kernel gets (0: not asked yet) */
     int64_t mergecount_lds_bytes = 0;  /* ... and a launch of avk_merge_count_kernel */
     int last_merge_counts_on_device = 0; /* the last avk_merge_packed_counts with counters made them by kernel */
-    struct StrataJob *strata_job = nullptr; /* set while avk_compare_packed_strata uploads its batch: the packer's region passes also count the batch's containment lists (avk_strata.inl) */
-    struct LabelFix *label_fix = nullptr; /* set while a one-call form with labels downloads: the capacity retry adds the repaired regions' blocks to the labels' sums */
     /* options */
     int64_t lds_bytes_per_wave = 10 * 1024;
     int64_t lds_ed_cap = 48;
@@ -610,6 +607,30 @@ void free_batch_buffers(avk_dev_batch *db) {
 }
 
 } // namespace
+
+/* What one call wants of the functions below it, handed down by argument: the context holds options and resources, nothing that lasts for one call only. */
+struct StrataJob;
+struct LabelFix;
+struct CallSpec {
+    bool emit_gm = true, emit_bp = false;                /* what the kernels write for this batch: per-region metric blocks, compact BASEPAIR groups */
+    hipStream_t up_stream = nullptr, up_side = nullptr;  /* the upload's streams; NULL: the context's stream and lane_stream4 (a submitted batch packs on streams of its own) */
+    StrataJob *strata = nullptr;                         /* the packer's region passes also count the batch's containment lists (avk_compare_packed_strata) */
+    LabelFix *label_fix = nullptr;                       /* the capacity retry of the download adds the repaired regions' blocks to the labels' sums */
+};
+/* the resident entry points: the options as they are at the time of the call */
+static CallSpec call_spec(const avk_ctx *ctx) {
+    CallSpec spec;
+    spec.emit_gm = ctx->emit_group_metrics != 0, spec.emit_bp = ctx->emit_bp_groups != 0;
+    return spec;
+}
+/* the one-call forms: per-region metric blocks only when the caller has an array for them, the groups when it has a place for them — or the call reads them itself
+ * (need_bp: the label kernel, the shared spill list of a split call) */
+static CallSpec call_spec(const avk_ctx *ctx, const avk_result_batch *out, bool need_bp) {
+    CallSpec spec = call_spec(ctx);
+    if (!out->group_metrics) spec.emit_gm = false;
+    if (need_bp || ((out->bp_off || (out->bp_packed && out->bp_spilled)) && out->bp_groups)) spec.emit_bp = true;
+    return spec;
+}
 
 #include "avk_devpack_host.inl"
 
@@ -1152,12 +1173,12 @@ int avk_group_metrics_from_compact(const avk_region_batch *b, uint64_t r, const 
     return k == hi ? 0 : AVK_E_ARG;
 }
 
-static int upload_internal(avk_ctx *ctx, const avk_region_batch *batch, bool pairs_mode, avk_dev_batch **out) {
+static int upload_internal(avk_ctx *ctx, const CallSpec &spec, const avk_region_batch *batch, bool pairs_mode, avk_dev_batch **out) {
     if (!ctx || !batch || !out) return AVK_E_ARG;
     *out = nullptr;
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->device_pack) return upload_device_packed(ctx, batch, nullptr, pairs_mode, out);
+    if (ctx->device_pack) return upload_device_packed(ctx, spec, batch, nullptr, pairs_mode, out);
     const bool timing = getenv("AVK_TIMING") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -1283,7 +1304,7 @@ static int upload_internal(avk_ctx *ctx, const avk_region_batch *batch, bool pai
     return 0;
 }
 
-int avk_batch_upload(avk_ctx *ctx, const avk_region_batch *batch, avk_dev_batch **out) { return upload_internal(ctx, batch, false, out); }
+int avk_batch_upload(avk_ctx *ctx, const avk_region_batch *batch, avk_dev_batch **out) { return ctx ? upload_internal(ctx, call_spec(ctx), batch, false, out) : AVK_E_ARG; }
 
 void avk_batch_free(avk_ctx *ctx, avk_dev_batch *db) {
     if (!db) return;
@@ -1414,7 +1435,7 @@ static int ensure_pair_table(avk_ctx *ctx, uint32_t max_branch_factor, hipStream
  * memory is scrubbed when it is handed out (75 ms per GB): n_cus x 3 workgroups were 3 of the 4.8 GB a process's first whole-genome call waited 0.39 s for
  * (profiles/r05_first_solve.txt); the step does not notice the difference (profiles/r05_quad_sweeps.txt) */
 #define AVK_HBM_BLOCKS_BESIDE_LANES 192u
-static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_config *cfg, void *tally_dev, uint32_t mode) {
+static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, const avk_compare_config *cfg, void *tally_dev, uint32_t mode) {
     if (!ctx || !db || !cfg) return AVK_E_ARG;
     AVK_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = db->n_regions;
@@ -1525,11 +1546,11 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
         AVK_HIP(ctx, hipMemsetAsync(db->d_counters, 0, AVK_N_COUNTERS * sizeof(uint32_t), ctx->stream));
     }
     db->scratch_clean = false;
-    if (ctx->emit_bp_groups && mode == 0 && !db->d_bp && db->d_bp_off) {
+    if (spec.emit_bp && mode == 0 && !db->d_bp && db->d_bp_off) {
         int rc = db->dev_packed ? pool_alloc_t(ctx, db, &db->d_bp, (size_t)db->n_bp_groups * 4 + 4) : dev_alloc(ctx, &db->d_bp, (size_t)db->n_bp_groups * 4 + 4);
         if (rc) return rc;
     }
-    if (ctx->emit_group_metrics && !db->d_gm) {
+    if (spec.emit_gm && !db->d_gm) {
         int rc = db->dev_packed ? pool_alloc_t(ctx, db, &db->d_gm, (size_t)n * AVK_N_GROUPS * AVK_N_FIELDS + 4) : dev_alloc(ctx, &db->d_gm, (size_t)n * AVK_N_GROUPS * AVK_N_FIELDS);
         if (rc) return rc;
     }
@@ -1554,12 +1575,12 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
     a.tier[3].ws_bytes = (uint64_t)big_bytes;
     a.tier[3].ed_cap = 0;
     a.region_out = db->d_region_out;
-    a.group_metrics = ctx->emit_group_metrics ? db->d_gm : nullptr;
+    a.group_metrics = spec.emit_gm ? db->d_gm : nullptr;
     a.var_out = db->d_var_out;
     a.seq_bytes = cfg->enable_sequences ? db->d_seq : nullptr;
     a.seq_len = cfg->enable_sequences ? db->d_seqlen : nullptr;
     a.tally = db->d_partials;
-    if (ctx->emit_bp_groups && mode == 0 && db->d_bp) {
+    if (spec.emit_bp && mode == 0 && db->d_bp) {
         a.bp_off = db->d_bp_off;
         a.bp_out = db->d_bp;
     }
@@ -2143,14 +2164,14 @@ static int run_internal(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_confi
     db->last_cfg = *cfg;
     db->last_mode = mode;
     db->has_run = true;
-    db->bp_valid = ctx->emit_bp_groups && mode == 0 && db->d_bp != nullptr;
+    db->bp_valid = spec.emit_bp && mode == 0 && db->d_bp != nullptr;
     if (timed) AVK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->ev_valid = timed;
     return 0;
 }
 
 int avk_compare_resident(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_config *cfg, void *tally_dev) {
-    return run_internal(ctx, db, cfg, tally_dev, 0);
+    return ctx ? run_internal(ctx, call_spec(ctx), db, cfg, tally_dev, 0) : AVK_E_ARG;
 }
 
 #ifdef AVK_QUAD_WAVE_LOG
@@ -2277,7 +2298,10 @@ struct CapacityFix {
 };
 } // namespace
 
-static int rerun_capacity_regions(avk_ctx *ctx, avk_dev_batch *db, const std::vector<uint32_t> &cap, bool want_gm, bool want_seq, bool want_bp, uint64_t slice_bytes, CapacityFix *fx) {
+static int results_download_impl(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, avk_result_batch *out, struct DownloadLater *later, const uint64_t *tally_ready);
+/* sub_spec: what the sub-batch's kernels write (emit_gm, emit_bp) — the blocks and groups the repair needs, whatever the caller's batch ran with */
+static int rerun_capacity_regions(avk_ctx *ctx, const CallSpec &sub_spec, avk_dev_batch *db, const std::vector<uint32_t> &cap, bool want_seq, uint64_t slice_bytes, CapacityFix *fx) {
+    const bool want_gm = sub_spec.emit_gm, want_bp = sub_spec.emit_bp;
     const uint64_t m = cap.size();
     std::vector<uint64_t> rid(m), st(m), en(m), toff(m), qoff(m), vpos, a0off, a1off;
     std::vector<uint32_t> cidx(m), tcnt(m), qcnt(m), vraw, a0len, a1len;
@@ -2335,13 +2359,11 @@ static int rerun_capacity_regions(avk_ctx *ctx, avk_dev_batch *db, const std::ve
         fx->gm.assign(m * AVK_N_GROUPS * AVK_N_FIELDS, 0);
         o.group_metrics = fx->gm.data();
     }
-    const int64_t keep_bp = ctx->emit_bp_groups;
     if (want_bp) {
         fx->bp_off.assign(m + 1, 0);
         fx->bp.assign((m + nvs + 1) * 4, 0);
         o.bp_off = fx->bp_off.data(), o.bp_groups = fx->bp.data();
     }
-    ctx->emit_bp_groups = want_bp ? 1 : 0;
     if (want_seq) {
         fx->seq_off.assign(m, 0), fx->seq_stride.assign(m, 0), fx->seq_len.assign(m * 5, 0);
         uint64_t total = 0;
@@ -2353,19 +2375,18 @@ static int rerun_capacity_regions(avk_ctx *ctx, avk_dev_batch *db, const std::ve
         fx->seq.assign(total + 16, 0);
         o.seq_bytes = fx->seq.data(), o.seq_off = fx->seq_off.data(), o.seq_stride = fx->seq_stride.data(), o.seq_len = fx->seq_len.data();
     }
-    /* the big-slice tier alone */
-    const int64_t keep[] = {ctx->lds_bytes_per_wave, ctx->lds2_bytes_per_wave, ctx->ws_bytes_per_wave, ctx->big_ws_bytes, ctx->big_waves, ctx->lane_kernel, ctx->capacity_retry,
-                            ctx->emit_group_metrics};
+    /* the big-slice tier alone.  The one save and restore of options left: run_internal reads these seven in some thirty places, and they are tuning the caller set
+     * for its own batches, not something a call decides — nothing between the two lines below returns early */
+    const int64_t keep[] = {ctx->lds_bytes_per_wave, ctx->lds2_bytes_per_wave, ctx->ws_bytes_per_wave, ctx->big_ws_bytes, ctx->big_waves, ctx->lane_kernel, ctx->capacity_retry};
     ctx->lds_bytes_per_wave = 0, ctx->lds2_bytes_per_wave = 0, ctx->ws_bytes_per_wave = 0, ctx->big_ws_bytes = (int64_t)slice_bytes, ctx->big_waves = m < 4 ? (int64_t)m : 4,
-    ctx->lane_kernel = 0, ctx->capacity_retry = 0, ctx->emit_group_metrics = want_gm ? 1 : 0;
+    ctx->lane_kernel = 0, ctx->capacity_retry = 0;
     avk_dev_batch *sub = nullptr;
-    int rc = upload_internal(ctx, &b, false, &sub);
-    if (!rc) rc = run_internal(ctx, sub, &db->last_cfg, nullptr, 0);
-    if (!rc) rc = avk_results_download(ctx, sub, &o);
+    int rc = upload_internal(ctx, sub_spec, &b, false, &sub);
+    if (!rc) rc = run_internal(ctx, sub_spec, sub, &db->last_cfg, nullptr, 0);
+    if (!rc) rc = results_download_impl(ctx, sub_spec, sub, &o, nullptr, nullptr);
     if (sub) avk_batch_free(ctx, sub);
     ctx->lds_bytes_per_wave = keep[0], ctx->lds2_bytes_per_wave = keep[1], ctx->ws_bytes_per_wave = keep[2], ctx->big_ws_bytes = keep[3], ctx->big_waves = keep[4],
-    ctx->lane_kernel = keep[5], ctx->capacity_retry = keep[6], ctx->emit_group_metrics = keep[7];
-    ctx->emit_bp_groups = keep_bp;
+    ctx->lane_kernel = keep[5], ctx->capacity_retry = keep[6];
     return rc;
 }
 
@@ -2407,7 +2428,7 @@ static void label_fix_add(LabelFix *lf, uint64_t r, const uint32_t *block) {
 }
 /* avk_results_download in one piece (later == NULL), or in the two pieces of the asynchronous boundary: everything up to the queued copies (later given, tally_ready
  * NULL), and everything behind them — the tally, the statistics, the capacity retry — once the copies have arrived (tally_ready = the batch's tally words) */
-static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_batch *out, DownloadLater *later, const uint64_t *tally_ready) {
+static int results_download_impl(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, avk_result_batch *out, DownloadLater *later, const uint64_t *tally_ready) {
     if (!ctx || !db || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
     AVK_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = db->n_regions, nv = db->n_variants_dev;
@@ -2450,7 +2471,7 @@ static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_bat
     if (tally_ready) { /* the copies were queued earlier and have arrived */
         t_copied = std::chrono::steady_clock::now();
     } else if (db->dev_packed) { /* the caller's layout is made on the device (dp_unpack); the copies land in the caller's arrays */
-        const int rc = download_device_packed(ctx, db, out, nullptr, tally.data(), later);
+        const int rc = download_device_packed(ctx, spec, db, out, nullptr, tally.data(), later);
         if (rc || later) return rc;
         t_copied = std::chrono::steady_clock::now();
         if (want_seq) {
@@ -2460,7 +2481,7 @@ static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_bat
     } else {
         std::vector<uint32_t> rout(n * 4 + 4), vout(nv + 1);
         D2H(rout.data(), db->d_region_out, n * 4 * sizeof(uint32_t));
-        if (out->group_metrics && ctx->emit_group_metrics && db->d_gm) D2H(out->group_metrics, db->d_gm, n * AVK_N_GROUPS * AVK_N_FIELDS * sizeof(uint32_t));
+        if (out->group_metrics && spec.emit_gm && db->d_gm) D2H(out->group_metrics, db->d_gm, n * AVK_N_GROUPS * AVK_N_FIELDS * sizeof(uint32_t));
         if (out->bp_off && out->bp_groups && db->d_bp && db->d_bp_off) {
             D2H(out->bp_off, db->d_bp_off, (n + 1) * sizeof(uint32_t));
             D2H(out->bp_groups, db->d_bp, (size_t)db->n_bp_groups * 4 * sizeof(uint32_t));
@@ -2520,13 +2541,15 @@ static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_bat
         for (uint64_t slice = 1ull << 30; !cap.empty() && slice <= (16ull << 30); slice <<= 2) {
             if ((int64_t)slice <= ctx->big_ws_bytes) continue;
             CapacityFix fx;
-            const bool dev_gm = ctx->emit_group_metrics && db->d_gm; /* the batch keeps per-region blocks on the device (avk_label_tallies reads them) */
+            const bool dev_gm = spec.emit_gm && db->d_gm; /* the batch keeps per-region blocks on the device (avk_label_tallies reads them) */
             /* ... or the compact view avk_label_tallies_compact reads: the repaired region's per-call words and BASEPAIR groups are patched as well */
             const bool dev_compact = db->dev_packed && db->bp_valid && db->d_bp && db->d_bp_off && db->d_var_out;
-            const bool want_gm = (out->group_metrics && ctx->emit_group_metrics && db->d_gm) || dev_gm || ctx->label_fix != nullptr;
+            const bool want_gm = (out->group_metrics && spec.emit_gm && db->d_gm) || dev_gm || spec.label_fix != nullptr;
             const bool want_bp_words = out->bp_packed && out->bp_spilled && out->bp_groups && db->d_bp;
             const bool want_bp = (out->bp_off && out->bp_groups && db->d_bp) || want_bp_words || dev_compact;
-            const int rc = rerun_capacity_regions(ctx, db, cap, want_gm, want_seq, want_bp, slice, &fx);
+            CallSpec sub_spec;
+            sub_spec.emit_gm = want_gm, sub_spec.emit_bp = want_bp;
+            const int rc = rerun_capacity_regions(ctx, sub_spec, db, cap, want_seq, slice, &fx);
             if (rc == AVK_E_OOM) break; /* the device cannot hold slices of this size: the regions keep their status */
             if (rc) { /* reported after the statistics and the shared slices are back as they were (below) */
                 retry_rc = rc;
@@ -2572,7 +2595,7 @@ static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_bat
                     }
                     if (ew != hipSuccess && !retry_rc) retry_rc = fail(ctx, AVK_E_HIP, "capacity retry: %s", hipGetErrorString(ew));
                 }
-                if (ctx->label_fix && fx.status[k] == 0) label_fix_add(ctx->label_fix, r, fx.gm.data() + (size_t)k * AVK_N_GROUPS * AVK_N_FIELDS);
+                if (spec.label_fix && fx.status[k] == 0) label_fix_add(spec.label_fix, r, fx.gm.data() + (size_t)k * AVK_N_GROUPS * AVK_N_FIELDS);
                 if (want_gm && out->group_metrics) memcpy(out->group_metrics + (size_t)r * AVK_N_GROUPS * AVK_N_FIELDS, fx.gm.data() + (size_t)k * AVK_N_GROUPS * AVK_N_FIELDS, sizeof(uint32_t) * AVK_N_GROUPS * AVK_N_FIELDS);
                 if (want_bp_words) { /* the packed form: the repaired region's groups join the spilled ones */
                     const uint32_t ng = fx.bp_off[k + 1] - fx.bp_off[k], at = out->bp_spilled[0];
@@ -2612,7 +2635,7 @@ static int results_download_impl(avk_ctx *ctx, avk_dev_batch *db, avk_result_bat
 
 extern "C" {
 
-int avk_results_download(avk_ctx *ctx, avk_dev_batch *db, avk_result_batch *out) { return results_download_impl(ctx, db, out, nullptr, nullptr); }
+int avk_results_download(avk_ctx *ctx, avk_dev_batch *db, avk_result_batch *out) { return ctx ? results_download_impl(ctx, call_spec(ctx), db, out, nullptr, nullptr) : AVK_E_ARG; }
 
 /* ---- the asynchronous boundary: one context, batches in flight -------------------------------------------------------------------------------
  * The reference streams its regions through a rayon loop and collects at the end (src/main.rs:251-268); a caller with several batches gets the same here:
@@ -2625,7 +2648,7 @@ struct avk_ticket {
     avk_dev_batch *db = nullptr;
     avk_result_batch out;
     DownloadLater later;
-    int64_t keep_gm = 0, keep_bp = 0;
+    CallSpec spec; /* what the batch was submitted with: the copies out were queued with it, avk_wait finishes the download with it */
     /* submitted with labels: the lists (the caller's arrays, read again should the capacity retry repair a region), where the sums go, the device sums */
     bool has_lab = false;
     avk_region_labels lab;
@@ -2690,6 +2713,16 @@ static int labels_launch(avk_ctx *ctx, avk_dev_batch *db, const uint64_t *d_off,
         AVK_HIP(ctx, hipGetLastError());
     }
     if (timing && ctx->ev_lab1) (void)hipEventRecord(ctx->ev_lab1, s);
+    return 0;
+}
+/* ... with the sums cleared first (clear) and queued back to the host behind the kernels (host given), all on the context's stream */
+static int label_sums_queue(avk_ctx *ctx, avk_dev_batch *db, const void *d_off, const void *d_idx, uint32_t n_labels, void *d_out, bool clear, uint64_t *host) {
+    const size_t bytes = (size_t)n_labels * AVK_TALLY_LEN * sizeof(uint64_t);
+    hipError_t e = clear ? hipMemsetAsync(d_out, 0, bytes, ctx->stream) : hipSuccess;
+    if (e != hipSuccess) return fail(ctx, AVK_E_HIP, host ? "label tallies failed: %s" : "label sums: %s", hipGetErrorString(e)); /* (no host copy: the submit, with its own text) */
+    const int rc = labels_launch(ctx, db, (const uint64_t *)d_off, (const uint32_t *)d_idx, n_labels, (uint64_t *)d_out, ctx->stream);
+    if (rc) return rc;
+    if (host && (e = hipMemcpyAsync(host, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(e));
     return 0;
 }
 static void labels_timing_print(avk_ctx *ctx, const char *route, uint32_t n_labels, uint64_t n, uint64_t n_idx) { /* behind a synchronisation with the kernels' stream */
@@ -2896,43 +2929,38 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     const double ts1 = now_ms();
     sl.busy = true;
     t->slot = slot;
-    t->keep_gm = ctx->emit_group_metrics, t->keep_bp = ctx->emit_bp_groups;
-    if (!out->group_metrics) ctx->emit_group_metrics = 0;
-    if (bp_queueable || lab) ctx->emit_bp_groups = 1;
+    CallSpec spec = t->spec = call_spec(ctx, out, bp_queueable || lab); /* (the ticket keeps the emit flags; the packing streams are this call's alone) */
     t->later.h_tally = sl.h_tally, t->later.ev_unpacked = sl.ev_unpacked, t->later.ev_done = sl.ev_done;
     t->later.shared_spill = bp_queueable ? shared_spill : nullptr, t->later.shared_spill_count = bp_queueable ? shared_spill_count : nullptr;
     /* Packing on a stream of its own: its kernels stream the batch's arrays through HBM while the solver launches of the batch before are busy with their searches,
      * and the plan's round trip to the host no longer waits for that solve.  Pool buffers stay ordered: what this upload is handed was released either by an upload
      * (on this same stream) or by a batch whose work is over (avk_wait). */
     if (ctx->async_pack_stream) {
-        ctx->up_stream = ctx->pack_stream, ctx->up_side = ctx->pack_side_stream;
+        spec.up_stream = ctx->pack_stream, spec.up_side = ctx->pack_side_stream;
         if (ctx->pool_fence_pending) { /* a synchronous upload released buffers behind kernels of the context's stream that may still be queued */
             (void)hipStreamWaitEvent(ctx->pack_stream, ctx->ev_pool_fence, 0);
             ctx->pool_fence_pending = false;
         }
     }
-    rc = upload_device_packed(ctx, nullptr, nullptr, false, &t->db, nullptr, batch, nullptr, &pre, esc);
-    if (!rc && ctx->up_stream) {
-        hipError_t e = hipEventRecord(ctx->ev_packed, ctx->up_stream);
+    rc = upload_device_packed(ctx, spec, nullptr, nullptr, false, &t->db, nullptr, batch, nullptr, &pre, esc);
+    if (!rc && spec.up_stream) {
+        hipError_t e = hipEventRecord(ctx->ev_packed, spec.up_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ev_packed, 0);
         if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(e));
     }
-    ctx->up_stream = nullptr, ctx->up_side = nullptr;
     const double ts2 = now_ms();
-    if (!rc) rc = avk_compare_resident(ctx, t->db, cfg, nullptr);
+    if (!rc) rc = run_internal(ctx, spec, t->db, cfg, nullptr, 0);
     if (!rc && lab) { /* behind the solve's tally reduce: the label kernel, its sums cross with the results */
         const size_t words = (size_t)lab->n_labels * AVK_TALLY_LEN;
         rc = pool_alloc(ctx, &t->d_lab_out, words * sizeof(uint64_t));
-        if (!rc && hipMemsetAsync(t->d_lab_out, 0, words * sizeof(uint64_t), ctx->stream) != hipSuccess) rc = fail(ctx, AVK_E_HIP, "label sums: %s", hipGetErrorString(hipGetLastError()));
-        if (!rc) rc = labels_launch(ctx, t->db, pre.lab_off, pre.lab_idx, lab->n_labels, (uint64_t *)t->d_lab_out, ctx->stream);
+        if (!rc) rc = label_sums_queue(ctx, t->db, pre.lab_off, pre.lab_idx, lab->n_labels, (uint64_t *)t->d_lab_out, true, nullptr);
         t->later.lab_dev = t->d_lab_out, t->later.lab_host = sl.h_labels, t->later.lab_bytes = words * sizeof(uint64_t);
     }
     const double ts3 = now_ms();
-    if (!rc) rc = results_download_impl(ctx, t->db, out, &t->later, nullptr);
+    if (!rc) rc = results_download_impl(ctx, spec, t->db, out, &t->later, nullptr);
     if (timing)
         fprintf(stderr, "avk submit (slot %d): called at %.3f ms; copies queued +%.3f, packed and planned +%.3f, solver launches queued +%.3f, results queued +%.3f\n", slot, ts0, ts1 - ts0,
                 ts2 - ts0, ts3 - ts0, now_ms() - ts0);
-    ctx->emit_group_metrics = t->keep_gm, ctx->emit_bp_groups = t->keep_bp;
     if (rc) { /* nothing of this batch stays in flight */
         (void)hipStreamSynchronize(ctx->copy_in_stream);
         (void)hipStreamSynchronize(ctx->pack_stream);
@@ -2965,13 +2993,10 @@ int avk_wait(avk_ctx *ctx, avk_ticket *t) {
     const auto tw1 = std::chrono::steady_clock::now();
     int rc = e == hipSuccess ? 0 : fail(ctx, AVK_E_HIP, "waiting for the batch's results failed: %s", hipGetErrorString(e));
     if (!rc) { /* the tally, the statistics and — should a region have come back AVK_ST_CAPACITY — the retry, as in avk_results_download */
-        const int64_t gm = ctx->emit_group_metrics;
-        if (!t->out.group_metrics) ctx->emit_group_metrics = 0;
         LabelFix lf{&t->lab, t->lab_out};
-        if (t->has_lab) ctx->label_fix = &lf; /* (a region the retry repairs was not solved when the label kernel ran) */
-        rc = results_download_impl(ctx, t->db, &t->out, nullptr, sl.h_tally);
-        ctx->label_fix = nullptr;
-        ctx->emit_group_metrics = gm;
+        CallSpec spec = t->spec;
+        if (t->has_lab) spec.label_fix = &lf; /* (a region the retry repairs was not solved when the label kernel ran) */
+        rc = results_download_impl(ctx, spec, t->db, &t->out, nullptr, sl.h_tally);
         if (!rc && t->has_lab) {
             const size_t words = (size_t)t->lab.n_labels * AVK_TALLY_LEN;
             for (size_t k = 0; k < words; ++k) t->lab_out[k] += sl.h_labels[k];
@@ -3177,20 +3202,24 @@ int avk_ctx_warmup(avk_ctx *ctx, uint64_t n_regions_hint, uint64_t n_variants_hi
     return 0;
 }
 
-int avk_batch_upload_compact(avk_ctx *ctx, const avk_compact_batch *batch, avk_dev_batch **out) {
+static int upload_compact(avk_ctx *ctx, const CallSpec &spec, const avk_compact_batch *batch, avk_dev_batch **out) {
     if (!ctx || !batch || !out) return AVK_E_ARG;
     *out = nullptr;
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    return upload_device_packed(ctx, nullptr, batch, false, out);
+    return upload_device_packed(ctx, spec, nullptr, batch, false, out);
 }
+int avk_batch_upload_compact(avk_ctx *ctx, const avk_compact_batch *batch, avk_dev_batch **out) { return ctx ? upload_compact(ctx, call_spec(ctx), batch, out) : AVK_E_ARG; }
 
-int avk_batch_upload_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, avk_dev_batch **out) {
+static int upload_packed(avk_ctx *ctx, const CallSpec &spec, const avk_packed_batch *batch, const avk_packed_escapes *esc, avk_dev_batch **out) {
     if (!ctx || !batch || !out) return AVK_E_ARG;
     *out = nullptr;
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    return upload_device_packed(ctx, nullptr, nullptr, false, out, nullptr, batch, nullptr, nullptr, esc);
+    return upload_device_packed(ctx, spec, nullptr, nullptr, false, out, nullptr, batch, nullptr, nullptr, esc);
+}
+int avk_batch_upload_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, avk_dev_batch **out) {
+    return ctx ? upload_packed(ctx, call_spec(ctx), batch, esc, out) : AVK_E_ARG;
 }
 int avk_batch_upload_packed(avk_ctx *ctx, const avk_packed_batch *batch, avk_dev_batch **out) { return avk_batch_upload_packed_esc(ctx, batch, nullptr, out); }
 
@@ -3316,107 +3345,6 @@ static int compare_packed_split(avk_ctx *ctx, const avk_packed_batch *batch, con
 int avk_compare_packed(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out) {
     return avk_compare_packed_esc(ctx, batch, nullptr, cfg, out);
 }
-int avk_compare_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_compare_config *cfg, avk_result_batch *out) {
-    if (!ctx || !batch || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
-    ctx->last_one_shot = 0;
-    if (!esc_present(esc)) esc = nullptr;
-    if (ctx->split_parts > 1 && ctx->d_ref && !esc) { /* (the split cuts the narrow arrays by their own running sums: a batch with escapes runs whole) */
-        const int rs = compare_packed_split(ctx, batch, cfg, out);
-        if (rs >= 0) return rs;
-    }
-    avk_dev_batch *db = nullptr;
-    const int64_t keep_gm = ctx->emit_group_metrics, keep_bp = ctx->emit_bp_groups;
-    if (!out->group_metrics) ctx->emit_group_metrics = 0;
-    if ((out->bp_off || (out->bp_packed && out->bp_spilled)) && out->bp_groups) ctx->emit_bp_groups = 1;
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = avk_batch_upload_packed_esc(ctx, batch, esc, &db);
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
-    const auto t2 = std::chrono::steady_clock::now();
-    if (!rc) rc = avk_results_download(ctx, db, out);
-    const auto t3 = std::chrono::steady_clock::now();
-    ctx->emit_group_metrics = keep_gm, ctx->emit_bp_groups = keep_bp;
-    if (db) {
-        ctx->last_one_shot = 1;
-        avk_batch_free(ctx, db);
-    }
-    if (getenv("AVK_TIMING")) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "avk compare packed: upload %.3f ms, launches %.3f ms, download %.3f ms, free %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3),
-                ms(t3, std::chrono::steady_clock::now()));
-        if (!rc && ctx->ev_tl[4] && ctx->ev_valid) { /* the same call on the device's clock, free-running (no profiler): events on the context's stream */
-            float c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, c7 = 0;
-            if (!ctx->tl_region_valid || !ctx->ev_tl[5] || hipEventElapsedTime(&c7, ctx->ev_tl[0], ctx->ev_tl[5]) != hipSuccess) c7 = -1.f, (void)hipGetLastError(); /* (-1: this call recorded none) */
-            if (hipEventElapsedTime(&c1, ctx->ev_tl[0], ctx->ev_tl[1]) == hipSuccess && hipEventElapsedTime(&c2, ctx->ev_tl[0], ctx->ev_tl[2]) == hipSuccess &&
-                hipEventElapsedTime(&c3, ctx->ev_tl[0], ctx->ev_tl[3]) == hipSuccess && hipEventElapsedTime(&c4, ctx->ev_tl[0], ctx->ev0) == hipSuccess &&
-                hipEventElapsedTime(&c5, ctx->ev_tl[0], ctx->ev1) == hipSuccess && hipEventElapsedTime(&c6, ctx->ev_tl[0], ctx->ev_tl[4]) == hipSuccess)
-                fprintf(stderr, "avk compare packed, device clock from the first copy: copies in done %.3f ms, region pass done %.3f, work order done %.3f, record writers done %.3f, solver launches %.3f .. %.3f, results out %.3f\n",
-                        c1, c7, c2, c3, c4, c5, c6);
-            else
-                (void)hipGetLastError();
-            /* where each chain of the launch graph ended, from the first solver launch (events of this call only when the batch used the chain) */
-            const struct { const char *what; hipEvent_t ev; } chains[] = {{"LDS solo", ctx->ev_join}, {"HBM solo", ctx->ev_join2}, {"wide", ctx->ev_wide}, {"lane stream 1", ctx->ev_lane_join},
-                {"lane stream 2", ctx->ev_lane_join2}, {"lane stream 3", ctx->ev_lane_join3}, {"lane stream 4", ctx->ev_lane_join4}, {"early hand-backs", ctx->ev_lane_early},
-                {"hand-back launches", ctx->ev_lane_done}};
-            fprintf(stderr, "avk compare packed, chains end (ms after the first solver launch):");
-            for (const auto &c : chains) {
-                float t = 0;
-                if (c.ev && hipEventElapsedTime(&t, ctx->ev0, c.ev) == hipSuccess) fprintf(stderr, " %s %.3f;", c.what, t);
-                else (void)hipGetLastError();
-            }
-            fprintf(stderr, " all %.3f\n", c5 - c4);
-        }
-    }
-    return rc;
-}
-
-int avk_compare_compact(avk_ctx *ctx, const avk_compact_batch *batch, const avk_compare_config *cfg, avk_result_batch *out) {
-    if (!ctx || !batch || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
-    ctx->last_one_shot = 0;
-    avk_dev_batch *db = nullptr;
-    const int64_t keep_gm = ctx->emit_group_metrics, keep_bp = ctx->emit_bp_groups;
-    if (!out->group_metrics) ctx->emit_group_metrics = 0;
-    if ((out->bp_off || (out->bp_packed && out->bp_spilled)) && out->bp_groups) ctx->emit_bp_groups = 1;
-    int rc = avk_batch_upload_compact(ctx, batch, &db);
-    if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
-    if (!rc) rc = avk_results_download(ctx, db, out);
-    ctx->emit_group_metrics = keep_gm, ctx->emit_bp_groups = keep_bp;
-    if (db) {
-        ctx->last_one_shot = 1;
-        avk_batch_free(ctx, db);
-    }
-    return rc;
-}
-
-int avk_compare_batch(avk_ctx *ctx, const avk_region_batch *batch, const avk_compare_config *cfg, avk_result_batch *out) {
-    if (!ctx || !batch || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
-    if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
-    ctx->last_one_shot = 0;
-    avk_dev_batch *db = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    /* per-region metric blocks only when the caller has an array for them */
-    const int64_t keep_gm = ctx->emit_group_metrics, keep_bp = ctx->emit_bp_groups;
-    if (!out->group_metrics) ctx->emit_group_metrics = 0;
-    if ((out->bp_off || (out->bp_packed && out->bp_spilled)) && out->bp_groups) ctx->emit_bp_groups = 1;
-    int rc = avk_batch_upload(ctx, batch, &db);
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
-    const auto t2 = std::chrono::steady_clock::now();
-    if (!rc) rc = avk_results_download(ctx, db, out);
-    const auto t3 = std::chrono::steady_clock::now();
-    ctx->emit_group_metrics = keep_gm, ctx->emit_bp_groups = keep_bp;
-    if (db) {
-        ctx->last_one_shot = db->dev_packed ? 1 : 0;
-        avk_batch_free(ctx, db);
-    }
-    if (getenv("AVK_TIMING")) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "avk compare batch: upload %.3f ms, launches %.3f ms, download %.3f ms, free %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3),
-                ms(t3, std::chrono::steady_clock::now()));
-    }
-    return rc;
-}
-
 int avk_dwfa_script_batch(avk_ctx *ctx, int engine, uint32_t n_scripts, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *base_off, const uint64_t *other_off,
                           const uint64_t *step_off, const uint8_t *step_op, const uint32_t *step_blen, const uint32_t *step_olen, uint32_t *step_ed,
                           int32_t *step_status, uint32_t wf_cap, uint32_t *final_wf, uint32_t *final_wf_len) {
@@ -3558,59 +3486,13 @@ int avk_label_tallies_compact(avk_ctx *ctx, avk_dev_batch *db, const avk_region_
     void *d_off = nullptr, *d_idx = nullptr, *d_out = nullptr;
     std::vector<uint64_t> host(words, 0);
     int rc = labels_upload(ctx, n, lab, &d_off, &d_idx, &d_out);
-    if (!rc) rc = labels_launch(ctx, db, (const uint64_t *)d_off, (const uint32_t *)d_idx, lab->n_labels, (uint64_t *)d_out, ctx->stream);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && e == hipSuccess) e = hipGetLastError();
+    if (!rc) rc = label_sums_queue(ctx, db, d_off, d_idx, lab->n_labels, d_out, false, host.data()); /* (labels_upload cleared the sums) */
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
     pool_release(ctx, d_off), pool_release(ctx, d_idx), pool_release(ctx, d_out);
     if (rc) return rc;
     if (e != hipSuccess) return fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(e));
     labels_timing_print(ctx, "resident", lab->n_labels, n, lab->label_off[n]);
     for (size_t k = 0; k < words; ++k) out[k] += host[k];
-    return 0;
-}
-
-int avk_compare_packed_labels(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_region_labels *lab, const avk_compare_config *cfg,
-                              avk_result_batch *out, uint64_t *label_tallies) {
-    if (!lab || lab->n_labels == 0) return avk_compare_packed_esc(ctx, batch, esc, cfg, out); /* the call without labels, launch for launch */
-    if (!batch) return AVK_E_ARG;
-    { /* (first of all: these refusals need no device, avk_last_error(NULL) has their text when ctx is NULL) */
-        const int rl = labels_check(ctx, batch->n_regions, lab, label_tallies);
-        if (rl) return rl;
-    }
-    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
-    ctx->last_one_shot = 0;
-    if (!esc_present(esc)) esc = nullptr;
-    const uint64_t n = batch->n_regions;
-    const size_t words = (size_t)lab->n_labels * AVK_TALLY_LEN;
-    avk_dev_batch *db = nullptr;
-    const int64_t keep_gm = ctx->emit_group_metrics, keep_bp = ctx->emit_bp_groups;
-    if (!out->group_metrics) ctx->emit_group_metrics = 0;
-    ctx->emit_bp_groups = 1; /* the groups are what the label kernel reads, whether the caller asked for them or not */
-    void *d_off = nullptr, *d_idx = nullptr, *d_out = nullptr;
-    std::vector<uint64_t> host(words, 0);
-    int rc = avk_batch_upload_packed_esc(ctx, batch, esc, &db);
-    if (!rc) rc = labels_upload(ctx, n, lab, &d_off, &d_idx, &d_out);
-    if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
-    if (!rc) rc = labels_launch(ctx, db, (const uint64_t *)d_off, (const uint32_t *)d_idx, lab->n_labels, (uint64_t *)d_out, ctx->stream);
-    if (!rc && hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        rc = fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(hipGetLastError()));
-    if (!rc) { /* (the download waits for the stream; a region its capacity retry repairs is added on the host: it was not solved when the label kernel ran) */
-        LabelFix lf{lab, label_tallies};
-        ctx->label_fix = &lf;
-        rc = avk_results_download(ctx, db, out);
-        ctx->label_fix = nullptr;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->emit_group_metrics = keep_gm, ctx->emit_bp_groups = keep_bp;
-    pool_release(ctx, d_off), pool_release(ctx, d_idx), pool_release(ctx, d_out);
-    if (db) {
-        ctx->last_one_shot = 1;
-        avk_batch_free(ctx, db);
-    }
-    if (rc) return rc;
-    labels_timing_print(ctx, "one call", lab->n_labels, n, lab->label_off[n]);
-    for (size_t k = 0; k < words; ++k) label_tallies[k] += host[k];
     return 0;
 }
 
@@ -3750,11 +3632,8 @@ int avk_label_tallies_strata(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *
     void *d_out = nullptr;
     int rc = strata_lists_make(ctx, db, st, true, L);
     if (!rc) rc = pool_alloc(ctx, &d_out, words * 8);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
-    if (!rc && e == hipSuccess) rc = labels_launch(ctx, db, (const uint64_t *)L.d_off, (const uint32_t *)L.d_idx, st->n_labels, (uint64_t *)d_out, ctx->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && e == hipSuccess) e = hipGetLastError();
+    if (!rc) rc = label_sums_queue(ctx, db, L.d_off, L.d_idx, st->n_labels, d_out, true, host.data());
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
     const uint64_t n_idx = L.total;
     strata_lists_release(ctx, L);
     pool_release(ctx, d_out);
@@ -3765,6 +3644,138 @@ int avk_label_tallies_strata(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *
     return 0;
 }
 
+/* AVK_TIMING: the packed call on the device's clock, free-running (no profiler): events on the context's stream */
+static void packed_timeline_print(avk_ctx *ctx) {
+    if (!ctx->ev_tl[4] || !ctx->ev_valid) return;
+    float c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, c7 = 0;
+    if (!ctx->tl_region_valid || !ctx->ev_tl[5] || hipEventElapsedTime(&c7, ctx->ev_tl[0], ctx->ev_tl[5]) != hipSuccess) c7 = -1.f, (void)hipGetLastError(); /* (-1: this call recorded none) */
+    if (hipEventElapsedTime(&c1, ctx->ev_tl[0], ctx->ev_tl[1]) == hipSuccess && hipEventElapsedTime(&c2, ctx->ev_tl[0], ctx->ev_tl[2]) == hipSuccess &&
+        hipEventElapsedTime(&c3, ctx->ev_tl[0], ctx->ev_tl[3]) == hipSuccess && hipEventElapsedTime(&c4, ctx->ev_tl[0], ctx->ev0) == hipSuccess &&
+        hipEventElapsedTime(&c5, ctx->ev_tl[0], ctx->ev1) == hipSuccess && hipEventElapsedTime(&c6, ctx->ev_tl[0], ctx->ev_tl[4]) == hipSuccess)
+        fprintf(stderr, "avk compare packed, device clock from the first copy: copies in done %.3f ms, region pass done %.3f, work order done %.3f, record writers done %.3f, solver launches %.3f .. %.3f, results out %.3f\n",
+                c1, c7, c2, c3, c4, c5, c6);
+    else
+        (void)hipGetLastError();
+    /* where each chain of the launch graph ended, from the first solver launch (events of this call only when the batch used the chain) */
+    const struct { const char *what; hipEvent_t ev; } chains[] = {{"LDS solo", ctx->ev_join}, {"HBM solo", ctx->ev_join2}, {"wide", ctx->ev_wide}, {"lane stream 1", ctx->ev_lane_join},
+        {"lane stream 2", ctx->ev_lane_join2}, {"lane stream 3", ctx->ev_lane_join3}, {"lane stream 4", ctx->ev_lane_join4}, {"early hand-backs", ctx->ev_lane_early},
+        {"hand-back launches", ctx->ev_lane_done}};
+    fprintf(stderr, "avk compare packed, chains end (ms after the first solver launch):");
+    for (const auto &c : chains) {
+        float t = 0;
+        if (c.ev && hipEventElapsedTime(&t, ctx->ev0, c.ev) == hipSuccess) fprintf(stderr, " %s %.3f;", c.what, t);
+        else (void)hipGetLastError();
+    }
+    fprintf(stderr, " all %.3f\n", c5 - c4);
+}
+
+/* ---- the synchronous one-call forms ------------------------------------------------------------------------------------------------------------
+ * One driver: upload (the form's own), solve, download, free — with the label kernel and the copy of its sums between solve and download for the two forms with
+ * labels.  Their lists are the caller's arrays, uploaded behind the batch (lab), or made on the device: counted inside the upload, filled behind it (st). */
+struct LabelStage {
+    const avk_region_labels *lab;
+    const avk_strata *st;
+    uint64_t *sums; /* the caller's [n_labels * AVK_TALLY_LEN]: gains the sums */
+};
+static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_result_batch *out, uint64_t n, const char *timed_as,
+                            const std::function<int(const CallSpec &, avk_dev_batch **)> &upload, const LabelStage *ls = nullptr) {
+    ctx->last_one_shot = 0;
+    CallSpec spec = call_spec(ctx, out, ls != nullptr); /* (the groups are what the label kernel reads, whether the caller asked for them or not) */
+    const uint32_t n_labels = !ls ? 0 : ls->st ? ls->st->n_labels : ls->lab->n_labels;
+    std::vector<uint64_t> host((size_t)n_labels * AVK_TALLY_LEN, 0);
+    avk_dev_batch *db = nullptr;
+    StrataLists L; /* (the caller's lists use d_off and d_idx only) */
+    void *d_out = nullptr;
+    StrataJob job{ls ? ls->st : nullptr, nullptr, nullptr};
+    int rc = 0;
+    if (job.st) { /* pass 1 of the lists runs inside the upload, behind the packer's region passes; their size comes back with the plan */
+        rc = strata_lists_alloc(ctx, job.st, n, L);
+        if (!rc) rc = pool_alloc(ctx, &d_out, host.size() * 8);
+        job.d_mask = (uint32_t *)L.d_mask, job.d_sums = (uint64_t *)L.d_sums;
+        spec.strata = &job;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!rc) rc = upload(spec, &db);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!rc && job.st) {
+        if (n && !job.counted) rc = fail(ctx, AVK_E_STATE, "strata lists: the upload did not count them");
+        L.total = job.total;
+        if (!rc) rc = pool_alloc(ctx, &L.d_idx, (size_t)L.total * 4 + 16);
+        if (!rc) {
+            hipError_t e = hipMemsetAsync(d_out, 0, host.size() * 8, ctx->stream);
+            if (e == hipSuccess) e = strata_fill_launch(job.st, n, (const uint32_t *)L.d_mask, (const uint64_t *)L.d_sums, (uint64_t *)L.d_off, (uint32_t *)L.d_idx, L.total, ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata lists failed: %s", hipGetErrorString(e));
+        }
+    } else if (!rc && ls)
+        rc = labels_upload(ctx, n, ls->lab, &L.d_off, &L.d_idx, &d_out);
+    if (!rc) rc = run_internal(ctx, spec, db, cfg, nullptr, 0);
+    const auto t2 = std::chrono::steady_clock::now();
+    if (!rc && ls) rc = label_sums_queue(ctx, db, L.d_off, L.d_idx, n_labels, d_out, false, host.data());
+    if (!rc) { /* (the download waits for the stream; a region its capacity retry repairs is added on the host: it was not solved when the label kernel ran) */
+        LabelFix lf{ls ? ls->lab : nullptr, ls ? ls->sums : nullptr}; /* the caller's lists; device lists: a repaired region's entries are fetched from there */
+        if (job.st) lf.d_off = (const uint64_t *)L.d_off, lf.d_idx = (const uint32_t *)L.d_idx, lf.n = n;
+        if (ls) spec.label_fix = &lf;
+        rc = results_download_impl(ctx, spec, db, out, nullptr, nullptr);
+        if (!rc && lf.err != hipSuccess) rc = fail(ctx, AVK_E_HIP, "label tallies: the lists of the regions the capacity retry repaired could not be fetched: %s", hipGetErrorString(lf.err));
+    }
+    const auto t3 = std::chrono::steady_clock::now();
+    const uint64_t n_strata_idx = L.total;
+    if (ls) (void)hipStreamSynchronize(ctx->stream);
+    strata_lists_release(ctx, L);
+    pool_release(ctx, d_out);
+    if (db) {
+        ctx->last_one_shot = db->dev_packed ? 1 : 0;
+        avk_batch_free(ctx, db);
+    }
+    if (timed_as && getenv("AVK_TIMING")) {
+        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        fprintf(stderr, "avk compare %s: upload %.3f ms, launches %.3f ms, download %.3f ms, free %.3f ms\n", timed_as, ms(t0, t1), ms(t1, t2), ms(t2, t3),
+                ms(t3, std::chrono::steady_clock::now()));
+    }
+    if (rc || !ls) return rc;
+    labels_timing_print(ctx, job.st ? "one call, device lists" : "one call", n_labels, n, job.st ? n_strata_idx : ls->lab->label_off[n]);
+    for (size_t k = 0; k < host.size(); ++k) ls->sums[k] += host[k];
+    return 0;
+}
+
+int avk_compare_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_compare_config *cfg, avk_result_batch *out) {
+    if (!ctx || !batch || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    ctx->last_one_shot = 0;
+    if (!esc_present(esc)) esc = nullptr;
+    if (ctx->split_parts > 1 && ctx->d_ref && !esc) { /* (the split cuts the narrow arrays by their own running sums: a batch with escapes runs whole) */
+        const int rs = compare_packed_split(ctx, batch, cfg, out);
+        if (rs >= 0) return rs;
+    }
+    const int rc = compare_one_call(ctx, cfg, out, batch->n_regions, "packed", [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); });
+    if (!rc && getenv("AVK_TIMING")) packed_timeline_print(ctx);
+    return rc;
+}
+
+int avk_compare_compact(avk_ctx *ctx, const avk_compact_batch *batch, const avk_compare_config *cfg, avk_result_batch *out) {
+    if (!ctx || !batch || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_compact(ctx, spec, batch, db); });
+}
+
+int avk_compare_batch(avk_ctx *ctx, const avk_region_batch *batch, const avk_compare_config *cfg, avk_result_batch *out) {
+    if (!ctx || !batch || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
+    return compare_one_call(ctx, cfg, out, batch->n_regions, "batch", [&](const CallSpec &spec, avk_dev_batch **db) { return upload_internal(ctx, spec, batch, false, db); });
+}
+
+int avk_compare_packed_labels(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_region_labels *lab, const avk_compare_config *cfg,
+                              avk_result_batch *out, uint64_t *label_tallies) {
+    if (!lab || lab->n_labels == 0) return avk_compare_packed_esc(ctx, batch, esc, cfg, out); /* the call without labels, launch for launch */
+    if (!batch) return AVK_E_ARG;
+    { /* (first of all: these refusals need no device, avk_last_error(NULL) has their text when ctx is NULL) */
+        const int rl = labels_check(ctx, batch->n_regions, lab, label_tallies);
+        if (rl) return rl;
+    }
+    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    if (!esc_present(esc)) esc = nullptr;
+    const LabelStage ls{lab, nullptr, label_tallies};
+    return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, &ls);
+}
+
 int avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg, avk_result_batch *out,
                               uint64_t *label_tallies) {
     if (!st || st->n_labels == 0) return avk_compare_packed_esc(ctx, batch, esc, cfg, out); /* the call without labels, launch for launch */
@@ -3773,57 +3784,9 @@ int avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, const
     if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
     if (strata_handle_check(ctx, st)) return AVK_E_ARG;
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->last_one_shot = 0;
     if (!esc_present(esc)) esc = nullptr;
-    const uint64_t n = batch->n_regions;
-    const size_t words = (size_t)st->n_labels * AVK_TALLY_LEN;
-    avk_dev_batch *db = nullptr;
-    const int64_t keep_gm = ctx->emit_group_metrics, keep_bp = ctx->emit_bp_groups;
-    if (!out->group_metrics) ctx->emit_group_metrics = 0;
-    ctx->emit_bp_groups = 1; /* the groups are what the label kernel reads, whether the caller asked for them or not */
-    StrataLists L;
-    void *d_out = nullptr;
-    std::vector<uint64_t> host(words, 0);
-    int rc = strata_lists_alloc(ctx, st, n, L);
-    if (!rc) rc = pool_alloc(ctx, &d_out, words * 8);
-    if (!rc) { /* pass 1 of the lists runs inside the upload, behind the packer's region passes; their size comes back with the plan */
-        StrataJob job{st, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums};
-        ctx->strata_job = &job;
-        rc = avk_batch_upload_packed_esc(ctx, batch, esc, &db);
-        ctx->strata_job = nullptr;
-        if (!rc && n && !job.counted) rc = fail(ctx, AVK_E_STATE, "strata lists: the upload did not count them");
-        L.total = job.total;
-    }
-    if (!rc) rc = pool_alloc(ctx, &L.d_idx, (size_t)L.total * 4 + 16);
-    if (!rc) {
-        hipError_t e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
-        if (e == hipSuccess) e = strata_fill_launch(st, n, (const uint32_t *)L.d_mask, (const uint64_t *)L.d_sums, (uint64_t *)L.d_off, (uint32_t *)L.d_idx, L.total, ctx->stream);
-        if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata lists failed: %s", hipGetErrorString(e));
-    }
-    if (!rc) rc = avk_compare_resident(ctx, db, cfg, nullptr);
-    if (!rc) rc = labels_launch(ctx, db, (const uint64_t *)L.d_off, (const uint32_t *)L.d_idx, st->n_labels, (uint64_t *)d_out, ctx->stream);
-    if (!rc && hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        rc = fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(hipGetLastError()));
-    if (!rc) { /* (the download waits for the stream; a region its capacity retry repairs is added on the host, its list fetched from the device) */
-        LabelFix lf{nullptr, label_tallies, (const uint64_t *)L.d_off, (const uint32_t *)L.d_idx, n};
-        ctx->label_fix = &lf;
-        rc = avk_results_download(ctx, db, out);
-        ctx->label_fix = nullptr;
-        if (!rc && lf.err != hipSuccess) rc = fail(ctx, AVK_E_HIP, "label tallies: the lists of the regions the capacity retry repaired could not be fetched: %s", hipGetErrorString(lf.err));
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->emit_group_metrics = keep_gm, ctx->emit_bp_groups = keep_bp;
-    const uint64_t n_idx = L.total;
-    strata_lists_release(ctx, L);
-    pool_release(ctx, d_out);
-    if (db) {
-        ctx->last_one_shot = 1;
-        avk_batch_free(ctx, db);
-    }
-    if (rc) return rc;
-    labels_timing_print(ctx, "one call, device lists", st->n_labels, n, n_idx);
-    for (size_t k = 0; k < words; ++k) label_tallies[k] += host[k];
-    return 0;
+    const LabelStage ls{nullptr, st, label_tallies};
+    return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, &ls);
 }
 
 /* solve_merge_region's pairwise test (merge_solver.rs:128-147) for every region of the batch: the "truth"
@@ -3836,18 +3799,17 @@ int avk_optimize_pairs_batch(avk_ctx *ctx, const avk_region_batch *batch, uint32
     cfg.enable_sequences = 0;
     cfg.enable_exact_shortcut = 0;
     avk_dev_batch *db = nullptr;
-    int rc = upload_internal(ctx, batch, true, &db);
+    CallSpec spec = call_spec(ctx);
+    spec.emit_gm = false; /* the pair solve writes no metric blocks */
+    int rc = upload_internal(ctx, spec, batch, true, &db);
     if (rc) return rc;
-    const int64_t keep = ctx->emit_group_metrics;
-    ctx->emit_group_metrics = 0;
-    rc = run_internal(ctx, db, &cfg, nullptr, 1);
-    ctx->emit_group_metrics = keep;
+    rc = run_internal(ctx, spec, db, &cfg, nullptr, 1);
     if (!rc && db->dev_packed) { /* status and the exact-match flag in the caller's layout come from dp_unpack */
         avk_result_batch ro;
         memset(&ro, 0, sizeof(ro));
         ro.status = status;
         std::vector<uint64_t> tally((size_t)AVK_TALLY_STRIDE);
-        rc = download_device_packed(ctx, db, &ro, is_exact_match, tally.data());
+        rc = download_device_packed(ctx, spec, db, &ro, is_exact_match, tally.data());
         ctx->last_one_shot = rc == 0;
         memcpy(ctx->last_tiers, tally.data() + AVK_TALLY_LEN, 5 * sizeof(uint64_t));
         ctx->last_lane_solved = tally[AVK_TALLY_LANE_SOLVED];
@@ -4002,14 +3964,13 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
         if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
         AVK_HIP(ctx, hipSetDevice(ctx->device));
         avk_dev_batch *db = nullptr;
-        int rc = upload_device_packed(ctx, nullptr, nullptr, true, &db, mb, nullptr, pm, nullptr, esc);
+        CallSpec spec = call_spec(ctx);
+        spec.emit_gm = false; /* the pair solve writes no metric blocks */
+        int rc = upload_device_packed(ctx, spec, nullptr, nullptr, true, &db, mb, nullptr, pm, nullptr, esc);
         if (rc) return rc;
         avk_compare_config pcfg;
         pcfg.max_branch_factor = cfg->max_branch_factor, pcfg.enable_sequences = 0, pcfg.enable_exact_shortcut = 0;
-        const int64_t keep = ctx->emit_group_metrics;
-        ctx->emit_group_metrics = 0;
-        rc = run_internal(ctx, db, &pcfg, nullptr, 1);
-        ctx->emit_group_metrics = keep;
+        rc = run_internal(ctx, spec, db, &pcfg, nullptr, 1);
         const uint64_t nm = mb->n_regions;
         void *d_st = nullptr, *d_cl = nullptr, *d_mem = nullptr;
         if (!rc) rc = pool_alloc(ctx, &d_st, (nm + 1) * 4);

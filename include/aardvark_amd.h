@@ -355,6 +355,7 @@ int  avk_ctx_set_stream(avk_ctx *ctx, void *hip_stream);
  *   outputs          "emit_group_metrics" (0 = kernels skip the per-region 13 x 22 block; the batch tally is always produced), "emit_bp_groups" (1 = kernels write the
  *                    compact per-region BASEPAIR groups; the one-call entry points switch it on when the caller hands the arrays in), "accumulate_tally" (1 =
  *                    avk_compare_resident ADDS the batch tally to tally_dev)
+ *                    Options are read when a batch is submitted: a batch in flight (avk_compare_packed_submit .. avk_wait) keeps the values of its submit.
  * The launches of one call run on HIP streams side by side; the HIP runtime gives a process 4 hardware queues by default and streams that share one take turns:
  * avk_ctx_create sets GPU_MAX_HW_QUEUES=24 unless the environment already has it (effective when it is the process's first HIP call). */
 int  avk_ctx_set_option(avk_ctx *ctx, const char *name, int64_t value);
