@@ -181,6 +181,14 @@ class AvkResultBatch(C.Structure):
     ]
 
 
+def declare_submit_strata(lib):
+    """avk_compare_packed_submit_strata(avk_ctx *, const avk_packed_batch *, const avk_packed_escapes *, const avk_strata *, const avk_compare_config *,
+    avk_result_batch *, uint64_t *label_tallies, avk_ticket **) -> int: the submit with the resident sets' handle in place of label lists"""
+    vp = C.c_void_p
+    lib.avk_compare_packed_submit_strata.restype = C.c_int
+    lib.avk_compare_packed_submit_strata.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkResultBatch), _p(C.c_uint64), _p(vp)]
+
+
 def _ptr(arr, ctype):
     return arr.ctypes.data_as(_p(ctype))
 

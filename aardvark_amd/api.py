@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
-                   PackedBatch, RegionBatch, ResultBatch, region_labels)
+                   PackedBatch, RegionBatch, ResultBatch, declare_submit_strata, region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -85,6 +85,8 @@ def load_library():
         lib.avk_strata_region_labels.argtypes = [vp, vp, vp, u64p, C.POINTER(C.c_uint32), C.c_uint64]
         lib.avk_label_tallies_strata.argtypes = [vp, vp, vp, u64p]
         lib.avk_compare_packed_strata.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, vp, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p]
+    if hasattr(lib, "avk_compare_packed_submit_strata"):  # the submit with resident sets (AVK_LIB may name an older in-tree build: A/B runs)
+        declare_submit_strata(lib)
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
     lib.avk_results_download.argtypes = [vp, vp, C.POINTER(AvkResultBatch)]
     lib.avk_batch_free.argtypes = [vp, vp]
@@ -319,15 +321,25 @@ class Context:
             self._check(self.lib.avk_compare_packed_esc(self.handle, C.byref(pb), C.byref(esc), C.byref(cfg), C.byref(ro)))
         return res
 
-    def submit_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None):
+    def submit_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None, strata=None):
         """avk_compare_packed_submit: the batch is queued (its copies run beside the kernels of the batch submitted before) -> a Ticket; Ticket.wait() -> ResultBatch.
         `pbatch` and `res` must live in pinned memory (pinned_packed / pinned_results) for the copies to overlap anything; at most four tickets are in flight.
         labels=(n_labels, label_off, label_idx): avk_compare_packed_submit_labels — res.label_tallies holds the per-label sums once wait() has returned (pin the
-        two arrays with host_array for the submit to stay asynchronous)"""
+        two arrays with host_array for the submit to stay asynchronous).
+        strata=a Strata handle (upload_strata): avk_compare_packed_submit_strata — the same sums, the labels read from the masks made on the device; the Ticket
+        keeps the Strata object alive (Strata.free() before wait() is allowed: the library finishes the batch's mask pass first)"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
         pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
         handle = C.c_void_p()
+        if strata is not None:
+            if labels is not None:
+                raise ValueError("labels and strata exclude each other")
+            sums = np.zeros((strata.n_labels, TALLY_LEN), np.uint64) if label_tallies is None else label_tallies
+            self._check(self.lib.avk_compare_packed_submit_strata(self.handle, C.byref(pb), None if esc is None else C.byref(esc), strata.handle, C.byref(cfg), C.byref(ro),
+                                                                  sums.ctypes.data_as(u64p), C.byref(handle)))
+            res.label_tallies = sums
+            return Ticket(self, handle, res, (pbatch, pb, ro, esc, strata, sums))
         if labels is not None:
             lab, keep = region_labels(*labels)
             sums = np.zeros((int(labels[0]), TALLY_LEN), np.uint64) if label_tallies is None else label_tallies

@@ -913,6 +913,13 @@ static hipError_t strata_count_launch(const avk_strata *st, const dpk::DpIn &in,
     hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, s, d_sums, nb, d_sums + nb);
     return hipGetLastError();
 }
+/* pass 1 alone, for a batch whose tally reads the masks themselves (avk_compare_packed_submit_strata): no scan, no list; d_sums[strata_blocks(n)] only takes the
+ * workgroups' counts the kernel writes */
+static hipError_t strata_mask_launch(const avk_strata *st, const dpk::DpIn &in, uint64_t n, uint32_t *d_mask, uint64_t *d_sums, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(avk_strata_mask_kernel, dim3(strata_blocks(n)), dim3(256), 0, s, in, strata_trees(st), (uint32_t)n, d_mask, (unsigned long long *)d_sums);
+    return hipGetLastError();
+}
 /* pass 2: the offsets, and with d_idx the indices (idx_cap entries of room) */
 static hipError_t strata_fill_launch(const avk_strata *st, uint64_t n, const uint32_t *d_mask, const uint64_t *d_sums, uint64_t *d_off, uint32_t *d_idx, uint64_t idx_cap, hipStream_t s) {
     if (!n) return hipMemsetAsync(d_off, 0, 8, s);
@@ -921,13 +928,15 @@ static hipError_t strata_fill_launch(const avk_strata *st, uint64_t n, const uin
     return hipGetLastError();
 }
 /* avk_compare_packed_strata: pass 1 rides behind the packer's region passes, and the number of list entries comes back with the packer's state block — the
- * call's one round trip — so the index array is sized without a round trip of its own */
+ * call's one round trip — so the index array is sized without a round trip of its own.  mask_only (a submitted batch): the mask pass alone, on the upload's
+ * stream; nothing comes back, total stays 0. */
 struct StrataJob {
     const avk_strata *st;
     uint32_t *d_mask;
     uint64_t *d_sums;
     uint64_t total = 0;
     bool counted = false;
+    bool mask_only = false;
 };
 
 struct PackedOnDevice {
@@ -1514,13 +1523,15 @@ static int upload_device_packed(avk_ctx *ctx, const CallSpec &spec, const avk_re
             x = hipGetLastError();
         }
         StrataJob *sj = n && spec.strata && !spec.strata->counted ? spec.strata : nullptr; /* (once: the lists do not depend on alt_ed, a second round of the passes leaves them) */
-        if (x == hipSuccess && sj) x = strata_count_launch(sj->st, a.in, n, sj->d_mask, sj->d_sums, s);
+        const bool sj_total = sj && !sj->mask_only;
+        if (x == hipSuccess && sj) x = sj_total ? strata_count_launch(sj->st, a.in, n, sj->d_mask, sj->d_sums, s) : strata_mask_launch(sj->st, a.in, n, sj->d_mask, sj->d_sums, s);
         mark(2);
         if (x == hipSuccess) x = hipMemcpyAsync(hs, a.st, sizeof(dpk::DpState), hipMemcpyDeviceToHost, s);
         if (x == hipSuccess && pk_totals) x = hipMemcpyAsync(hs + 1, pk_totals, has_esc ? 24 : 16, hipMemcpyDeviceToHost, s); /* (the packed forms' two sums ride along: 16 bytes behind the state block) */
-        if (x == hipSuccess && sj) x = hipMemcpyAsync((uint8_t *)(hs + 1) + 24, sj->d_sums + strata_blocks(n), 8, hipMemcpyDeviceToHost, s); /* (and the lists' size behind those) */
+        if (x == hipSuccess && sj_total) x = hipMemcpyAsync((uint8_t *)(hs + 1) + 24, sj->d_sums + strata_blocks(n), 8, hipMemcpyDeviceToHost, s); /* (and the lists' size behind those) */
         if (x == hipSuccess) x = hipStreamSynchronize(s);
-        if (x == hipSuccess && sj) memcpy(&sj->total, (const uint8_t *)(hs + 1) + 24, 8), sj->counted = true;
+        if (x == hipSuccess && sj_total) memcpy(&sj->total, (const uint8_t *)(hs + 1) + 24, 8);
+        if (x == hipSuccess && sj) sj->counted = true;
         if (x == hipSuccess) engine_rate_check(ctx);
         return x;
     };

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -558,12 +559,19 @@ struct avk_dev_batch {
 };
 
 /* the interval sets of a stratified job, resident in HBM (avk_strata_upload; the layout of avk_strata.inl) */
+/* the batches submitted with a handle and not yet waited for (avk_compare_packed_submit_strata), and the streams their mask passes — the only readers of the
+ * trees — were queued on.  Shared by the handle and those tickets, so a ticket never looks at a handle that may have been freed. */
+struct StrataUse {
+    uint32_t in_flight = 0;
+    std::vector<hipStream_t> streams;
+};
 struct avk_strata {
     avk_ctx *ctx = nullptr;
     uint32_t n_labels = 0, n_contigs = 0;
     uint64_t n_intervals = 0;
     uint64_t *d_tree_off = nullptr;
     uint32_t *d_start = nullptr, *d_end_max = nullptr;
+    std::shared_ptr<StrataUse> use = std::make_shared<StrataUse>();
 };
 
 namespace {
@@ -614,7 +622,8 @@ struct LabelFix;
 struct CallSpec {
     bool emit_gm = true, emit_bp = false;                /* what the kernels write for this batch: per-region metric blocks, compact BASEPAIR groups */
     hipStream_t up_stream = nullptr, up_side = nullptr;  /* the upload's streams; NULL: the context's stream and lane_stream4 (a submitted batch packs on streams of its own) */
-    StrataJob *strata = nullptr;                         /* the packer's region passes also count the batch's containment lists (avk_compare_packed_strata) */
+    StrataJob *strata = nullptr;                         /* the packer's region passes also run the batch's containment pass (avk_compare_packed_strata: masks and the
+                                                          * lists' size; avk_compare_packed_submit_strata: the masks alone) */
     LabelFix *label_fix = nullptr;                       /* the capacity retry of the download adds the repaired regions' blocks to the labels' sums */
 };
 /* the resident entry points: the options as they are at the time of the call */
@@ -2398,11 +2407,26 @@ struct LabelFix {
     uint64_t *out; /* [n_labels * AVK_TALLY_LEN] */
     const uint64_t *d_off = nullptr;
     const uint32_t *d_idx = nullptr;
+    const uint32_t *d_mask = nullptr; /* no lists at all (avk_compare_packed_submit_strata): a repaired region's n_words mask words, word-major over n regions */
+    uint32_t n_words = 0;
     uint64_t n = 0;               /* regions of the batch */
     std::vector<uint64_t> h_off;  /* the device lists' offsets, fetched once, at the first repaired region */
     hipError_t err = hipSuccess;  /* a failed fetch: the call that set the fix up fails with it */
 };
 static void label_fix_add(LabelFix *lf, uint64_t r, const uint32_t *block) {
+    if (!lf->lab && lf->d_mask) { /* one strided copy of the region's words (the mask pass finished before the solve), made into the region's small list */
+        if (lf->err != hipSuccess || !lf->n_words || r >= lf->n) return;
+        std::vector<uint32_t> words(lf->n_words), idx;
+        lf->err = hipMemcpy2D(words.data(), 4, lf->d_mask + r, (size_t)lf->n * 4, 4, lf->n_words, hipMemcpyDeviceToHost);
+        if (lf->err != hipSuccess) return;
+        for (uint32_t w = 0; w < lf->n_words; ++w) /* (set bits lowest first: the order of the kernels' lists) */
+            for (uint32_t x = words[w]; x; x &= x - 1u) idx.push_back(w * 32u + (uint32_t)__builtin_ctz(x));
+        const uint64_t off[2] = {0, idx.size()};
+        const avk_region_labels one{lf->n_words * 32u, off, idx.data()};
+        LabelFix host{&one, lf->out};
+        label_fix_add(&host, 0, block);
+        return;
+    }
     if (!lf->lab) { /* (the list kernels finished before the solve whose results the retry has just read) */
         if (lf->err != hipSuccess) return;
         if (lf->h_off.empty()) {
@@ -2654,13 +2678,22 @@ struct avk_ticket {
     avk_region_labels lab;
     uint64_t *lab_out = nullptr;
     void *d_lab_out = nullptr;
+    /* submitted with resident sets (avk_compare_packed_submit_strata): the job of the packer's mask pass, the masks and the workgroup counts it writes, the number
+     * of labels, and the count it shares with the handle — nothing of the handle itself, which may be freed before avk_wait */
+    bool has_strata = false;
+    StrataJob sjob{nullptr, nullptr, nullptr};
+    uint32_t n_labels = 0;
+    void *d_mask = nullptr, *d_mask_sums = nullptr;
+    std::shared_ptr<StrataUse> strata_use;
 };
 
 /* ---- stratified sums from the compact results (avk_labels.inl) -------------------------------------------------------------------------------- */
 static int64_t label_lds(avk_ctx *ctx) { /* the LDS a launch of the label kernel really gets: the whole CU's where the runtime grants it */
     if (!ctx->label_lds_bytes) {
         int64_t b = 64 * 1024;
-        if (hipFuncSetAttribute((const void *)avk_label_tally_compact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) b = 160 * 1024;
+        if (hipFuncSetAttribute((const void *)avk_label_tally_compact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+            hipFuncSetAttribute((const void *)avk_label_tally_mask_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess)
+            b = 160 * 1024;
         else {
             (void)hipGetLastError();
             int attr = 0;
@@ -2687,14 +2720,17 @@ static int labels_check(avk_ctx *ctx, uint64_t n, const avk_region_labels *lab, 
     if (!label_tallies) return fail(ctx, AVK_E_ARG, "label_tallies missing");
     return 0;
 }
-/* the label kernel over the blocks of labels, on stream s behind the batch's solve: d_out[n_labels * AVK_TALLY_LEN] gains the sums */
-static int labels_launch(avk_ctx *ctx, avk_dev_batch *db, const uint64_t *d_off, const uint32_t *d_idx, uint32_t n_labels, uint64_t *d_out, hipStream_t s) {
+/* the label kernel over the blocks of labels, on stream s behind the batch's solve: d_out[n_labels * AVK_TALLY_LEN] gains the sums.  d_mask given: the labels
+ * come from the strata pass's bit masks (avk_label_tally_mask_kernel), d_off and d_idx are not read. */
+static int labels_launch(avk_ctx *ctx, avk_dev_batch *db, const uint64_t *d_off, const uint32_t *d_idx, uint32_t n_labels, uint64_t *d_out, hipStream_t s,
+                         const uint32_t *d_mask = nullptr) {
     const uint64_t n = db->n_regions;
     if (!n || !n_labels) return 0;
     avk::lb::LbView v;
     memset(&v, 0, sizeof(v));
     v.in = db->dp_args.in, v.vinfo = db->dp_args.vinfo, v.region_out = db->d_region_out, v.var_out = db->d_var_out, v.v_off = db->d_voff, v.bp_off = db->d_bp_off, v.bp = db->d_bp;
-    const uint32_t B = label_block(ctx);
+    uint32_t B = label_block(ctx);
+    if (d_mask && B > AVK_LB_MASK_BLOCK_MAX) B = AVK_LB_MASK_BLOCK_MAX; /* (a lane keeps the block's mask words in registers) */
     const bool timing = getenv("AVK_TIMING") != nullptr;
     if (timing) {
         if (!ctx->ev_lab0 && hipEventCreate(&ctx->ev_lab0) != hipSuccess) ctx->ev_lab0 = nullptr, (void)hipGetLastError();
@@ -2708,19 +2744,22 @@ static int labels_launch(avk_ctx *ctx, avk_dev_batch *db, const uint64_t *d_off,
         const uint32_t per_cu = lds * 2 <= (size_t)label_lds(ctx) ? 2u : 1u;
         uint64_t blocks = (n + 1023) / 1024;
         if (blocks > (uint64_t)ctx->n_cus * per_cu) blocks = (uint64_t)ctx->n_cus * per_cu;
-        hipLaunchKernelGGL(avk_label_tally_compact_kernel, dim3((unsigned)blocks), dim3(1024), lds, s, v, (const unsigned long long *)d_off, d_idx, (uint32_t)n, lo, hi,
-                           (unsigned long long *)d_out);
+        if (d_mask) hipLaunchKernelGGL(avk_label_tally_mask_kernel, dim3((unsigned)blocks), dim3(1024), lds, s, v, d_mask, (uint32_t)n, lo, hi, (unsigned long long *)d_out);
+        else
+            hipLaunchKernelGGL(avk_label_tally_compact_kernel, dim3((unsigned)blocks), dim3(1024), lds, s, v, (const unsigned long long *)d_off, d_idx, (uint32_t)n, lo, hi,
+                               (unsigned long long *)d_out);
         AVK_HIP(ctx, hipGetLastError());
     }
     if (timing && ctx->ev_lab1) (void)hipEventRecord(ctx->ev_lab1, s);
     return 0;
 }
 /* ... with the sums cleared first (clear) and queued back to the host behind the kernels (host given), all on the context's stream */
-static int label_sums_queue(avk_ctx *ctx, avk_dev_batch *db, const void *d_off, const void *d_idx, uint32_t n_labels, void *d_out, bool clear, uint64_t *host) {
+static int label_sums_queue(avk_ctx *ctx, avk_dev_batch *db, const void *d_off, const void *d_idx, uint32_t n_labels, void *d_out, bool clear, uint64_t *host,
+                            const uint32_t *d_mask = nullptr) {
     const size_t bytes = (size_t)n_labels * AVK_TALLY_LEN * sizeof(uint64_t);
     hipError_t e = clear ? hipMemsetAsync(d_out, 0, bytes, ctx->stream) : hipSuccess;
     if (e != hipSuccess) return fail(ctx, AVK_E_HIP, host ? "label tallies failed: %s" : "label sums: %s", hipGetErrorString(e)); /* (no host copy: the submit, with its own text) */
-    const int rc = labels_launch(ctx, db, (const uint64_t *)d_off, (const uint32_t *)d_idx, n_labels, (uint64_t *)d_out, ctx->stream);
+    const int rc = labels_launch(ctx, db, (const uint64_t *)d_off, (const uint32_t *)d_idx, n_labels, (uint64_t *)d_out, ctx->stream, d_mask);
     if (rc) return rc;
     if (host && (e = hipMemcpyAsync(host, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return fail(ctx, AVK_E_HIP, "label tallies failed: %s", hipGetErrorString(e));
     return 0;
@@ -2848,7 +2887,8 @@ static bool packed_inputs_pinned(const avk_packed_batch *batch, const avk_packed
 }
 
 static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket, uint32_t *shared_spill,
-                       uint32_t *shared_spill_count, const avk_packed_escapes *esc = nullptr, const avk_region_labels *lab = nullptr, uint64_t *label_tallies = nullptr);
+                       uint32_t *shared_spill_count, const avk_packed_escapes *esc = nullptr, const avk_region_labels *lab = nullptr, uint64_t *label_tallies = nullptr,
+                       const avk_strata *st = nullptr);
 int avk_compare_packed_submit(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket) {
     return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr);
 }
@@ -2857,10 +2897,12 @@ int avk_compare_packed_submit_esc(avk_ctx *ctx, const avk_packed_batch *batch, c
     return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr, esc);
 }
 /* shared_spill / shared_spill_count: the device list and counter the parts of one split call spill their BASEPAIR groups into (compare_packed_split); with them a
- * batch that returns the packed groups can be queued like any other */
+ * batch that returns the packed groups can be queued like any other.  st (avk_compare_packed_submit_strata, which has checked the handle): the labels come from
+ * the resident sets — the packer's region passes run the mask pass, the tally reads the masks; lab is NULL then. */
 static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_compare_config *cfg, avk_result_batch *out, avk_ticket **ticket, uint32_t *shared_spill,
-                       uint32_t *shared_spill_count, const avk_packed_escapes *esc, const avk_region_labels *lab, uint64_t *label_tallies) {
+                       uint32_t *shared_spill_count, const avk_packed_escapes *esc, const avk_region_labels *lab, uint64_t *label_tallies, const avk_strata *st) {
     if (lab && lab->n_labels == 0) lab = nullptr; /* (no labels: the call without them, launch for launch) */
+    if (st && st->n_labels == 0) st = nullptr;
     if (lab && batch) { /* (first of all: these refusals need no device, avk_last_error(NULL) has their text when ctx is NULL) */
         const int rl = labels_check(ctx, batch->n_regions, lab, label_tallies);
         if (rl) return rl;
@@ -2901,7 +2943,9 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
         return fail(ctx, AVK_E_STATE, "four batches are in flight: avk_wait for one of them first");
     }
     if (slot < 0) { /* solved here and now (it uses no staging slot): a complete ticket on success, no ticket on failure — the caller owns what it is handed */
-        const int rc_now = lab ? avk_compare_packed_labels(ctx, batch, esc, lab, cfg, out, label_tallies) : avk_compare_packed_esc(ctx, batch, esc, cfg, out);
+        const int rc_now = lab  ? avk_compare_packed_labels(ctx, batch, esc, lab, cfg, out, label_tallies)
+                           : st ? avk_compare_packed_strata(ctx, batch, esc, st, cfg, out, label_tallies)
+                                : avk_compare_packed_esc(ctx, batch, esc, cfg, out);
         if (rc_now) {
             delete t;
             return rc_now;
@@ -2913,23 +2957,35 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     avk_ctx::StageSlot &sl = ctx->stage[slot];
     PackedOnDevice pre;
     int rc = stage_layout(ctx, sl, batch, esc, &pre, lab);
-    if (!rc && lab && sl.h_labels_words < (size_t)lab->n_labels * AVK_TALLY_LEN) { /* the pinned block the sums land in */
+    const size_t lab_words = (size_t)(lab ? lab->n_labels : st ? st->n_labels : 0) * AVK_TALLY_LEN;
+    if (!rc && lab_words && sl.h_labels_words < lab_words) { /* the pinned block the sums land in */
         if (sl.h_labels) (void)hipHostFree(sl.h_labels);
         sl.h_labels = nullptr, sl.h_labels_words = 0;
-        hipError_t eh = hipHostMalloc((void **)&sl.h_labels, (size_t)lab->n_labels * AVK_TALLY_LEN * sizeof(uint64_t), hipHostMallocDefault);
+        hipError_t eh = hipHostMalloc((void **)&sl.h_labels, lab_words * sizeof(uint64_t), hipHostMallocDefault);
         if (eh != hipSuccess) rc = fail(ctx, AVK_E_HIP, "pinned block of the label sums: %s", hipGetErrorString(eh));
-        else sl.h_labels_words = (size_t)lab->n_labels * AVK_TALLY_LEN;
+        else sl.h_labels_words = lab_words;
+    }
+    if (!rc && st) { /* the masks of this batch and the workgroup counts the mask kernel writes beside them: the ticket's until avk_wait */
+        rc = pool_alloc(ctx, &t->d_mask, (size_t)n * strata_words(st) * 4 + 16);
+        if (!rc) rc = pool_alloc(ctx, &t->d_mask_sums, ((size_t)strata_blocks(n) + 1) * 8);
     }
     if (rc) {
         (void)hipStreamSynchronize(ctx->copy_in_stream);
+        pool_release(ctx, t->d_mask), pool_release(ctx, t->d_mask_sums);
         delete t;
         return rc;
     }
     if (lab) t->has_lab = true, t->lab = *lab, t->lab_out = label_tallies;
+    if (st) {
+        t->has_strata = true, t->n_labels = st->n_labels, t->lab_out = label_tallies;
+        t->sjob = StrataJob{st, (uint32_t *)t->d_mask, (uint64_t *)t->d_mask_sums};
+        t->sjob.mask_only = true;
+    }
     const double ts1 = now_ms();
     sl.busy = true;
     t->slot = slot;
-    CallSpec spec = t->spec = call_spec(ctx, out, bp_queueable || lab); /* (the ticket keeps the emit flags; the packing streams are this call's alone) */
+    CallSpec spec = t->spec = call_spec(ctx, out, bp_queueable || lab || st); /* (the ticket keeps the emit flags; the packing streams and the mask job are this call's alone) */
+    if (st) spec.strata = &t->sjob;
     t->later.h_tally = sl.h_tally, t->later.ev_unpacked = sl.ev_unpacked, t->later.ev_done = sl.ev_done;
     t->later.shared_spill = bp_queueable ? shared_spill : nullptr, t->later.shared_spill_count = bp_queueable ? shared_spill_count : nullptr;
     /* Packing on a stream of its own: its kernels stream the batch's arrays through HBM while the solver launches of the batch before are busy with their searches,
@@ -2950,6 +3006,13 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
     }
     const double ts2 = now_ms();
     if (!rc) rc = run_internal(ctx, spec, t->db, cfg, nullptr, 0);
+    if (!rc && st && n && !t->sjob.counted) rc = fail(ctx, AVK_E_STATE, "strata masks: the upload did not make them");
+    if (!rc && st) { /* behind the solve's tally reduce: the label kernel on the masks, its sums cross with the results */
+        const size_t words = (size_t)st->n_labels * AVK_TALLY_LEN;
+        rc = pool_alloc(ctx, &t->d_lab_out, words * sizeof(uint64_t));
+        if (!rc) rc = label_sums_queue(ctx, t->db, nullptr, nullptr, st->n_labels, (uint64_t *)t->d_lab_out, true, nullptr, (const uint32_t *)t->d_mask);
+        t->later.lab_dev = t->d_lab_out, t->later.lab_host = sl.h_labels, t->later.lab_bytes = words * sizeof(uint64_t);
+    }
     if (!rc && lab) { /* behind the solve's tally reduce: the label kernel, its sums cross with the results */
         const size_t words = (size_t)lab->n_labels * AVK_TALLY_LEN;
         rc = pool_alloc(ctx, &t->d_lab_out, words * sizeof(uint64_t));
@@ -2969,10 +3032,19 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
         (void)hipStreamSynchronize(ctx->copy_out_stream);
         for (void *p : t->later.temps) pool_release(ctx, p);
         if (t->d_lab_out) pool_release(ctx, t->d_lab_out);
+        pool_release(ctx, t->d_mask), pool_release(ctx, t->d_mask_sums);
         if (t->db) avk_batch_free(ctx, t->db);
         sl.busy = false;
         delete t;
         return rc;
+    }
+    if (st) { /* the handle counts this batch until avk_wait; avk_strata_free meanwhile waits for the stream the mask pass ran on */
+        t->sjob.st = nullptr;
+        t->strata_use = st->use;
+        StrataUse &u = *t->strata_use;
+        const hipStream_t ms = spec.up_stream ? spec.up_stream : ctx->stream;
+        u.in_flight += 1;
+        if (std::find(u.streams.begin(), u.streams.end(), ms) == u.streams.end()) u.streams.push_back(ms);
     }
     ctx->last_one_shot = 1;
     *ticket = t;
@@ -2993,10 +3065,17 @@ int avk_wait(avk_ctx *ctx, avk_ticket *t) {
     const auto tw1 = std::chrono::steady_clock::now();
     int rc = e == hipSuccess ? 0 : fail(ctx, AVK_E_HIP, "waiting for the batch's results failed: %s", hipGetErrorString(e));
     if (!rc) { /* the tally, the statistics and — should a region have come back AVK_ST_CAPACITY — the retry, as in avk_results_download */
-        LabelFix lf{&t->lab, t->lab_out};
+        LabelFix lf{t->has_strata ? nullptr : &t->lab, t->lab_out};
+        if (t->has_strata) lf.d_mask = (const uint32_t *)t->d_mask, lf.n_words = (t->n_labels + 31u) / 32u, lf.n = t->db->n_regions; /* a repaired region's labels: its own mask words */
         CallSpec spec = t->spec;
-        if (t->has_lab) spec.label_fix = &lf; /* (a region the retry repairs was not solved when the label kernel ran) */
+        if (t->has_lab || t->has_strata) spec.label_fix = &lf; /* (a region the retry repairs was not solved when the label kernel ran) */
         rc = results_download_impl(ctx, spec, t->db, &t->out, nullptr, sl.h_tally);
+        if (!rc && lf.err != hipSuccess) rc = fail(ctx, AVK_E_HIP, "label tallies: the mask words of the regions the capacity retry repaired could not be fetched: %s", hipGetErrorString(lf.err));
+        if (!rc && t->has_strata) {
+            const size_t words = (size_t)t->n_labels * AVK_TALLY_LEN;
+            for (size_t k = 0; k < words; ++k) t->lab_out[k] += sl.h_labels[k];
+            labels_timing_print(ctx, "submitted, masks", t->n_labels, t->db->n_regions, 0);
+        }
         if (!rc && t->has_lab) {
             const size_t words = (size_t)t->lab.n_labels * AVK_TALLY_LEN;
             for (size_t k = 0; k < words; ++k) t->lab_out[k] += sl.h_labels[k];
@@ -3004,6 +3083,8 @@ int avk_wait(avk_ctx *ctx, avk_ticket *t) {
         }
     }
     if (t->d_lab_out) pool_release(ctx, t->d_lab_out);
+    pool_release(ctx, t->d_mask), pool_release(ctx, t->d_mask_sums);
+    if (t->strata_use && --t->strata_use->in_flight == 0) t->strata_use->streams.clear();
     /* the batch's buffers go back to the pool: its work is over (the copies out ran behind its last kernel), so whoever is handed them next may use them at once */
     for (void *p : t->later.temps) pool_release(ctx, p);
     if (t->db) {
@@ -3550,6 +3631,8 @@ int avk_strata_upload(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs, const
 void avk_strata_free(avk_ctx *ctx, avk_strata *st) {
     if (!st) return;
     if (ctx) (void)hipSetDevice(ctx->device);
+    if (st->use->in_flight) /* batches submitted with the handle are not waited for yet: their mask passes, the only readers of the trees, must be over */
+        for (const hipStream_t ms : st->use->streams) (void)hipStreamSynchronize(ms);
     if (st->d_tree_off) (void)hipFree(st->d_tree_off);
     if (st->d_start) (void)hipFree(st->d_start);
     if (st->d_end_max) (void)hipFree(st->d_end_max);
@@ -3787,6 +3870,15 @@ int avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, const
     if (!esc_present(esc)) esc = nullptr;
     const LabelStage ls{nullptr, st, label_tallies};
     return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, &ls);
+}
+
+int avk_compare_packed_submit_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg,
+                                     avk_result_batch *out, uint64_t *label_tallies, avk_ticket **ticket) {
+    if (!st || st->n_labels == 0) return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr, esc); /* the submit without labels, launch for launch */
+    if (!ctx) return AVK_E_ARG;
+    if (!label_tallies) return fail(ctx, AVK_E_ARG, "label_tallies missing");
+    if (strata_handle_check(ctx, st)) return AVK_E_ARG;
+    return submit_impl(ctx, batch, cfg, out, ticket, nullptr, nullptr, esc, nullptr, label_tallies, st);
 }
 
 /* solve_merge_region's pairwise test (merge_solver.rs:128-147) for every region of the batch: the "truth"

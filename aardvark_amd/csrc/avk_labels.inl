@@ -8,7 +8,12 @@
  * lb_region_groups below is avk_group_metrics_from_compact (the host's statement of the rule) on that view, one LANE per region — 99.6 % of a genome's regions
  * have at most three calls a side — and lb_region_labels adds its groups to the 64-bit sums of the labels the region's list names.
  *
- * Written against avk_wave.h / DpIn like avk_devpack.inl, so tests/emu/label_emu.cpp runs the same two functions on the CPU against the oracle's blocks.
+ * A batch in flight (avk_compare_packed_submit_strata) has no lists: lb_region_labels_mask reads the region's labels straight from the bit masks the strata mask
+ * pass leaves (avk_strata.inl: 32 labels a word, word-major), so neither the offsets nor an index array — larger than the batch with hundreds of overlapping
+ * labels — exist for the one read they would get.
+ *
+ * Written against avk_wave.h / DpIn like avk_devpack.inl, so tests/emu/label_emu.cpp and tests/emu/label_mask_emu.cpp run the same functions on the CPU against
+ * the oracle's blocks.
  */
 #ifndef AVK_LABELS_INL
 #define AVK_LABELS_INL
@@ -17,6 +22,8 @@
 
 #define AVK_LB_WORDS (AVK_N_GROUPS * AVK_N_FIELDS)
 #define AVK_LB_LABEL_BYTES (AVK_LB_WORDS * 8) /* one label's 64-bit sums in LDS */
+#define AVK_LB_MASK_WORDS 4                                     /* mask words a lane keeps in registers for one launch's block of labels ... */
+#define AVK_LB_MASK_BLOCK_MAX (32 * (AVK_LB_MASK_WORDS - 1) + 1) /* ... which therefore holds at most 97 labels, wherever it starts in its first word (160 KB of LDS: 71) */
 
 namespace avk {
 namespace lb {
@@ -127,6 +134,42 @@ AVK_DEV void lb_region_labels(const LbView &v, u64 r, const u64 *label_off, cons
     });
 }
 
+/* The same lane with the region's labels as BIT MASKS: bit (l & 31) of mask[(l >> 5) * n + r] says region r of n is in label l (sx_mask_at's layout).  The block
+ * [label_lo, label_hi), at most AVK_LB_MASK_BLOCK_MAX labels, lies in words label_lo >> 5 .. (label_hi - 1) >> 5; each is read once into a register — the lanes of
+ * a wave read consecutive words — and the two edge words are cut to the block, which ends on a word only by chance.  A region whose words are all zero reads
+ * nothing else, not even its status.  Set bits are walked lowest first: the order of a list made from the same masks (sx_fill_region), and the same sums. */
+template <class Add>
+AVK_DEV void lb_region_labels_mask(const LbView &v, u64 r, const u32 *mask, u64 n, u32 label_lo, u32 label_hi, u64 *acc, Add &&add) {
+    if (label_hi <= label_lo) return;
+    const u32 w_lo = label_lo >> 5, w_hi = (label_hi - 1u) >> 5;
+    u32 x[AVK_LB_MASK_WORDS];
+    u32 any = 0;
+#pragma unroll
+    for (u32 j = 0; j < AVK_LB_MASK_WORDS; ++j) {
+        const u32 w = w_lo + j;
+        u32 m = 0;
+        if (w <= w_hi) {
+            m = mask[(u64)w * n + r];
+            if (w == w_lo) m &= ~0u << (label_lo & 31u);
+            if (w == w_hi && (label_hi & 31u)) m &= ~0u >> (32u - (label_hi & 31u));
+        }
+        x[j] = m;
+        any |= m;
+    }
+    if (!any || v.region_out[4 * r] != 0) return;
+    lb_region_groups(v, r, [&](u32 g, const u32(&F)[AVK_N_FIELDS]) {
+#pragma unroll
+        for (u32 j = 0; j < AVK_LB_MASK_WORDS; ++j)
+            for (u32 m = x[j]; m; m &= m - 1u) {
+                const u32 l = ((w_lo + j) << 5) + (u32)__builtin_ctz(m);
+                u64 *dst = acc + (u64)(l - label_lo) * AVK_LB_WORDS + g * AVK_N_FIELDS;
+#pragma unroll
+                for (int f = 0; f < AVK_N_FIELDS; ++f)
+                    if (F[f]) add(dst + f, F[f]);
+            }
+    });
+}
+
 } // namespace lb
 } // namespace avk
 
@@ -145,6 +188,26 @@ __global__ void __launch_bounds__(1024) avk_label_tally_compact_kernel(avk::lb::
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_regions; r += step)
         avk::lb::lb_region_labels(v, r, (const uint64_t *)label_off, label_idx, label_lo, label_hi, (uint64_t *)acc,
                                   [](uint64_t *p, uint32_t x) { atomicAdd((unsigned long long *)p, (unsigned long long)x); });
+    __syncthreads();
+    for (unsigned k = threadIdx.x; k < words; k += blockDim.x) {
+        const unsigned long long x = acc[k];
+        if (x) atomicAdd(out + (size_t)(label_lo + k / AVK_LB_WORDS) * AVK_TALLY_LEN + k % AVK_LB_WORDS, x);
+    }
+}
+
+/* The same launch for a batch whose labels are the strata pass's bit masks (mask[w * n_regions + r]): same block of labels in LDS, same lanes, same flush; per
+ * region the status and at most AVK_LB_MASK_WORDS mask words — no offsets, no index array. */
+__global__ void __launch_bounds__(1024) avk_label_tally_mask_kernel(avk::lb::LbView v, const uint32_t *mask, uint32_t n_regions, uint32_t label_lo, uint32_t label_hi,
+                                                                    unsigned long long *out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char avk_smem[];
+    unsigned long long *acc = (unsigned long long *)avk_smem;
+    const unsigned words = (label_hi - label_lo) * AVK_LB_WORDS;
+    for (unsigned k = threadIdx.x; k < words; k += blockDim.x) acc[k] = 0;
+    __syncthreads();
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_regions; r += step)
+        avk::lb::lb_region_labels_mask(v, r, mask, n_regions, label_lo, label_hi, (uint64_t *)acc,
+                                       [](uint64_t *p, uint32_t x) { atomicAdd((unsigned long long *)p, (unsigned long long)x); });
     __syncthreads();
     for (unsigned k = threadIdx.x; k < words; k += blockDim.x) {
         const unsigned long long x = acc[k];

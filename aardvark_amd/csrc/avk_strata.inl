@@ -12,6 +12,9 @@
  * genome searching the same tree, so a wave's searches visit the same few cache lines — and write the CSR lists avk_label_tally_compact_kernel reads:
  * 64-bit label_off, label_idx ascending within a region (the order of the host's loop over the labels).
  *
+ * A batch in flight (avk_compare_packed_submit_strata) runs pass 1 alone: its tally reads the masks themselves (lb_region_labels_mask, avk_labels.inl), and neither
+ * the scan nor pass 2 is queued for it.
+ *
  * Written against avk_wave.h / DpIn like avk_labels.inl, so tests/emu/strata_emu.cpp runs the same rule on the CPU against the host's lists.
  */
 #ifndef AVK_STRATA_INL

@@ -577,6 +577,18 @@ int  avk_label_tallies_strata(avk_ctx *ctx, avk_dev_batch *db, const avk_strata 
  * call without labels, launch for launch.  An escaped batch takes the route it takes today. */
 int  avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata, const avk_compare_config *cfg,
                                avk_result_batch *out, uint64_t *label_tallies);
+/* avk_compare_packed_submit_labels with the handle in place of the lists, for a job that keeps batches in flight: the mask pass of the lists' kernels runs with
+ * the packer's region passes on the batch's own upload streams, and the label kernel reads a region's labels straight from its mask words behind the solve — no
+ * offsets, no index array, nothing made on or copied from the host.  The sums are ADDED to label_tallies[n_labels * AVK_TALLY_LEN] in avk_wait (until which
+ * label_tallies belongs to the library); words AVK_TALLY_SOLVED / AVK_TALLY_ERRORS are untouched; the library switches the BASEPAIR groups on itself; regions the
+ * capacity retry repairs are counted.  strata == NULL or zero labels: exactly avk_compare_packed_submit_esc, launch for launch.  AVK_E_ARG, before anything is
+ * queued: a handle of another context, a NULL label_tallies.  Four batches in flight: AVK_E_STATE, as for every submit.  A batch that cannot be queued (pageable
+ * arrays, sequences asked for, ...) is solved at submit by avk_compare_packed_strata and its ticket is complete.
+ * Lifetime of the handle: it counts the batches submitted with it that have not been waited for.  avk_strata_free may be called while that count is not zero: it
+ * first waits for the streams those batches' mask passes were queued on — nothing else reads the trees — and then frees them; avk_wait on such a ticket uses only
+ * what the ticket itself holds (its masks, its sums, the number of labels).  Destroying the context with tickets in flight stays the caller's error. */
+int  avk_compare_packed_submit_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata,
+                                      const avk_compare_config *cfg, avk_result_batch *out, uint64_t *label_tallies, avk_ticket **ticket);
 
 /* Merge path (src/merge_solver.rs:137-143): for pair p, optimize_sequences(set a, set b) and
  * report all_opt_haps[0].is_exact_match().  Pair p compares variant ranges
