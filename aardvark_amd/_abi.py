@@ -189,6 +189,18 @@ def declare_submit_strata(lib):
     lib.avk_compare_packed_submit_strata.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkResultBatch), _p(C.c_uint64), _p(vp)]
 
 
+def declare_debug_ref_packed(lib):
+    """avk_debug_ref_packed(avk_ctx *, uint32_t *words_out, uint64_t n_words_cap, uint32_t *flags_out, uint64_t n_flag_words_cap) -> int"""
+    lib.avk_debug_ref_packed.restype = C.c_int
+    lib.avk_debug_ref_packed.argtypes = [C.c_void_p, _p(C.c_uint32), C.c_uint64, _p(C.c_uint32), C.c_uint64]
+
+
+def ref_packed_sizes(n_bases):
+    """(packed words, flag words) avk_debug_ref_packed returns for a reference of n_bases bases in all"""
+    n_words = (int(n_bases) + 15) // 16
+    return n_words, n_words // 32 + 8
+
+
 def _ptr(arr, ctype):
     return arr.ctypes.data_as(_p(ctype))
 

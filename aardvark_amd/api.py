@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
-                   PackedBatch, RegionBatch, ResultBatch, declare_submit_strata, region_labels)
+                   PackedBatch, RegionBatch, ResultBatch, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes, region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -87,6 +87,8 @@ def load_library():
         lib.avk_compare_packed_strata.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, vp, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p]
     if hasattr(lib, "avk_compare_packed_submit_strata"):  # the submit with resident sets (AVK_LIB may name an older in-tree build: A/B runs)
         declare_submit_strata(lib)
+    if hasattr(lib, "avk_debug_ref_packed"):  # (AVK_LIB may name an older in-tree build: A/B runs)
+        declare_debug_ref_packed(lib)
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
     lib.avk_results_download.argtypes = [vp, vp, C.POINTER(AvkResultBatch)]
     lib.avk_batch_free.argtypes = [vp, vp]
@@ -530,6 +532,18 @@ class Context:
         c = [int(x) for x in counts]
         return (order[:n] if want_order else None), {"class_c": c[0], "class_c_not_wide": c[1], "class_b": c[2], "lanes": c[3],
                                                       "fast": [(c[4 + 3 * k], c[5 + 3 * k], c[6 + 3 * k]) for k in range(6)]}
+
+    def debug_ref_packed(self):
+        """avk_debug_ref_packed: (packed words uint32[], flag words uint32[]) of the current reference as the device holds them — the words that cover the reference and
+        the context's whole flag bitmap (include/aardvark_amd.h has the layout)"""
+        if self._contigs is None:
+            n_words, n_flags = 0, 8  # no upload through this object: the library refuses
+        else:
+            n_words, n_flags = ref_packed_sizes(sum(a.size for a in self._contigs))
+        words, flags = np.zeros(max(n_words, 1), np.uint32), np.zeros(n_flags, np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.lib.avk_debug_ref_packed(self.handle, words.ctypes.data_as(u32p), n_words, flags.ctypes.data_as(u32p), n_flags))
+        return words[:n_words], flags
 
     def debug_phase_cycles(self):
         out = (C.c_uint64 * 16)()

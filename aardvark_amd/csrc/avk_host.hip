@@ -2283,6 +2283,23 @@ int avk_debug_work_order(avk_ctx *ctx, avk_dev_batch *db, uint32_t *order, uint6
     return 0;
 }
 
+/* The 2-bit copy of the current reference and its flag bitmap, as avk_pack_reference left them (avk_ref_upload): a test aid, read-only.  The packed words are those that
+ * cover the reference; the flag words are the whole bitmap the context allocated, so that a test also sees what lies behind the covered part. */
+int avk_debug_ref_packed(avk_ctx *ctx, uint32_t *words_out, uint64_t n_words_cap, uint32_t *flags_out, uint64_t n_flag_words_cap) {
+    if (!ctx) return AVK_E_ARG;
+    if (!ctx->d_ref || !ctx->d_ref2b || !ctx->d_refexc) return fail(ctx, AVK_E_ARG, "avk_ref_upload has not been called");
+    uint64_t total = 0;
+    for (uint64_t len : ctx->contig_len) total += len;
+    const uint64_t n_words = (total + 15) >> 4, n_flag_words = (n_words >> 5) + 8;
+    if (!flags_out || (n_words && !words_out) || n_words_cap < n_words || n_flag_words_cap < n_flag_words)
+        return fail(ctx, AVK_E_ARG, "avk_debug_ref_packed needs room for %llu packed words and %llu flag words", (unsigned long long)n_words, (unsigned long long)n_flag_words);
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    AVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_words) AVK_HIP(ctx, hipMemcpy(words_out, ctx->d_ref2b, (size_t)n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    AVK_HIP(ctx, hipMemcpy(flags_out, ctx->d_refexc, (size_t)n_flag_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int avk_last_tier_counts(avk_ctx *ctx, uint64_t counts[5]) {
     if (!ctx || !counts) return AVK_E_ARG;
     memcpy(counts, ctx->last_tiers, sizeof(ctx->last_tiers));

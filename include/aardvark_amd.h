@@ -510,6 +510,13 @@ int  avk_debug_snapshot(avk_ctx *ctx, avk_dev_batch *db, uint32_t *counters, uin
  * regions and head regions of lane class fc (0 .. 5; 5 = the looked-up pairs).  Between class B and the first lane class lies the bulk.  order may be NULL. */
 int  avk_debug_work_order(avk_ctx *ctx, avk_dev_batch *db, uint32_t *order, uint64_t counts[22]);
 
+/* test aid, read-only: the 2-bit copy of the current reference that avk_ref_upload made and that every fast kernel reads, and its flag bitmap.  The contigs are packed as one
+ * string, contig after contig without padding, B bases in all: base p of that string sits in bits 2 (p % 16) .. 2 (p % 16) + 1 of packed word p / 16, A = 0, C = 1, G = 2, T = 3,
+ * any other byte 0; bit w % 32 of flag word w / 32 is set when one of the bytes packed word w covers is not an upper-case A, C, G or T (such windows are read from the byte copy).
+ * Positions behind base B - 1 count as 0 and raise no flag.  words_out gets the (B + 15) / 16 packed words that cover the reference, flags_out the whole bitmap of the context,
+ * (B + 15) / 16 / 32 + 8 words: the words behind the covered ones are 0.  AVK_E_ARG without a reference or when a capacity (in words) is smaller than that. */
+int  avk_debug_ref_packed(avk_ctx *ctx, uint32_t *words_out, uint64_t n_words_cap, uint32_t *flags_out, uint64_t n_flag_words_cap);
+
 /* Stratified tallies on the device (SummaryWriter::add_comparison_benchmark with the region's containment labels,
  * src/writers/summary.rs:146-163): after avk_compare_resident with the option emit_group_metrics set, label l's block of
  * AVK_TALLY_LEN words gets the sum of the metric blocks of the solved regions whose label list names l.  The labels of region r (caller

@@ -482,6 +482,23 @@ dpk::DpOpts dp_opts_of(uint64_t lds_bytes, uint32_t lds_ed_cap, uint64_t lds2_by
 
 extern "C" {
 
+/* packed copy of the reference and its flag bitmap, as avk_pack_reference builds them on the device (the sizes are those avk_ref_upload allocates) */
+static void emu_pack_reference_into(const uint8_t *bytes, uint64_t total, std::vector<uint32_t> *ref2b, std::vector<uint32_t> *refexc) {
+    const uint64_t n_words = (total + 15) >> 4;
+    ref2b->assign(n_words + 80, 0);
+    refexc->assign((n_words >> 5) + 8, 0);
+    for (uint64_t p = 0; p < total; ++p) {
+        const uint8_t ch = bytes[p];
+        uint32_t code = 0;
+        if (ch == 'A') code = 0;
+        else if (ch == 'C') code = 1;
+        else if (ch == 'G') code = 2;
+        else if (ch == 'T') code = 3;
+        else (*refexc)[(p >> 4) >> 5] |= 1u << ((p >> 4) & 31);
+        (*ref2b)[p >> 4] |= code << (2 * (p & 15));
+    }
+}
+
 /* Mirrors avk_compare_batch on emulated wavefronts.  lds_bytes / lds2_bytes / ws_bytes / big_ws_bytes
  * are the per-wave workspace sizes of the four tiers (0 disables a tier), *_ed_cap the wavefront caps
  * of the LDS tiers, n_waves the number of persistent waves, threads the OS threads running them.
@@ -532,19 +549,8 @@ static int emu_run(uint32_t mode, const avk_region_batch *batch, const uint8_t *
     a.regions = pb.regions.data();
     a.blob = devpack ? dpr.blob.data() : pb.blob.data();
     a.ref_bytes = refcat.data();
-    /* packed copy, as avk_pack_reference builds it on the device */
-    const uint64_t n_words = (total + 15) >> 4;
-    std::vector<uint32_t> ref2b(n_words + 80, 0), refexc((n_words >> 5) + 8, 0);
-    for (uint64_t p = 0; p < total; ++p) {
-        const uint8_t ch = refcat[p];
-        uint32_t code = 0;
-        if (ch == 'A') code = 0;
-        else if (ch == 'C') code = 1;
-        else if (ch == 'G') code = 2;
-        else if (ch == 'T') code = 3;
-        else refexc[(p >> 4) >> 5] |= 1u << ((p >> 4) & 31);
-        ref2b[p >> 4] |= code << (2 * (p & 15));
-    }
+    std::vector<uint32_t> ref2b, refexc;
+    emu_pack_reference_into(refcat.data(), total, &ref2b, &refexc);
     a.ref_2bit = ref2b.data();
     a.ref_exc = refexc.data();
     a.n_regions = (uint32_t)n;
@@ -1383,6 +1389,21 @@ int emu_optimize_pairs_batch(const avk_region_batch *batch, const uint8_t *const
                                                                                                      pair_classes: pair batches plan their classes C and B with solo_min_variants 5) */
     if (rc) return rc;
     for (uint64_t r = 0; r < batch->n_regions; ++r) is_exact_match[r] = status[r] == 0 && ed1[r] ? 1 : 0;
+    return 0;
+}
+
+/* The packed copy and the flag bitmap the emulated kernels read (emu_pack_reference_into, what emu_run builds for every call) for the contigs given: words_out gets the words
+ * that cover the reference, flags_out the whole bitmap.  Returns 0, or -1 when a capacity (in words) is too small. */
+int emu_ref_packed(const uint8_t *const *refs, const uint64_t *ref_lens, uint32_t n_contigs, uint32_t *words_out, uint64_t n_words_cap, uint32_t *flags_out,
+                   uint64_t n_flag_words_cap) {
+    std::vector<uint8_t> refcat;
+    for (uint32_t c = 0; c < n_contigs; ++c) refcat.insert(refcat.end(), refs[c], refs[c] + ref_lens[c]);
+    std::vector<uint32_t> ref2b, refexc;
+    emu_pack_reference_into(refcat.data(), refcat.size(), &ref2b, &refexc);
+    const uint64_t n_words = (refcat.size() + 15) >> 4;
+    if (n_words_cap < n_words || n_flag_words_cap < refexc.size()) return -1;
+    if (n_words) memcpy(words_out, ref2b.data(), n_words * sizeof(uint32_t));
+    memcpy(flags_out, refexc.data(), refexc.size() * sizeof(uint32_t));
     return 0;
 }
 

@@ -27,6 +27,7 @@ def test_library_exports_every_declared_symbol():
     lib = aardvark_amd.load_library()
     names = declared_functions()
     assert len(names) >= 18
+    assert "avk_debug_ref_packed" in names  # the read-only export of the 2-bit reference (tests/test_gpu_ref_edges.py)
     for n in names:
         assert hasattr(lib, n), "libaardvark_amd.so does not export %s" % n
     assert b"gfx950" in lib.avk_version()
