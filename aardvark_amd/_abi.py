@@ -42,6 +42,8 @@ ST_NAMES = {
     11: "AUTOFAIL_OOB", 20: "INVALID_INPUT", 21: "CAPACITY",
 }
 
+MERGE_SWEEP_MAX = 8  # AVK_MERGE_SWEEP_MAX: the configs one avk_merge_packed_sweep / avk_merge_classify_sweep decides on top of one pair solve
+
 _p = C.POINTER
 
 

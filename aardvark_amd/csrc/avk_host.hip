@@ -41,6 +41,8 @@
 #include "avk_labels.inl"
 #include "avk_strata.inl"
 #include "avk_mergecount.inl"
+#include "avk_mergesweep.inl"
+static_assert((int)avk::ms::MS_KMAX == (int)avk::dp::DP_MERGE_KMAX, "the sweep kernel decides what the classification kernel decides");
 
 /* ---------------------------------------------------------------------------------- kernels */
 /* LDS passes: regions in the LDS slice of their wavefront (small slices at high occupancy first, then
@@ -3958,10 +3960,12 @@ int avk_merge_classify(uint64_t n_regions, uint32_t k, const uint32_t *in_cnt, c
 static bool merge_on_device(const avk_ctx *ctx, uint64_t n_regions, uint32_t k) {
     return ctx->device_pack && k >= 2 && k <= (uint32_t)avk::dp::DP_MERGE_KMAX && n_regions && n_regions * (uint64_t)(k * (k - 1) / 2) <= 0x7FFFFFFFull;
 }
+/* n_sweep = 0: the one config *cfg, the launches of avk_merge_packed_counts.  n_sweep >= 1 (avk_merge_packed_sweep): cfg[n_sweep] with one max_branch_factor, decided on
+ * top of ONE pair solve; classification / members are config-major and counts holds a block per config. */
 static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                uint64_t *members, const avk_packed_escapes *esc = nullptr, uint64_t *counts = nullptr);
+                                uint64_t *members, const avk_packed_escapes *esc = nullptr, uint64_t *counts = nullptr, uint32_t n_sweep = 0);
 static int merge_packed_internal(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                 uint64_t *members, uint64_t *counts);
+                                 uint64_t *members, uint64_t *counts, uint32_t n_sweep = 0);
 /* the LDS a launch of the count kernel really gets (as for the label kernel: the whole CU's where the runtime grants it) */
 static int64_t mergecount_lds(avk_ctx *ctx) {
     if (!ctx->mergecount_lds_bytes) {
@@ -4004,8 +4008,30 @@ int avk_merge_packed_esc(avk_ctx *ctx, const avk_packed_multi_batch *pm, const a
                          uint64_t *members) {
     return merge_packed_internal(ctx, pm, esc, cfg, status, classification, members, nullptr);
 }
+/* the decisions of several configs on top of one pair matrix (avk_mergesweep.inl) */
+int avk_merge_classify_sweep(uint64_t n_regions, uint32_t k, const uint32_t *in_cnt, const uint8_t *has_unknown_zyg, const int32_t *pair_status, const uint8_t *pair_exact,
+                             uint32_t n_cfgs, const avk_merge_config *cfgs, int32_t *status, uint8_t *classification, uint64_t *members) {
+    return avk::ms::merge_classify_sweep_host(n_regions, k, in_cnt, has_unknown_zyg, pair_status, pair_exact, n_cfgs, cfgs, status, classification, members);
+}
+/* One pair solve, n_cfgs decisions (include/aardvark_amd.h).  Everything that can be refused from the arguments alone is refused here, before anything is queued. */
+int avk_merge_packed_sweep(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, uint32_t n_cfgs, const avk_merge_config *cfgs, int32_t *status,
+                           uint8_t *classification, uint64_t *members, uint64_t *counts) {
+    if (!ctx || !pm || !cfgs || !status || !classification || !members) return AVK_E_ARG;
+    ctx->last_merge_counts_on_device = 0;
+    if (n_cfgs < 1 || n_cfgs > (uint32_t)AVK_MERGE_SWEEP_MAX) return fail(ctx, AVK_E_ARG, "a sweep takes 1 to %d configs (n_cfgs %u)", AVK_MERGE_SWEEP_MAX, n_cfgs);
+    if (pm->n_inputs < 1 || pm->n_inputs > 64) return fail(ctx, AVK_E_ARG, "n_inputs must be in [1, 64]");
+    for (uint32_t c = 0; c < n_cfgs; ++c) {
+        if (cfgs[c].max_branch_factor != cfgs[0].max_branch_factor)
+            return fail(ctx, AVK_E_ARG, "the configs of a sweep share one pair solve: config %u has max_branch_factor %u, config 0 has %u", c, cfgs[c].max_branch_factor, cfgs[0].max_branch_factor);
+        if (!avk::ms::merge_sweep_cfg_ok(pm->n_inputs, cfgs[c]))
+            return fail(ctx, AVK_E_ARG, "config %u: conflict_selection %d is not -1 or one of the %u inputs", c, cfgs[c].conflict_selection, pm->n_inputs);
+    }
+    if (counts && avk_merge_counts_len(pm->n_inputs) == 0)
+        return fail(ctx, AVK_E_ARG, "summary counters exist for 2 to %d inputs (n_inputs %u)", AVK_MERGE_COUNTS_MAX_INPUTS, pm->n_inputs);
+    return merge_packed_internal(ctx, pm, esc, cfgs, status, classification, members, counts, n_cfgs);
+}
 static int merge_packed_internal(avk_ctx *ctx, const avk_packed_multi_batch *pm, const avk_packed_escapes *esc, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                 uint64_t *members, uint64_t *counts) {
+                                 uint64_t *members, uint64_t *counts, uint32_t n_sweep) {
     if (!ctx || !pm || !cfg || !status || !classification || !members) return AVK_E_ARG;
     if (!esc_present(esc)) esc = nullptr;
     const uint32_t k = pm->n_inputs;
@@ -4016,14 +4042,16 @@ static int merge_packed_internal(avk_ctx *ctx, const avk_packed_multi_batch *pm,
     avk_multi_batch mb;
     memset(&mb, 0, sizeof(mb));
     mb.n_regions = n, mb.n_inputs = k, mb.n_variants = nv, mb.allele_bytes = pm->allele_bytes, mb.allele_bytes_len = pm->allele_bytes_len;
-    if (merge_on_device(ctx, n, k)) return merge_batch_internal(ctx, &mb, pm, cfg, status, classification, members, esc, counts);
+    if (merge_on_device(ctx, n, k)) return merge_batch_internal(ctx, &mb, pm, cfg, status, classification, members, esc, counts, n_sweep);
     if (counts) { /* no device route: the solve as it is, then the host's count into a block of its own (nothing reaches counts[] of a batch that is refused) */
-        int rc = merge_packed_internal(ctx, pm, esc, cfg, status, classification, members, nullptr);
+        int rc = merge_packed_internal(ctx, pm, esc, cfg, status, classification, members, nullptr, n_sweep);
         if (rc) return rc;
         for (uint64_t v = 0; v < nv; ++v)
             if ((pm->var_type_zyg[v] & 15u) >= AVK_N_VARIANT_TYPES) return fail(ctx, AVK_E_ARG, "summary counters: call %llu has the unknown type %u", (unsigned long long)v, pm->var_type_zyg[v] & 15u);
-        std::vector<uint64_t> block((size_t)avk_merge_counts_len(k), 0);
-        rc = avk_merge_counts_esc(pm, esc, status, classification, members, block.data());
+        const uint32_t nc = n_sweep ? n_sweep : 1u; /* (a sweep: a block per config, and none of them reaches counts[] unless all are made) */
+        const size_t len = (size_t)avk_merge_counts_len(k);
+        std::vector<uint64_t> block(len * nc, 0);
+        for (uint32_t c = 0; c < nc && !rc; ++c) rc = avk_merge_counts_esc(pm, esc, status, classification + (size_t)c * n, members + (size_t)c * n, block.data() + c * len);
         if (rc) return fail(ctx, AVK_E_ARG, "summary counters: the batch and its results do not fit together (call counts, escape lists, classifications)");
         for (size_t w = 0; w < block.size(); ++w) counts[w] += block[w];
         return AVK_E_OK;
@@ -4055,7 +4083,7 @@ static int merge_packed_internal(avk_ctx *ctx, const avk_packed_multi_batch *pm,
     if (ab != pm->allele_bytes_len && nv) return fail(ctx, AVK_E_ARG, "packed batch: the allele lengths sum to %llu (allele_bytes_len %llu)", (unsigned long long)ab, (unsigned long long)pm->allele_bytes_len);
     mb.contig_idx = contig.data(), mb.start = start.data(), mb.end = end.data(), mb.in_off = in_off.data(), mb.in_cnt = in_cnt.data(), mb.var_pos = pos.data(), mb.var_type = type.data(),
     mb.var_zyg = zyg.data(), mb.var_raw_space = raw.data(), mb.a0_off = a0_off.data(), mb.a0_len = a0_len.data(), mb.a1_off = a1_off.data(), mb.a1_len = a1_len.data();
-    return avk_merge_batch(ctx, &mb, cfg, status, classification, members);
+    return merge_batch_internal(ctx, &mb, nullptr, cfg, status, classification, members, nullptr, nullptr, n_sweep);
 }
 
 int avk_merge_batch(avk_ctx *ctx, const avk_multi_batch *mb, const avk_merge_config *cfg, int32_t *status, uint8_t *classification, uint64_t *members) {
@@ -4063,9 +4091,10 @@ int avk_merge_batch(avk_ctx *ctx, const avk_multi_batch *mb, const avk_merge_con
 }
 
 static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const avk_packed_multi_batch *pm, const avk_merge_config *cfg, int32_t *status, uint8_t *classification,
-                                uint64_t *members, const avk_packed_escapes *esc, uint64_t *counts) {
+                                uint64_t *members, const avk_packed_escapes *esc, uint64_t *counts, uint32_t n_sweep) {
     if (!ctx || !mb || !cfg || !status || !classification || !members) return AVK_E_ARG;
     const uint32_t k = mb->n_inputs;
+    const uint32_t nc = n_sweep ? n_sweep : 1u; /* decisions per region */
     if (k < 1 || k > 64) return fail(ctx, AVK_E_ARG, "n_inputs must be in [1, 64]");
     if (merge_on_device(ctx, mb->n_regions, k)) {
         /* all of solve_merge_region on the device: the MultiRegions as they are over PCIe, one region per input pair made by a kernel, the pair solve (mode 1),
@@ -4083,9 +4112,20 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
         const uint64_t nm = mb->n_regions;
         void *d_st = nullptr, *d_cl = nullptr, *d_mem = nullptr;
         if (!rc) rc = pool_alloc(ctx, &d_st, (nm + 1) * 4);
-        if (!rc) rc = pool_alloc(ctx, &d_cl, nm + 16);
-        if (!rc) rc = pool_alloc(ctx, &d_mem, (nm + 1) * 8);
-        if (!rc) {
+        if (!rc) rc = pool_alloc(ctx, &d_cl, nc * nm + 16);
+        if (!rc) rc = pool_alloc(ctx, &d_mem, (nc * nm + 1) * 8);
+        if (!rc && n_sweep) { /* every config's decision by one kernel: the pair records are read once */
+            avk::ms::MsSweep c;
+            memset(&c, 0, sizeof(c));
+            c.region_out = db->d_region_out, c.in_off = db->d_m_in_off, c.in_cnt = db->d_m_in_cnt, c.var_zyg = db->d_in_zyg, c.n_multi = nm, c.n_variants = mb->n_variants, c.k = k,
+            c.ppr = k * (k - 1) / 2, c.n_cfgs = nc;
+            for (uint32_t q = 0; q < nc; ++q)
+                c.cfg[q].no_conflict_enabled = cfg[q].no_conflict_enabled, c.cfg[q].majority_voting_enabled = cfg[q].majority_voting_enabled, c.cfg[q].conflict_selection = cfg[q].conflict_selection;
+            c.status = (int32_t *)d_st, c.classification = (uint8_t *)d_cl, c.members = (uint64_t *)d_mem;
+            hipLaunchKernelGGL(avk_merge_sweep_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, ctx->stream, c);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "merge sweep failed: %s", hipGetErrorString(e));
+        } else if (!rc) {
             avk::dp::DpMerge c;
             memset(&c, 0, sizeof(c));
             c.region_out = db->d_region_out, c.in_off = db->d_m_in_off, c.in_cnt = db->d_m_in_cnt, c.var_zyg = db->d_in_zyg, c.n_multi = nm, c.n_variants = mb->n_variants, c.k = k,
@@ -4095,11 +4135,12 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "merge classification failed: %s", hipGetErrorString(e));
         }
-        /* the summary counters (avk_merge_packed_counts): a cleared block and its error word behind it, the count kernel behind the classification */
+        /* the summary counters (avk_merge_packed_counts): a cleared block and its error word behind it, the count kernel behind the classification — of a sweep: a block
+         * and an error word per config, the count kernel once per config on that config's slices */
         const size_t words = counts ? (size_t)avk::mc::merge_counts_words(k) : 0;
         void *d_cnt = nullptr;
-        std::vector<uint64_t> h_cnt(counts ? words + 1 : 0);
-        if (!rc && counts) rc = pool_alloc(ctx, &d_cnt, (words + 1) * 8);
+        std::vector<uint64_t> h_cnt(counts ? nc * (words + 1) : 0);
+        if (!rc && counts) rc = pool_alloc(ctx, &d_cnt, nc * (words + 1) * 8);
         if (!rc && counts) {
             const int64_t lds_max = mergecount_lds(ctx);
             const bool in_lds = avk::mc::mc_fits_lds(k, (uint64_t)lds_max);
@@ -4112,31 +4153,35 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
             const uint32_t per_cu = lds * 2 <= (size_t)lds_max ? 2u : 1u;
             uint64_t blocks = (nm * k + 1023) / 1024;
             if (blocks > (uint64_t)ctx->n_cus * per_cu) blocks = (uint64_t)ctx->n_cus * per_cu;
-            hipError_t e = hipMemsetAsync(d_cnt, 0, (words + 1) * 8, ctx->stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(avk_merge_count_kernel, dim3((unsigned)blocks), dim3(1024), lds, ctx->stream, v, (uint32_t)(in_lds ? words : 0), (unsigned long long *)d_cnt,
-                                   (uint32_t *)((uint64_t *)d_cnt + words));
+            hipError_t e = hipMemsetAsync(d_cnt, 0, nc * (words + 1) * 8, ctx->stream);
+            for (uint32_t q = 0; q < nc && e == hipSuccess; ++q) {
+                uint64_t *block = (uint64_t *)d_cnt + q * (words + 1);
+                v.classification = (const uint8_t *)d_cl + (size_t)q * nm, v.members = (const uint64_t *)d_mem + (size_t)q * nm;
+                hipLaunchKernelGGL(avk_merge_count_kernel, dim3((unsigned)blocks), dim3(1024), lds, ctx->stream, v, (uint32_t)(in_lds ? words : 0), (unsigned long long *)block,
+                                   (uint32_t *)(block + words));
                 e = hipGetLastError();
             }
             if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "merge counting failed: %s", hipGetErrorString(e));
         }
         if (!rc) {
-            std::vector<CopySeg> segs = {{status, d_st, nm * 4}, {classification, d_cl, nm}, {members, d_mem, nm * 8}};
-            if (counts) segs.push_back({h_cnt.data(), d_cnt, (words + 1) * 8});
+            std::vector<CopySeg> segs = {{status, d_st, nm * 4}, {classification, d_cl, nc * nm}, {members, d_mem, nc * nm * 8}};
+            if (counts) segs.push_back({h_cnt.data(), d_cnt, nc * (words + 1) * 8});
             CopyOut co;
             rc = copy_out(ctx, segs, &co);
             if (!rc) rc = finish_copy_out(ctx, co);
         }
         (void)hipStreamSynchronize(ctx->stream);
         pool_release(ctx, d_st), pool_release(ctx, d_cl), pool_release(ctx, d_mem), pool_release(ctx, d_cnt);
-        if (!rc && counts) { /* the error word first: nothing of a refused batch reaches counts[] */
-            const uint32_t err = (uint32_t)h_cnt[words];
+        if (!rc && counts) { /* the error words first: nothing of a refused batch reaches counts[], of whichever config */
+            uint32_t err = 0;
+            for (uint32_t q = 0; q < nc; ++q) err |= (uint32_t)h_cnt[q * (words + 1) + words];
             if (err)
                 rc = fail(ctx, AVK_E_ARG, "summary counters: %s", err & avk::mc::MC_ERR_TYPE    ? "a call's type is none of the variant types"
                                                                   : err & avk::mc::MC_ERR_RANGE ? "an input's calls are not inside the batch"
                                                                                                 : "a solved region's classification is not a merge classification");
             else {
-                for (size_t w = 0; w < words; ++w) counts[w] += h_cnt[w];
+                for (uint32_t q = 0; q < nc; ++q)
+                    for (size_t w = 0; w < words; ++w) counts[q * words + w] += h_cnt[q * (words + 1) + w];
                 ctx->last_merge_counts_on_device = 1;
             }
         }
@@ -4198,6 +4243,7 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
         const int rc = avk_optimize_pairs_batch(ctx, &b, cfg->max_branch_factor, pst.data(), pex.data());
         if (rc) return rc;
     }
+    if (n_sweep) return avk_merge_classify_sweep(n, k, mb->in_cnt, unknown.data(), pst.data(), pex.data(), n_sweep, cfg, status, classification, members);
     return avk_merge_classify(n, k, mb->in_cnt, unknown.data(), pst.data(), pex.data(), cfg, status, classification, members);
 }
 

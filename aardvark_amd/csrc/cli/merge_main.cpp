@@ -37,7 +37,9 @@ void usage() {
             "  [--min-variant-gap 50] [--disable-variant-trimming] [--merge-strategy exact|no_conflict|majority|all]\n"
             "  [--enable-no-conflict] [--enable-voting] [--conflict-select INDEX] [--max-branch-factor 50]\n"
             "  [--skip N] [--take N] [--device 0 | --devices 0,1,..] [--batch-regions 1000000] [--contexts 2] [--batch-form packed|wide]\n"
-            "  [--summary-counts device|host (default host)]\n");
+            "  [--summary-counts device|host (default host)]\n"
+            "  [--sweep exact,no_conflict,majority,all (any subset, in this order of writing): ONE solve decided under each strategy; the outputs go to\n"
+            "   OUT_VCF_DIR/<strategy>/ and SUMMARY.<strategy>.tsv; not with --merge-strategy, --enable-no-conflict, --enable-voting, several --devices or --contexts]\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -80,6 +82,8 @@ int main(int argc, char **argv) {
     bool ref_upper = true; /* --reference-case upper|raw (include/aardvark_feeder.h, avf_genome_load_case) */
     long long conflict_select = -1;
     int device = 0;
+    std::vector<std::string> sweep; /* --sweep: the strategies one solve is decided under (avk_merge_packed_sweep), in the order given */
+    bool contexts_given = false;
     std::vector<int> devices; /* --devices: one solver context per entry; the regions are sharded over them by avk_region_shard (the first entry is `device`) */
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -123,7 +127,20 @@ int main(int argc, char **argv) {
             }
         }
         else if (a == "--batch-regions") batch_regions = strtoull(val(), nullptr, 10);
-        else if (a == "--contexts") contexts = strtoull(val(), nullptr, 10);
+        else if (a == "--contexts") contexts = strtoull(val(), nullptr, 10), contexts_given = true;
+        else if (a == "--sweep") {
+            const std::string list = val();
+            sweep.clear();
+            for (size_t b = 0; b <= list.size();) {
+                const size_t e = list.find(',', b);
+                const std::string item = list.substr(b, e == std::string::npos ? std::string::npos : e - b);
+                if ((item != "exact" && item != "no_conflict" && item != "majority" && item != "all") || std::find(sweep.begin(), sweep.end(), item) != sweep.end())
+                    die(64, "invalid value for --sweep (a list of exact, no_conflict, majority, all without repeats)", list.c_str());
+                sweep.push_back(item);
+                if (e == std::string::npos) break;
+                b = e + 1;
+            }
+        }
         else if (a == "--batch-form") { /* packed (default; wide when the call sets do not fit the form) | wide */
             const std::string v = val();
             if (v != "packed" && v != "wide") die(78, "--batch-form must be 'packed' or 'wide'", "");
@@ -149,6 +166,11 @@ int main(int argc, char **argv) {
     if (vcfs.size() > 64) die(78, "Error while verifying settings", "at most 64 input VCFs are supported");
     if (gap == 0) die(78, "Error while verifying settings", "--min-variant-gap must be >0");
     if (branch == 0 || branch > 0xFFFFFFFFull) die(78, "Error while verifying settings", "--max-branch-factor must be >0");
+    if (!sweep.empty()) {
+        if (!strategy.empty() || no_conflict || voting) die(64, "--sweep names the strategies itself: it does not go with --merge-strategy, --enable-no-conflict or --enable-voting", "");
+        if (devices.size() > 1 || (contexts_given && contexts > 1)) die(64, "--sweep runs on one context: it does not go with several --devices or --contexts above 1", "");
+        if (!want_packed) die(64, "--sweep takes the packed batch form", "");
+    }
     std::string strategy_name; /* serde name of MergeStrategy for cli_settings.json */
     if (!strategy.empty()) {
         std::string s = strategy;
@@ -300,6 +322,79 @@ int main(int argc, char **argv) {
         packed = rc_pack == 0;
     }
     const bool escaped = packed && (esc_all.n_esc_regions || esc_all.n_esc_slots || esc_all.n_esc_calls);
+    if (!sweep.empty()) {
+        /* One solve, several strategies: every batch goes through avk_merge_packed_sweep once, its config-major answers are scattered into one set of arrays per
+         * strategy, and the existing writers run once per strategy on them.  --summary-counts device: the counters of every strategy come back with the same call. */
+        if (!packed) die(70, "--sweep takes the packed batch form, and the call sets do not fit it", "");
+        const uint32_t nc = (uint32_t)sweep.size();
+        std::vector<avk_merge_config> cfgs(nc, cfg);
+        for (uint32_t c = 0; c < nc; ++c) {
+            cfgs[c].no_conflict_enabled = sweep[c] == "no_conflict" || sweep[c] == "all" ? 1 : 0;
+            cfgs[c].majority_voting_enabled = sweep[c] == "majority" || sweep[c] == "all" ? 1 : 0;
+        }
+        const uint64_t len = avk_merge_counts_len(k);
+        const bool with_counts = len != 0 && counts_with_call && !summary_path.empty();
+        std::vector<int32_t> st(all->n_regions + 1, -1); /* regions outside --skip/--take stay unsolved and unwritten */
+        std::vector<std::vector<uint8_t>> cls(nc, std::vector<uint8_t>(all->n_regions + 1, 0));
+        std::vector<std::vector<uint64_t>> mem(nc, std::vector<uint64_t>(all->n_regions + 1, 0));
+        std::vector<uint64_t> sums(with_counts ? nc * len : 0, 0);
+        uint64_t by_kernel = 0, n_calls = 0;
+        for (uint64_t at = 0; at < count; at += batch_regions, ++n_calls) {
+            const uint64_t n = count - at < batch_regions ? count - at : batch_regions;
+            avk_packed_multi_batch part;
+            avk_packed_escapes part_esc;
+            if (avf_packed_multi_slice_esc(feed, &packed_all, &esc_all, first + at, n, &part, &part_esc)) die(70, "cannot select the regions", avf_last_error());
+            std::vector<uint8_t> b_cls(nc * n + 1);
+            std::vector<uint64_t> b_mem(nc * n + 1);
+            if (avk_merge_packed_sweep(ctx, &part, &part_esc, nc, cfgs.data(), st.data() + first + at, b_cls.data(), b_mem.data(), with_counts ? sums.data() : nullptr))
+                die(70, "merge failed", avk_last_error(ctx));
+            by_kernel += with_counts && avk_last_merge_counts_on_device(ctx) ? 1 : 0;
+            for (uint32_t c = 0; c < nc; ++c) {
+                std::copy(b_cls.begin() + c * n, b_cls.begin() + (c + 1) * n, cls[c].begin() + first + at);
+                std::copy(b_mem.begin() + c * n, b_mem.begin() + (c + 1) * n, mem[c].begin() + first + at);
+            }
+        }
+        if (verbosity)
+            fprintf(stderr, "Sweep: one solve served %u strateg%s (%llu call%s of avk_merge_packed_sweep; summary counters %s).\n", nc, nc == 1 ? "y" : "ies", (unsigned long long)n_calls,
+                    n_calls == 1 ? "" : "s", !with_counts ? "made region by region on the host" : by_kernel == n_calls ? "by kernel with the call" : "with the call, by the host function");
+        uint64_t solved = 0, errors = 0;
+        for (uint64_t r = first; r < first + count; ++r) {
+            if (st[r] == 0) {
+                solved += 1;
+                continue;
+            }
+            errors += 1;
+            fprintf(stderr, "Error while solving merge region #%llu (contig %u:%llu-%llu): status %d\n", (unsigned long long)all->region_id[r], all->contig_idx[r],
+                    (unsigned long long)all->start[r], (unsigned long long)all->end[r], st[r]);
+        }
+        const double s_solve = seconds_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        std::string command;
+        for (int i = 0; i < argc; ++i) command += (i ? " " : "") + std::string(argv[i]);
+        for (uint32_t c = 0; c < nc; ++c) {
+            const std::string dir = out_dir + "/" + sweep[c];
+            if (avf_write_merge_outputs(dir.c_str(), vcfs[0].c_str(), sample_ptrs[0], avk_version(), command.c_str(), genome, all, tag_ptrs.data(), st.data(), cls[c].data(), mem[c].data()))
+                die(74, "Error while writing merged VCF results", avf_last_error());
+            if (summary_path.empty()) continue;
+            /* SUMMARY.tsv -> SUMMARY.<strategy>.tsv (a name without an extension gains .<strategy>) */
+            const size_t slash = summary_path.rfind('/'), dot = summary_path.rfind('.');
+            const size_t cut = dot != std::string::npos && (slash == std::string::npos || dot > slash + 1) ? dot : summary_path.size();
+            const std::string path = summary_path.substr(0, cut) + "." + sweep[c] + summary_path.substr(cut);
+            if (with_counts ? avf_write_merge_summary_counts(path.c_str(), k, tag_ptrs.data(), sums.data() + c * len, len)
+                            : avf_write_merge_summary(path.c_str(), all, tag_ptrs.data(), st.data(), cls[c].data(), mem[c].data()))
+                die(74, "Error while saving summary file", avf_last_error());
+        }
+        fprintf(stderr, "Solved:error blocks: %llu : %llu\n", (unsigned long long)solved, (unsigned long long)errors);
+        fprintf(stderr, "stages [s]: load %.3f (reference %.3f beside the call sets and the gpu context), regions %.3f (beside it: reference upload %.3f), "
+                        "solve (pack + H2D + kernels + D2H, %u strategies) %.3f, outputs %.3f\n",
+                s_load, s_genome, s_feed, s_ref, nc, s_solve, seconds_since(t0));
+        fprintf(stderr, "Merge completed in %.3f seconds.\n", seconds_since(t_start));
+        th_free.join();
+        avk_ctx_destroy(ctx);
+        avf_feed_free(feed);
+        avf_genome_free(genome);
+        return 0;
+    }
     std::vector<int32_t> status(all->n_regions + 1, -1); /* regions outside --skip/--take stay unsolved and unwritten */
     std::vector<uint8_t> classification(all->n_regions + 1, 0);
     std::vector<uint64_t> members(all->n_regions + 1, 0);

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import ZYG, AvkPackedEscapes, PackedEscapes, RegionBatch
+from ._abi import MERGE_SWEEP_MAX, ZYG, AvkPackedEscapes, PackedEscapes, RegionBatch  # noqa: F401 (MERGE_SWEEP_MAX is re-exported)
 
 
 class MergeConfig:
@@ -354,6 +354,52 @@ def merge_multi_batch(ctx, mb, config=None, counts=None):
     entry.argtypes = [C.c_void_p, C.POINTER(AvkPackedMultiBatch if packed else AvkMultiBatch), C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
     ctx._check(entry(ctx.handle, C.byref(cb), C.byref(cfg), P(st, C.c_int32), P(cls, C.c_uint8), P(members, C.c_uint64)))
     return MergeResult(st[:n], cls[:n], members[:n], mb.n_inputs)
+
+
+def _c_merge_config(config):
+    return AvkMergeConfig(config.max_branch_factor, int(config.no_conflict_enabled), int(config.majority_voting_enabled),
+                          -1 if config.conflict_selection is None else int(config.conflict_selection))
+
+
+def merge_multi_batch_sweep(ctx, pm, configs, counts=None):
+    """avk_merge_packed_sweep on a PackedMultiBatch: ONE pair solve decided under every MergeConfig of `configs` (1 to MERGE_SWEEP_MAX of them, all with the same
+    max_branch_factor) -> one MergeResult per config; all of them share one status array.
+    counts: a (len(configs), merge_counts_len(k)) uint64 array; config c's summary counters are ADDED to row c by the same call."""
+    if not isinstance(pm, PackedMultiBatch):
+        raise ValueError("a sweep takes the packed form (a PackedMultiBatch)")
+    n, nc = pm.n_regions, len(configs)
+    cfgs = (AvkMergeConfig * max(nc, 1))(*[_c_merge_config(c) for c in configs])
+    st = np.zeros(max(n, 1), np.int32)
+    cls = np.zeros(max(nc * n, 1), np.uint8)
+    members = np.zeros(max(nc * n, 1), np.uint64)
+    if counts is not None:
+        assert counts.dtype == np.uint64 and counts.flags.c_contiguous and counts.size >= max(nc * merge_counts_len(ctx.lib, pm.n_inputs), 1)
+    P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    cb, esc = pm.c_struct(), pm.c_escapes()
+    entry = ctx.lib.avk_merge_packed_sweep
+    entry.argtypes = [C.c_void_p, C.POINTER(AvkPackedMultiBatch), C.POINTER(AvkPackedEscapes), C.c_uint32, C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
+                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    ctx._check(entry(ctx.handle, C.byref(cb), C.byref(esc) if esc is not None else None, nc, cfgs, P(st, C.c_int32), P(cls, C.c_uint8), P(members, C.c_uint64),
+                     None if counts is None else P(counts, C.c_uint64)))
+    return [MergeResult(st[:n], cls[c * n:(c + 1) * n], members[c * n:(c + 1) * n], pm.n_inputs) for c in range(nc)]
+
+
+def merge_classify_sweep(lib, n_inputs, in_cnt, has_unknown_zyg, pair_status, pair_exact, configs):
+    """avk_merge_classify_sweep (host only): the decisions of every MergeConfig of `configs` from a given pair matrix -> one MergeResult per config"""
+    in_cnt = np.ascontiguousarray(in_cnt, np.uint32)
+    n, nc = in_cnt.size // n_inputs, len(configs)
+    unknown = np.ascontiguousarray(has_unknown_zyg, np.uint8)
+    pst, pex = np.ascontiguousarray(pair_status, np.int32), np.ascontiguousarray(pair_exact, np.uint8)
+    cfgs = (AvkMergeConfig * max(nc, 1))(*[_c_merge_config(c) for c in configs])
+    st, cls, members = np.zeros(max(n, 1), np.int32), np.zeros(max(nc * n, 1), np.uint8), np.zeros(max(nc * n, 1), np.uint64)
+    P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    lib.avk_merge_classify_sweep.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_uint32,
+                                             C.POINTER(AvkMergeConfig), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
+    rc = lib.avk_merge_classify_sweep(n, n_inputs, P(in_cnt, C.c_uint32), P(unknown, C.c_uint8), P(pst, C.c_int32), P(pex, C.c_uint8), nc, cfgs, P(st, C.c_int32),
+                                      P(cls, C.c_uint8), P(members, C.c_uint64))
+    if rc:
+        raise ValueError("avk_merge_classify_sweep failed (%d)" % rc)
+    return [MergeResult(st[:n], cls[c * n:(c + 1) * n], members[c * n:(c + 1) * n], n_inputs) for c in range(nc)]
 
 
 def counts_on_device(ctx):

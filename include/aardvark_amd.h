@@ -713,6 +713,28 @@ int  avk_merge_packed_counts(avk_ctx *ctx, const avk_packed_multi_batch *batch, 
 int  avk_last_merge_counts_on_device(avk_ctx *ctx);
 int  avk_merge_counts_in_lds(avk_ctx *ctx, uint32_t n_inputs); /* 1: the count kernel of this context keeps the block of n_inputs inputs in LDS */
 
+/* ---- one pair solve, several strategies.  The pair matrix of a region depends on the batch and on max_branch_factor alone (src/merge_solver.rs:125-164); the
+ * switches no_conflict_enabled / majority_voting_enabled / conflict_selection are read when the last pair is solved (:166-197).  avk_merge_packed_sweep is
+ * avk_merge_packed_counts for n_cfgs configs at once: ONE upload and ONE pair solve, then every config's decision — status[n] is the same for all of them,
+ * classification and members are config-major: config c owns [c * n, (c + 1) * n) —, and with counts != NULL config c's dense block is ADDED to
+ * counts + c * avk_merge_counts_len(k).  On the device route (device_pack on, 2 <= k <= 8, a batch that is not empty) one kernel behind the pair solve reads every
+ * region's pair records once and writes all configs' decisions, the count kernel runs once per config behind it on the call's stream, and everything comes back in
+ * one copy; every other batch (k = 1 or k > 8, device_pack = 0, no regions) is solved once through the host route, decided by avk_merge_classify_sweep and counted
+ * by avk_merge_counts_esc per config.  The answers are the same either way, for every k <= 64, and with n_cfgs = 1 they are avk_merge_packed_counts' word for word.
+ *   AVK_E_ARG before anything is queued, with nothing written: n_cfgs is 0 or above AVK_MERGE_SWEEP_MAX; the configs do not all carry the same max_branch_factor
+ *   (the pair solve depends on it); a conflict_selection is >= k or < -1; counts != NULL with k outside [2, AVK_MERGE_COUNTS_MAX_INPUTS].
+ *   Duplicate configs are allowed.
+ *   AVK_E_ARG with counts untouched FOR EVERY CONFIG: what avk_merge_packed_counts refuses (one refused config refuses the call).
+ * avk_last_merge_counts_on_device is 1 afterwards only when all configs were counted by kernel. */
+#define AVK_MERGE_SWEEP_MAX 8
+int  avk_merge_packed_sweep(avk_ctx *ctx, const avk_packed_multi_batch *batch, const avk_packed_escapes *esc, uint32_t n_cfgs, const avk_merge_config *cfgs,
+                            int32_t *status /* [n] */, uint8_t *classification /* [n_cfgs * n], config-major */, uint64_t *members /* [n_cfgs * n] */,
+                            uint64_t *counts /* NULL, or [n_cfgs * avk_merge_counts_len(k)], ADDED to */);
+/* Host only (no GPU): the same decisions from a given pair matrix — avk_merge_classify's arguments with several configs (their max_branch_factor is not read).
+ * AVK_E_ARG with nothing written: a NULL array, n_inputs outside [1, 64], n_cfgs 0 or above AVK_MERGE_SWEEP_MAX, a conflict_selection >= n_inputs or < -1. */
+int  avk_merge_classify_sweep(uint64_t n_regions, uint32_t n_inputs, const uint32_t *in_cnt, const uint8_t *has_unknown_zyg, const int32_t *pair_status,
+                              const uint8_t *pair_exact, uint32_t n_cfgs, const avk_merge_config *cfgs, int32_t *status, uint8_t *classification, uint64_t *members);
+
 /* Host utility (no GPU involved): unit-cost edit distance of two byte strings, the value of the reference's
  * wfa_ed (src/util/sequence_alignment.rs:9-13).  The batch packer uses it for Variant::alt_ed
  * (src/data_types/variants.rs:413-415), which travels to the device with the region records. */
