@@ -32,6 +32,7 @@
 #include "avk_pack.h"
 #include "avk_pack_chunks.h"
 #include "avk_counters.h"
+#include "avk_step_plan.h"
 #include "avk_solver.inl"
 #include "avk_lane.inl"
 #include "avk_quad.inl"
@@ -496,6 +497,11 @@ struct avk_ctx {
     hipStream_t spare_stream[16] = {nullptr}; /* never used: see avk_ctx_create */
     int n_placeholders = 0;                   /* how many of them avk_ctx_create made (and destroyed again) */
     hipStream_t wide_stream = nullptr; /* the class C records that are not for the wide kernel (run_internal) */
+    /* the step's plan (avk_step_plan.h): which stream each launch chain of run_internal is queued on */
+    int64_t step_queues = 0;       /* option: 0 by the process's hardware queues (step_folded_auto), 4 the folded plan, 8 a stream per chain */
+    bool step_folded_auto = false; /* GPU_MAX_HW_QUEUES below AVK_STEP_QUEUES_WIDE when the context was made */
+    hipStream_t fold_stream[AVK_STEP_SLOTS_FOLDED - 1] = {nullptr, nullptr, nullptr}; /* the folded plan's streams beside the caller's */
+    bool last_step_chains = false; /* the last step ran with hand-back chains (it recorded no ev_lane_done) */
     std::thread reaper; /* releases the buffers of the last large batch behind the caller (avk_batch_free) */
     std::mutex reaper_mutex;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_wide = nullptr;
@@ -661,11 +667,22 @@ const char *avk_last_error(const avk_ctx *ctx) {
     return g_create_error.c_str();
 }
 
+/* the streams of the folded step plan: at context creation when the process has few hardware queues, else when a step first asks for them (option step_queues=4) */
+static hipError_t ensure_fold_streams(avk_ctx *ctx) {
+    for (hipStream_t &st : ctx->fold_stream)
+        if (!st) {
+            const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
 int avk_ctx_create(int device_id, avk_ctx **out) {
     if (!out) return AVK_E_ARG;
     *out = nullptr;
     /* six streams side by side need hardware queues of their own (the runtime's default is 4 and streams that share one run in turn);
-     * read by the runtime when it initialises, so this helps when this is the process's first HIP call; the caller's setting wins */
+     * read by the runtime when it initialises, so this helps when this is the process's first HIP call; the caller's setting wins (with fewer than eight queues
+     * the step folds its chains onto four streams: below) */
     setenv("GPU_MAX_HW_QUEUES", "24", 0); /* 8 are enough for this library alone; with a communicator (RCCL) in the process 8 make the step 6.0 ms instead of 3.8 */
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -692,6 +709,17 @@ int avk_ctx_create(int device_id, avk_ctx **out) {
         return fail(nullptr, AVK_E_HIP, "hipStreamCreate failed");
     }
     ctx->own_stream = true;
+    { /* the step's plan, by the hardware queues the runtime will see (the variable as it stands after the setenv above; not a number: a stream per chain).  The folded
+       * plan's three streams are made directly behind the context's own, ahead of every other stream, so that the four take the process's first four queues
+       * (profiles/step_four_queues.txt has the queue ids of a trace); AVK_STREAM_ORDER below does not place them */
+        const char *q = getenv("GPU_MAX_HW_QUEUES");
+        const int nq = q ? atoi(q) : 0;
+        ctx->step_folded_auto = nq > 0 && nq < AVK_STEP_QUEUES_WIDE;
+        if (ctx->step_folded_auto && ensure_fold_streams(ctx) != hipSuccess) {
+            avk_ctx_destroy(ctx);
+            return fail(nullptr, AVK_E_HIP, "hipStreamCreate failed");
+        }
+    }
     if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess || hipEventCreate(&ctx->evk1) != hipSuccess ||
         hipEventCreate(&ctx->ev_lane) != hipSuccess ||
         /* the buffer pool's fence exists from the start: a resident upload that releases its temporaries in stream order BEFORE the first asynchronous submit must be
@@ -833,6 +861,8 @@ void avk_ctx_destroy(avk_ctx *ctx) {
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->side_stream2) (void)hipStreamDestroy(ctx->side_stream2);
     if (ctx->wide_stream) (void)hipStreamDestroy(ctx->wide_stream);
+    for (hipStream_t fs : ctx->fold_stream)
+        if (fs) (void)hipStreamDestroy(fs);
     for (hipStream_t sp : ctx->spare_stream)
         if (sp) (void)hipStreamDestroy(sp);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -894,6 +924,9 @@ int avk_ctx_set_option(avk_ctx *ctx, const char *name, int64_t value) {
     } else if (n == "claim") {
         if (value < 1 || value > 64) return fail(ctx, AVK_E_ARG, "claim must be in [1, 64]");
         ctx->claim = value;
+    } else if (n == "step_queues") {
+        if (value != 0 && value != AVK_STEP_SLOTS_FOLDED && value != AVK_STEP_QUEUES_WIDE) return fail(ctx, AVK_E_ARG, "step_queues must be 0 (by GPU_MAX_HW_QUEUES), 4 (the folded plan) or 8 (a stream per chain)");
+        ctx->step_queues = value;
     } else if (n == "wide_kernel") {
         ctx->wide_kernel = value ? 1 : 0;
     } else if (n == "wide_lds_bytes") {
@@ -1610,16 +1643,72 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
     const bool timed = ctx->timing_events != 0;
     if (timed) AVK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     ctx->ev_lane_valid = false;
-    const uint32_t big_slots = use[2] && use[3] ? (uint32_t)(big_waves < (int64_t)AVK_CTR_BIG_BUSY_LEN ? big_waves : (int64_t)AVK_CTR_BIG_BUSY_LEN) : 0u;
+    /* ---- the step's plan: the launches below name chains (avk_step_plan.h), the plan gives each chain its stream.  Two chains on one stream follow each other in the
+     * order they are queued here, and the events between them are dropped:
+     *   fork      a stream waits for the caller's stream once, ahead of the first chain queued on it
+     *   end/join  the end of every chain is recorded as today; the caller's stream waits per STREAM, for the last end recorded on it, and not again for an earlier one */
+    const bool folded = ctx->step_queues ? ctx->step_queues < AVK_STEP_QUEUES_WIDE : ctx->step_folded_auto;
+    AvkStepPlan plan = avk_step_plan(folded ? AVK_STEP_SLOTS_FOLDED : AVK_STEP_QUEUES_WIDE, use_fast);
+    if (folded) {
+        AvkStepPlan trial;
+        if (use_fast && avk_step_plan_parse(getenv("AVK_STEP_PLAN"), &trial)) plan = trial; /* (measurements: another assignment, a digit per chain) */
+        AVK_HIP(ctx, ensure_fold_streams(ctx));
+    }
+    hipStream_t slot_stream[AVK_N_CHAINS] = {ctx->stream, ctx->side_stream, ctx->wide_stream, ctx->side_stream2, ctx->lane_stream, ctx->lane_stream2, ctx->lane_stream3, ctx->lane_stream4};
+    if (folded)
+        for (int k = 1; k < AVK_STEP_SLOTS_FOLDED; ++k) slot_stream[k] = ctx->fold_stream[k - 1];
+    auto S = [&](int chain) { return slot_stream[plan.slot[chain]]; };
+    auto same_stream = [&](int c1, int c2) { return plan.slot[c1] == plan.slot[c2]; };
+    bool slot_forked[AVK_N_CHAINS] = {true, false, false, false, false, false, false, false};
+    auto fork = [&](int chain, hipEvent_t ev) { /* ev: recorded on the caller's stream */
+        const int s = plan.slot[chain];
+        if (s == 0 || (folded && slot_forked[s])) return hipSuccess;
+        slot_forked[s] = true;
+        return hipStreamWaitEvent(slot_stream[s], ev, 0);
+    };
+    struct ChainEnd {
+        hipEvent_t ev;
+        int slot, seq;
+    };
+    enum { END_LDS_SOLO, END_CLASS_C, END_NOT_WIDE, END_LANE0, END_LANE1, END_LANE2, END_LANE3, END_EARLY, END_DONE, N_ENDS };
+    ChainEnd ends[N_ENDS];
+    int end_seq = 0, slot_joined[AVK_N_CHAINS] = {0, 0, 0, 0, 0, 0, 0, 0}; /* per stream: the latest end the caller's stream already waits for */
+    auto record_end = [&](int id, hipEvent_t ev, int chain) {
+        ends[id] = {ev, plan.slot[chain], ++end_seq};
+        return hipEventRecord(ev, S(chain));
+    };
+    auto join = [&](const int *ids, int k) { /* the caller's stream waits for these ends (the plan with a stream per chain: each of them, in this order) */
+        int order[N_ENDS];
+        for (int i = 0; i < k; ++i) order[i] = ids[i];
+        if (folded) std::sort(order, order + k, [&](int x, int y) { return ends[x].seq > ends[y].seq; });
+        for (int i = 0; i < k; ++i) {
+            const ChainEnd &e = ends[order[i]];
+            if (e.slot == 0 || (folded && slot_joined[e.slot] >= e.seq)) continue;
+            if (slot_joined[e.slot] < e.seq) slot_joined[e.slot] = e.seq;
+            const hipError_t r = hipStreamWaitEvent(ctx->stream, e.ev, 0);
+            if (r != hipSuccess) return r;
+        }
+        return hipSuccess;
+    };
+    auto join1 = [&](int id) { return join(&id, 1); };
+    const uint32_t big_slots =use[2] && use[3] ? (uint32_t)(big_waves < (int64_t)AVK_CTR_BIG_BUSY_LEN ? big_waves : (int64_t)AVK_CTR_BIG_BUSY_LEN) : 0u;
     const uint32_t *list = nullptr, *count = nullptr; /* first launch: the records themselves are in work order */
     uint32_t *lists[4] = {db->d_overflow, db->d_overflow2, db->d_overflow3, db->d_overflow4};
     int nlist = 0;
     bool solo_pending = false, hbm_solo_pending = false, deferred_pending = false, early_pending = false, hbm_shared = false, wide_x_pending = false, chains = false;
-    hipEvent_t chain_join[4] = {nullptr, nullptr, nullptr, nullptr}; /* handback_chains: the ends of the lane streams' chains, and the launch that follows them at the end of the step */
+    int chain_join[4] = {0, 0, 0, 0}; /* handback_chains: the ends of the lane chains, and the launch that follows them at the end of the step */
     int n_chain_join = 0;
+    bool chains_flushed = false;
     AvkKernelArgs chain_d;
     uint32_t chain_dblocks = 0;
     memset(&chain_d, 0, sizeof(chain_d));
+    auto flush_chains = [&]() { /* what the chains' launches of avk_wide.inl left (d_overflow7): behind the ends of the lane chains, once per step */
+        chains_flushed = true;
+        const hipError_t r = join(chain_join, n_chain_join);
+        if (r != hipSuccess) return r;
+        hipLaunchKernelGGL(avk_region_kernel_lds_lazy, dim3(chain_dblocks), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ctx->stream, chain_d);
+        return hipGetLastError();
+    };
     uint32_t hbm_shared_base = 0; /* records of class C ahead of the shared list (a team launch has them) */
     for (int t = 0; t < 4 && n; ++t) {
         if (!launch[t]) continue;
@@ -1637,16 +1726,12 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
         }
         const bool first_launch = list == nullptr; /* ev0 sits right before it */
         if (t >= 2) { /* the HBM launches read the list the LDS solo launch appends to; the tier-1 launch does not */
-            if (deferred_pending && chains) { /* what the chains' launches of avk_wide.inl left: ahead of the waits for the long solo launches, which it does not depend on */
-                for (int k = 0; k < n_chain_join; ++k) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, chain_join[k], 0));
-                hipLaunchKernelGGL(avk_region_kernel_lds_lazy, dim3(chain_dblocks), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ctx->stream, chain_d);
-                AVK_HIP(ctx, hipGetLastError());
-            }
-            if (solo_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+            if (deferred_pending && chains && !chains_flushed) AVK_HIP(ctx, flush_chains()); /* ahead of the waits for the long solo launches, which it does not depend on */
+            if (solo_pending) AVK_HIP(ctx, join1(END_LDS_SOLO));
             solo_pending = false;
             /* the tier-3 launch of its own (big_slots == 0) reads the list the HBM solo launch appends to */
             if (t == 3 && hbm_solo_pending) {
-                AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join2, 0));
+                AVK_HIP(ctx, join1(END_CLASS_C));
                 hbm_solo_pending = false;
             }
         }
@@ -1694,16 +1779,16 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
             if (hbm_solo && use_wide && db->plan.n_hbm_notwide && 2u * (db->plan.n_hbm_notwide < n_c ? db->plan.n_hbm_notwide : n_c) <= n_c && !db->notwide_ready) { /* (only the class's wide launch with its companion reads the list) */
                 /* the list of the class C records that are not avk_wide.inl's: once per batch, and the FIRST thing queued behind the fork — made behind the class's
                  * wide launch its 20-170 workgroups waited for a place among the step's persistent waves (0.2 ms in a queued shard step, 1.2 ms in a merge call) */
-                AVK_HIP(ctx, hipStreamWaitEvent(ctx->wide_stream, ctx->ev_fork, 0));
-                AVK_HIP(ctx, hipMemsetAsync(db->d_notwide + n + 1, 0, sizeof(uint32_t), ctx->wide_stream));
-                hipLaunchKernelGGL(avk_notwide_list_kernel, dim3((n_c + 255u) / 256u), dim3(256), 0, ctx->wide_stream, db->d_regions, n_c, db->d_notwide, db->d_notwide + n + 1);
+                AVK_HIP(ctx, fork(AVK_CH_NOT_WIDE, ctx->ev_fork));
+                AVK_HIP(ctx, hipMemsetAsync(db->d_notwide + n + 1, 0, sizeof(uint32_t), S(AVK_CH_NOT_WIDE)));
+                hipLaunchKernelGGL(avk_notwide_list_kernel, dim3((n_c + 255u) / 256u), dim3(256), 0, S(AVK_CH_NOT_WIDE), db->d_regions, n_c, db->d_notwide, db->d_notwide + n + 1);
                 AVK_HIP(ctx, hipGetLastError());
                 db->notwide_ready = true;
             }
             bool wide_c = false, wide_x = false;
             if (hbm_solo) {
                 const uint32_t *c_list = nullptr, *c_left = nullptr; /* what the launches of avk_wide.inl leave of class C (without them: the class's records themselves) */
-                AVK_HIP(ctx, hipStreamWaitEvent(ctx->side_stream2, ctx->ev_fork, 0));
+                AVK_HIP(ctx, fork(AVK_CH_CLASS_C, ctx->ev_fork));
                 /* how many of them are not the wide kernel's by their own record (a long window, many calls on a side): none or few in a genome, all of them in a
                  * batch of large windows (--min-variant-gap 1000) — which then keeps the launches of round 3: every HBM wave on the whole list */
                 const uint32_t n_nw = db->plan.n_hbm_notwide < n_c ? db->plan.n_hbm_notwide : n_c;
@@ -1733,7 +1818,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                     if (2u * xb > hbm_solo_max) xb = hbm_solo_max / 2u;
                     avk::wide::WideArgs wc = wa;
                     wc.skip_static = n_nw && xb ? 1u : 0u; /* (without the launch below such a record is handed over like any other) */
-                    hipLaunchKernelGGL(avk_wide_kernel, dim3(wg), dim3(64), (size_t)ctx->wide_lds_bytes, ctx->side_stream2, w, wc);
+                    hipLaunchKernelGGL(avk_wide_kernel, dim3(wg), dim3(64), (size_t)ctx->wide_lds_bytes, S(AVK_CH_CLASS_C), w, wc);
                     AVK_HIP(ctx, hipGetLastError());
                     if (n_nw && xb) { /* the records of class C that are not for the wide kernel by what they say themselves (avk_wide_static_ok: a long window, many calls on a
                        * side) start at the same time, on the HBM-tier kernel and a stream of their own: they are few and each of them is long */
@@ -1745,12 +1830,12 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         x.n_waves = xb * waves_per_block;
                         x.hbm_ws = ctx->d_ws + (size_t)(n_waves + (hbm_solo_max - xb) * waves_per_block) * (size_t)ws_bytes; /* the last slices of the solo launch's share (that launch gets the others) */
                         avk_big_slice_args(x, ctx->d_big, db->d_counters, big_slots);
-                        AVK_HIP(ctx, hipStreamWaitEvent(ctx->wide_stream, ctx->ev_fork, 0));
+                        AVK_HIP(ctx, fork(AVK_CH_NOT_WIDE, ctx->ev_fork));
                         /* (a wave per region here: these long windows hold a handful of calls, their searches are short chains where a team's hand-overs cost more
                          * than its parallel pieces give — shard 1.19 -> 1.31 ms, dense mix 2.29 -> 2.53 with teams, profiles/r06_team.txt) */
-                        hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(xb), dim3(256), 0, ctx->wide_stream, x);
+                        hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(xb), dim3(256), 0, S(AVK_CH_NOT_WIDE), x);
                         AVK_HIP(ctx, hipGetLastError());
-                        AVK_HIP(ctx, hipEventRecord(ctx->ev_wide, ctx->wide_stream));
+                        AVK_HIP(ctx, record_end(END_NOT_WIDE, ctx->ev_wide, AVK_CH_NOT_WIDE));
                         wide_x = true;
                         if (hbm_solo > hbm_solo_max - xb) hbm_solo = hbm_solo_max - xb; /* (at least half of the share: xb <= hbm_solo_max / 2) */
                     }
@@ -1770,7 +1855,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         w2.overflow_count = db->d_counters + AVK_CTR_WIDE_RETRY_LEFT;
                         avk::wide::WideArgs wb = wa;
                         wb.lds_words = (uint32_t)(ctx->wide_retry_lds_bytes / 4);
-                        hipLaunchKernelGGL(avk_wide_kernel, dim3(32), dim3(64), (size_t)ctx->wide_retry_lds_bytes, ctx->side_stream2, w2, wb);
+                        hipLaunchKernelGGL(avk_wide_kernel, dim3(32), dim3(64), (size_t)ctx->wide_retry_lds_bytes, S(AVK_CH_CLASS_C), w2, wb);
                         AVK_HIP(ctx, hipGetLastError());
                         c_list = db->d_overflow8;
                         c_left = db->d_counters + AVK_CTR_WIDE_RETRY_LEFT;
@@ -1792,10 +1877,10 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         x.n_waves = xb * waves_per_block;
                         x.hbm_ws = ctx->d_ws + (size_t)(n_waves + (hbm_solo_max - xb) * waves_per_block) * (size_t)ws_bytes; /* the last slices of the solo launch's share */
                         avk_big_slice_args(x, ctx->d_big, db->d_counters, big_slots);
-                        AVK_HIP(ctx, hipStreamWaitEvent(ctx->wide_stream, ctx->ev_fork, 0));
-                        hipLaunchKernelGGL(avk_region_kernel_team, dim3(xb), dim3(256), 0, ctx->wide_stream, x);
+                        AVK_HIP(ctx, fork(AVK_CH_NOT_WIDE, ctx->ev_fork));
+                        hipLaunchKernelGGL(avk_region_kernel_team, dim3(xb), dim3(256), 0, S(AVK_CH_NOT_WIDE), x);
                         AVK_HIP(ctx, hipGetLastError());
-                        AVK_HIP(ctx, hipEventRecord(ctx->ev_wide, ctx->wide_stream));
+                        AVK_HIP(ctx, record_end(END_NOT_WIDE, ctx->ev_wide, AVK_CH_NOT_WIDE));
                         wide_x = true;
                         team_head = xb;
                         if (hbm_solo > hbm_solo_max - xb) hbm_solo = hbm_solo_max - xb;
@@ -1814,9 +1899,9 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                     s.overflow_list = lists[launch[1] ? 2 : 1];
                     s.overflow_count = db->d_counters + avk_ctr_overflow_count(launch[1] ? 2 : 1);
                 }
-                hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(hbm_solo), dim3(256), 0, ctx->side_stream2, s);
+                hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(hbm_solo), dim3(256), 0, S(AVK_CH_CLASS_C), s);
                 AVK_HIP(ctx, hipGetLastError());
-                AVK_HIP(ctx, hipEventRecord(ctx->ev_join2, ctx->side_stream2));
+                AVK_HIP(ctx, record_end(END_CLASS_C, ctx->ev_join2, AVK_CH_CLASS_C));
                 hbm_solo_pending = true;
                 hbm_shared = !wide_c; /* (the records of class C are the wide launch's: the main stream's HBM launch has nothing to share) */
                 hbm_shared_base = team_head;
@@ -1835,10 +1920,10 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                 s.high_priority = 1;
                 s.overflow_list = later ? lists[solo_list] : nullptr;
                 s.overflow_count = later ? db->d_counters + avk_ctr_overflow_count((uint32_t)solo_list) : nullptr;
-                AVK_HIP(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-                hipLaunchKernelGGL(avk_region_kernel_lds, dim3(solo), dim3(64), (size_t)ctx->lds2_bytes_per_wave, ctx->side_stream, s);
+                AVK_HIP(ctx, fork(AVK_CH_LDS_SOLO, ctx->ev_fork));
+                hipLaunchKernelGGL(avk_region_kernel_lds, dim3(solo), dim3(64), (size_t)ctx->lds2_bytes_per_wave, S(AVK_CH_LDS_SOLO), s);
                 AVK_HIP(ctx, hipGetLastError());
-                AVK_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream));
+                AVK_HIP(ctx, record_end(END_LDS_SOLO, ctx->ev_join, AVK_CH_LDS_SOLO));
                 solo_pending = true;
             }
             if (solo || hbm_solo) {
@@ -1848,10 +1933,12 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
             /* ---- the lane-per-region launches (avk_lane.inl): the classes with two calls per side (long, latency-bound tiles at low
              * occupancy) on a stream of their own, the one-call classes on the caller's stream ahead of the bulk.  What a lane cannot
              * finish goes to the DEFERRED list, solved after the bulk by an LDS launch of the wave-per-region kernel. */
-            /* lane streams: 0 the two-call classes, 1 the one-call classes, 2 the three-call class, 3 the heads of the two-call classes */
+            /* lane chains: 0 the two-call classes, 1 the one-call classes, 2 the three-call class, 3 the heads of the two-call classes */
             enum { N_LS = 4 };
-            hipStream_t lstream[N_LS] = {ctx->lane_stream, ctx->lane_stream2, ctx->lane_stream3, ctx->lane_stream4};
+            const int lchain[N_LS] = {AVK_CH_TWO_CALL, AVK_CH_ONE_CALL, AVK_CH_THREE_CALL, AVK_CH_HEAD_HANDBACKS};
+            hipStream_t lstream[N_LS] = {S(lchain[0]), S(lchain[1]), S(lchain[2]), S(lchain[3])};
             hipEvent_t ljoin[N_LS] = {ctx->ev_lane_join, ctx->ev_lane_join2, ctx->ev_lane_join3, ctx->ev_lane_join4};
+            const int lend[N_LS] = {END_LANE0, END_LANE1, END_LANE2, END_LANE3};
             bool lused[N_LS] = {false, false, false, false}, ljoined[N_LS] = {false, false, false, false}, early_used = false;
             if (use_fast) {
                 if (!ctx->lane_attr_set) {
@@ -1912,7 +1999,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                          * 1.04 -> 1.00 ms, a genome's 2.33 -> 2.39: profiles/r06_handback_chains.txt) */
                         const int li = chains && getenv("AVK_PAIRS_OWN_STREAM") ? 3 : 1;
                         if (!lused[li]) {
-                            AVK_HIP(ctx, hipStreamWaitEvent(lstream[li], ctx->ev_lane_fork, 0));
+                            AVK_HIP(ctx, fork(lchain[li], ctx->ev_lane_fork));
                             lused[li] = true;
                         }
                         const int rt = ensure_pair_table(ctx, cfg->max_branch_factor, lstream[li]);
@@ -1959,7 +2046,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                     if (!lds) return fail(ctx, AVK_E_ARG, "lane kernel class %d does not fit the LDS", fc);
                     const int li = cl.maxv == 2 ? 0 : (cl.maxv == 1 ? 1 : 2);
                     if (!lused[li]) {
-                        AVK_HIP(ctx, hipStreamWaitEvent(lstream[li], ctx->ev_lane_fork, 0));
+                        AVK_HIP(ctx, fork(lchain[li], ctx->ev_lane_fork));
                         lused[li] = true;
                     }
                     if (cl.maxv > 2) {
@@ -1973,7 +2060,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         launch_lane_class(ctx, grid, lds, lstream[li], f3, la);
                         AVK_HIP(ctx, hipGetLastError());
                         /* the launch for what ALL lanes hand back waits for the lane launches only, not for the launch behind this class */
-                        AVK_HIP(ctx, hipEventRecord(ljoin[li], lstream[li]));
+                        AVK_HIP(ctx, record_end(lend[li], ljoin[li], lchain[li]));
                         ljoined[li] = true;
                         AvkKernelArgs e = avk_list_reader_args(a, lists[3], db->d_counters + AVK_CTR_HB3_COUNT, db->d_counters + AVK_CTR_HB3_CURSOR);
                         e.pass_tier = 2;
@@ -1994,7 +2081,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         e.n_waves = eb * waves_per_block;
                         hipLaunchKernelGGL(avk_region_kernel_hbm_lazy, dim3(eb), dim3(256), 0, es, e);
                         AVK_HIP(ctx, hipGetLastError());
-                        AVK_HIP(ctx, hipEventRecord(ctx->ev_lane_early, es)); /* the caller's stream waits for this one at the end */
+                        AVK_HIP(ctx, record_end(END_EARLY, ctx->ev_lane_early, lchain[li])); /* the caller's stream waits for this one at the end */
                         early_used = true;
                         continue;
                     }
@@ -2012,7 +2099,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         const size_t hlds = lane_launch_geometry(ctx, hd, &hgrid);
                         const int hi = (cl.maxv == 2 && ctx->lane_head_stream) ? 3 : li; /* a long head runs beside the rest of its class */
                         if (!lused[hi]) {
-                            AVK_HIP(ctx, hipStreamWaitEvent(lstream[hi], ctx->ev_lane_fork, 0));
+                            AVK_HIP(ctx, fork(lchain[hi], ctx->ev_lane_fork));
                             lused[hi] = true;
                         }
                         AvkKernelArgs fh = f;
@@ -2025,10 +2112,12 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         } else if (chains) {
                             fh.overflow_list = chain_seg[li].list, fh.overflow_count = chain_seg[li].count;
                         }
-                        launch_lane_class(ctx, hgrid, hlds, lstream[hi], fh, hd, staged ? ctx->ev_hb[hb_heads] : nullptr);
+                        const bool hb_follows = same_stream(lchain[hi], lchain[3]); /* the consumer follows its head in stream order: no event */
+                        launch_lane_class(ctx, hgrid, hlds, lstream[hi], fh, hd, staged && !hb_follows ? ctx->ev_hb[hb_heads] : nullptr);
                         AVK_HIP(ctx, hipGetLastError());
                         if (staged) { /* its hand-backs: solved beside the rest of the class */
-                            AVK_HIP(ctx, hipStreamWaitEvent(lstream[3], ctx->ev_hb[hb_heads], 0));
+                            if (!hb_follows) AVK_HIP(ctx, hipStreamWaitEvent(lstream[3], ctx->ev_hb[hb_heads], 0));
+                            slot_forked[plan.slot[lchain[3]]] = true;
                             lused[3] = true; /* (its first command waits for an event behind ev_lane_fork) */
                             AVK_HIP(ctx, hb_consume(lstream[3], hseg));
                             hb_heads += 1;
@@ -2048,10 +2137,10 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                         if (lused[li]) AVK_HIP(ctx, hb_consume(lstream[li], chain_seg[li]));
                 for (int li = 0; li < N_LS; ++li) {
                     if (!lused[li]) continue;
-                    if (!ljoined[li]) AVK_HIP(ctx, hipEventRecord(ljoin[li], lstream[li]));
+                    if (!ljoined[li]) AVK_HIP(ctx, record_end(lend[li], ljoin[li], lchain[li]));
                 }
                 if (lused[1] && timed) { /* end of the one-call classes' launches */
-                    AVK_HIP(ctx, hipEventRecord(ctx->ev_lane, ctx->lane_stream2));
+                    AVK_HIP(ctx, hipEventRecord(ctx->ev_lane, lstream[1]));
                     ctx->ev_lane_valid = true;
                 }
             }
@@ -2083,10 +2172,10 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                 hipStream_t ds = lstream[di];
                 if (chains) { /* every list has been through avk_wide.inl on its own stream; what that left is for the caller's stream at the end of the step (below) */
                     for (int li = 0; li < N_LS; ++li)
-                        if (lused[li]) chain_join[n_chain_join++] = ljoin[li];
+                        if (lused[li]) chain_join[n_chain_join++] = lend[li];
                 } else {
                     for (int li = 0; li < N_LS; ++li)
-                        if (li != di && lused[li]) AVK_HIP(ctx, hipStreamWaitEvent(ds, ljoin[li], 0));
+                        if (li != di && lused[li] && !same_stream(lchain[li], lchain[di])) AVK_HIP(ctx, hipStreamWaitEvent(ds, ljoin[li], 0));
                 }
                 AvkKernelArgs d = a;
                 d.work_list = chains ? db->d_overflow7 : lists[2];
@@ -2114,7 +2203,7 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
                 } else {
                     hipLaunchKernelGGL(avk_region_kernel_lds_lazy, dim3(dblocks), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ds, d);
                     AVK_HIP(ctx, hipGetLastError());
-                    AVK_HIP(ctx, hipEventRecord(ctx->ev_lane_done, ds)); /* everything of the lane streams is behind this record */
+                    AVK_HIP(ctx, record_end(END_DONE, ctx->ev_lane_done, lchain[di])); /* everything of the lane chains is behind this record */
                 }
                 deferred_pending = true;
                 early_pending = early_used;
@@ -2152,12 +2241,19 @@ static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, c
             nlist += 1;
         }
     }
-    if (solo_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-    if (hbm_solo_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join2, 0));
-    if (wide_x_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_wide, 0));
-    if (deferred_pending) { /* the lane streams (lane launches, then the handed-back regions) join here; what even the escalation could not hold */
-        if (!chains) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_lane_done, 0));
-        if (early_pending) AVK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_lane_early, 0));
+    /* (no launch of an HBM tier's own — both tiers off — has flushed the chains: never with lanes today, use_fast asks for the tier-2 launch) */
+    if (deferred_pending && chains && !chains_flushed) AVK_HIP(ctx, flush_chains());
+    { /* the end of the step: every stream that still has a chain the caller's stream has not waited for */
+        int pending[5], k = 0;
+        if (solo_pending) pending[k++] = END_LDS_SOLO;
+        if (hbm_solo_pending) pending[k++] = END_CLASS_C;
+        if (wide_x_pending) pending[k++] = END_NOT_WIDE;
+        if (deferred_pending && !chains) pending[k++] = END_DONE;
+        if (deferred_pending && early_pending) pending[k++] = END_EARLY;
+        AVK_HIP(ctx, join(pending, k));
+    }
+    ctx->last_step_chains = chains;
+    if (deferred_pending) { /* the lane chains (lane launches, then the handed-back regions) have joined; what even the escalation could not hold */
         AvkKernelArgs h = avk_list_reader_args(a, lists[1], db->d_counters + avk_ctr_overflow_count(1), db->d_counters + AVK_CTR_LAST_CURSOR);
         h.pass_tier = 2;
         h.high_priority = 0;
@@ -3761,7 +3857,7 @@ static void packed_timeline_print(avk_ctx *ctx) {
     /* where each chain of the launch graph ended, from the first solver launch (events of this call only when the batch used the chain) */
     const struct { const char *what; hipEvent_t ev; } chains[] = {{"LDS solo", ctx->ev_join}, {"HBM solo", ctx->ev_join2}, {"wide", ctx->ev_wide}, {"lane stream 1", ctx->ev_lane_join},
         {"lane stream 2", ctx->ev_lane_join2}, {"lane stream 3", ctx->ev_lane_join3}, {"lane stream 4", ctx->ev_lane_join4}, {"early hand-backs", ctx->ev_lane_early},
-        {"hand-back launches", ctx->ev_lane_done}};
+        {"hand-back launches", ctx->last_step_chains ? nullptr : ctx->ev_lane_done}}; /* (a step with hand-back chains records no such end) */
     fprintf(stderr, "avk compare packed, chains end (ms after the first solver launch):");
     for (const auto &c : chains) {
         float t = 0;

@@ -357,7 +357,10 @@ int  avk_ctx_set_stream(avk_ctx *ctx, void *hip_stream);
  *                    avk_compare_resident ADDS the batch tally to tally_dev)
  *                    Options are read when a batch is submitted: a batch in flight (avk_compare_packed_submit .. avk_wait) keeps the values of its submit.
  * The launches of one call run on HIP streams side by side; the HIP runtime gives a process 4 hardware queues by default and streams that share one take turns:
- * avk_ctx_create sets GPU_MAX_HW_QUEUES=24 unless the environment already has it (effective when it is the process's first HIP call). */
+ * avk_ctx_create sets GPU_MAX_HW_QUEUES=24 unless the environment already has it (effective when it is the process's first HIP call).
+ *   launch plan      "step_queues" (0: by the value of GPU_MAX_HW_QUEUES when the context was made — below 8 the launch chains of a step are folded onto the context's
+ *                    stream and three more, each chain whole and behind another, avk_step_plan.h and DESIGN section 4.7; 4: always folded; 8: always a stream per
+ *                    chain — same results either way) */
 int  avk_ctx_set_option(avk_ctx *ctx, const char *name, int64_t value);
 
 /* Replaces ReferenceGenome::from_fasta + get_full_chromosome (src/main.rs:94,
