@@ -191,6 +191,66 @@ def declare_submit_strata(lib):
     lib.avk_compare_packed_submit_strata.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkResultBatch), _p(C.c_uint64), _p(vp)]
 
 
+CONTEXT_PAD_MAX, CONTEXT_GC_EDGES_MAX, CONTEXT_HP_EDGES_MAX = 1024, 17, 16
+
+
+class AvkContextSpec(C.Structure):
+    """avk_context_spec: the sequence-context labels of a stratified job (GC bins, homopolymer classes)"""
+    _fields_ = [("gc_pad", C.c_uint32), ("n_gc_edges", C.c_uint32), ("gc_edges", C.c_uint32 * CONTEXT_GC_EDGES_MAX),
+                ("hp_pad", C.c_uint32), ("n_hp_edges", C.c_uint32), ("hp_edges", C.c_uint32 * CONTEXT_HP_EDGES_MAX)]
+
+
+def declare_context_strata(lib):
+    """avk_strata_upload_context, avk_strata_n_context_labels, avk_context_label_name (include/aardvark_amd.h)"""
+    vp, u32p = C.c_void_p, _p(C.c_uint32)
+    lib.avk_strata_upload_context.restype = C.c_int
+    lib.avk_strata_upload_context.argtypes = [vp, C.c_uint32, C.c_uint32, _p(C.c_uint64), u32p, u32p, _p(AvkContextSpec), _p(vp)]
+    lib.avk_strata_n_context_labels.restype = C.c_uint32
+    lib.avk_strata_n_context_labels.argtypes = [vp]
+    lib.avk_context_label_name.restype = C.c_int
+    lib.avk_context_label_name.argtypes = [_p(AvkContextSpec), C.c_uint32, C.c_char_p, C.c_size_t]
+
+
+class ContextSpec:
+    """The sequence-context labels of a stratified job: gc_edges percent values (n - 1 labels, window pad gc_pad), hp_edges run lengths (n labels, window pad
+    hp_pad); an empty family does not exist.  The defaults are the tool's (--context-strata gc,hp)."""
+    GC_EDGES = (0, 15, 20, 25, 30, 55, 60, 65, 70, 75, 80, 85, 101)
+    HP_EDGES = (4, 7, 12, 21)
+
+    def __init__(self, gc_edges=GC_EDGES, hp_edges=HP_EDGES, gc_pad=50, hp_pad=5):
+        self.gc_edges, self.hp_edges = tuple(int(x) for x in gc_edges), tuple(int(x) for x in hp_edges)
+        self.gc_pad, self.hp_pad = int(gc_pad), int(hp_pad)
+        if len(self.gc_edges) > CONTEXT_GC_EDGES_MAX or len(self.hp_edges) > CONTEXT_HP_EDGES_MAX:
+            raise ValueError("at most %d GC edges and %d run edges" % (CONTEXT_GC_EDGES_MAX, CONTEXT_HP_EDGES_MAX))
+        if min(self.gc_edges + self.hp_edges + (self.gc_pad, self.hp_pad), default=0) < 0:
+            raise ValueError("edges and pads are not negative")
+
+    @property
+    def n_labels(self):
+        return max(len(self.gc_edges) - 1, 0) + len(self.hp_edges)
+
+    def c_struct(self):
+        s = AvkContextSpec()
+        s.gc_pad, s.n_gc_edges, s.hp_pad, s.n_hp_edges = self.gc_pad, len(self.gc_edges), self.hp_pad, len(self.hp_edges)
+        for i, x in enumerate(self.gc_edges):
+            s.gc_edges[i] = x
+        for i, x in enumerate(self.hp_edges):
+            s.hp_edges[i] = x
+        return s
+
+    def names(self, lib=None):
+        """avk_context_label_name for every label, in label order (host only: no device, no context)"""
+        if lib is None:
+            from .api import load_library
+            lib = load_library()
+        s, buf, out = self.c_struct(), C.create_string_buffer(64), []
+        for j in range(self.n_labels):
+            if lib.avk_context_label_name(C.byref(s), j, buf, len(buf)):
+                raise ValueError((lib.avk_last_error(None) or b"invalid context spec").decode())
+            out.append(buf.value.decode())
+        return out
+
+
 def declare_debug_ref_packed(lib):
     """avk_debug_ref_packed(avk_ctx *, uint32_t *words_out, uint64_t n_words_cap, uint32_t *flags_out, uint64_t n_flag_words_cap) -> int"""
     lib.avk_debug_ref_packed.restype = C.c_int

@@ -13,7 +13,8 @@ import weakref
 import numpy as np
 
 from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
-                   PackedBatch, RegionBatch, ResultBatch, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes, region_labels)
+                   PackedBatch, RegionBatch, ResultBatch, ContextSpec, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
+                   region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -87,6 +88,8 @@ def load_library():
         lib.avk_compare_packed_strata.argtypes = [vp, C.POINTER(AvkPackedBatch), esc, vp, C.POINTER(AvkCompareConfig), C.POINTER(AvkResultBatch), u64p]
     if hasattr(lib, "avk_compare_packed_submit_strata"):  # the submit with resident sets (AVK_LIB may name an older in-tree build: A/B runs)
         declare_submit_strata(lib)
+    if hasattr(lib, "avk_strata_upload_context"):  # sequence-context labels behind the sets' (avk_context.inl); (AVK_LIB may name an older in-tree build: A/B runs)
+        declare_context_strata(lib)
     if hasattr(lib, "avk_debug_ref_packed"):  # (AVK_LIB may name an older in-tree build: A/B runs)
         declare_debug_ref_packed(lib)
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
@@ -163,9 +166,10 @@ class ResidentBatch:
 
 class Strata:
     """The interval sets of a stratified job resident in HBM (avk_strata): uploaded once per context, then handed to solve_packed(strata=..),
-    label_tallies_strata and strata_region_labels in place of label lists."""
+    label_tallies_strata and strata_region_labels in place of label lists.  context=a ContextSpec: its sequence-context labels follow the sets' labels
+    (avk_strata_upload_context); n_labels is then the total, n_context_labels the number of those."""
 
-    def __init__(self, ctx, n_labels, n_contigs, tree_off, start, end_max):
+    def __init__(self, ctx, n_labels, n_contigs, tree_off, start, end_max, context=None):
         self.ctx = ctx
         self.handle = C.c_void_p()
         tree_off = np.ascontiguousarray(tree_off, np.uint64)
@@ -173,9 +177,15 @@ class Strata:
         if len(tree_off) != int(n_labels) * int(n_contigs) + 1 or len(start) != len(end_max) or (len(tree_off) and int(tree_off[-1]) > len(start)):
             raise ValueError("strata arrays do not fit n_labels * n_contigs trees")
         u32p = C.POINTER(C.c_uint32)
-        ctx._check(ctx.lib.avk_strata_upload(ctx.handle, int(n_labels), int(n_contigs), tree_off.ctypes.data_as(u64p), start.ctypes.data_as(u32p) if len(start) else None,
-                                             end_max.ctypes.data_as(u32p) if len(end_max) else None, C.byref(self.handle)))
+        if context is None:
+            ctx._check(ctx.lib.avk_strata_upload(ctx.handle, int(n_labels), int(n_contigs), tree_off.ctypes.data_as(u64p), start.ctypes.data_as(u32p) if len(start) else None,
+                                                 end_max.ctypes.data_as(u32p) if len(end_max) else None, C.byref(self.handle)))
+        else:
+            spec = context.c_struct()
+            ctx._check(ctx.lib.avk_strata_upload_context(ctx.handle, int(n_labels), int(n_contigs), tree_off.ctypes.data_as(u64p), start.ctypes.data_as(u32p) if len(start) else None,
+                                                         end_max.ctypes.data_as(u32p) if len(end_max) else None, C.byref(spec), C.byref(self.handle)))
         self.n_labels = int(ctx.lib.avk_strata_n_labels(self.handle))
+        self.n_context_labels = 0 if context is None else int(ctx.lib.avk_strata_n_context_labels(self.handle))
         self.n_intervals = int(tree_off[-1]) - int(tree_off[0])
         ctx.__dict__.setdefault("_strata", weakref.WeakSet()).add(self)  # (Context.close frees the handles it still has: a handle must not outlive its context)
 
@@ -455,9 +465,11 @@ class Context:
         self._check(self.lib.avk_label_tallies_compact(self.handle, rb.handle, C.byref(lab), out.ctypes.data_as(u64p)))
         return out
 
-    def upload_strata(self, n_labels, n_contigs, tree_off, start, end_max):
-        """avk_strata_upload: the interval sets of a stratified job (Stratifications.export(genome) of the feeder) into HBM, once -> Strata"""
-        return Strata(self, n_labels, n_contigs, tree_off, start, end_max)
+    def upload_strata(self, n_labels, n_contigs, tree_off, start, end_max, context=None):
+        """avk_strata_upload: the interval sets of a stratified job (Stratifications.export(genome) of the feeder) into HBM, once -> Strata.
+        context=a ContextSpec: avk_strata_upload_context — GC and homopolymer labels, made by kernel from the uploaded reference, behind the sets' labels
+        (n_labels == 0 with tree_off == [0]: context labels only)"""
+        return Strata(self, n_labels, n_contigs, tree_off, start, end_max, context)
 
     def strata_region_labels(self, rb, strata):
         """avk_strata_region_labels: the containment lists of a resident batch, made on the device -> (label_off[n + 1], label_idx)"""

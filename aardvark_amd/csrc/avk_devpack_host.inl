@@ -900,16 +900,32 @@ static void release_pooled(avk_ctx *ctx, avk_dev_batch *db) {
 /* ---- the containment lists of a stratified batch, made on the device (avk_strata.inl) ------------------------------------------------------------------ */
 static avk::sx::SxTrees strata_trees(const avk_strata *st) {
     avk::sx::SxTrees t;
-    t.tree_off = st->d_tree_off, t.start = st->d_start, t.end_max = st->d_end_max, t.n_labels = st->n_labels, t.n_contigs = st->n_contigs;
+    t.tree_off = st->d_tree_off, t.start = st->d_start, t.end_max = st->d_end_max, t.n_labels = st->n_bed_labels, t.n_contigs = st->n_contigs;
     return t;
 }
 static inline uint32_t strata_words(const avk_strata *st) { return (st->n_labels + 31u) / 32u; }
 static inline uint32_t strata_blocks(uint64_t n) { return (uint32_t)((n + 255) / 256); }
+/* The mask pass of a handle: the BED labels' kernel (a handle with such labels), then — ONLY for a handle with context labels — avk_context_mask_kernel directly
+ * behind it on the same stream, same grid.  The reference is the context's as it is now (the entry points have checked that it is there and has the handle's
+ * number of contigs: strata_handle_check). */
+static void strata_mask_kernels(const avk_strata *st, const dpk::DpIn &in, uint64_t n, uint32_t *d_mask, uint64_t *d_sums, hipStream_t s) {
+    const uint32_t nb = strata_blocks(n);
+    if (st->n_bed_labels || !st->n_ctx_labels) /* (the second term: a handle without context labels launches what it always launched, with whatever labels it has) */
+        hipLaunchKernelGGL(avk_strata_mask_kernel, dim3(nb), dim3(256), 0, s, in, strata_trees(st), (uint32_t)n, d_mask, (unsigned long long *)d_sums);
+    if (st->n_ctx_labels) {
+        const avk_ctx *ctx = st->ctx;
+        avk::cx::CxRef ref;
+        ref.bytes = ctx->d_ref, ref.packed = ctx->d_ref2b, ref.exc = ctx->d_refexc, ref.contig_base = ctx->d_contig_tab, ref.contig_len = ctx->d_contig_tab + ctx->contig_len.size(),
+        ref.n_contigs = (uint32_t)ctx->contig_len.size();
+        hipLaunchKernelGGL(avk_context_mask_kernel, dim3(nb), dim3(256), 0, s, in, ref, st->spec, st->n_bed_labels, (uint32_t)n, st->n_bed_labels ? 0u : 1u, d_mask,
+                           (unsigned long long *)d_sums);
+    }
+}
 /* pass 1 and the scan of its workgroup sums: d_mask[strata_words * n], d_sums[strata_blocks(n) + 1] — the workgroups' bases, then the number of list entries */
 static hipError_t strata_count_launch(const avk_strata *st, const dpk::DpIn &in, uint64_t n, uint32_t *d_mask, uint64_t *d_sums, hipStream_t s) {
     if (!n) return hipSuccess;
     const uint32_t nb = strata_blocks(n);
-    hipLaunchKernelGGL(avk_strata_mask_kernel, dim3(nb), dim3(256), 0, s, in, strata_trees(st), (uint32_t)n, d_mask, (unsigned long long *)d_sums);
+    strata_mask_kernels(st, in, n, d_mask, d_sums, s);
     hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, s, d_sums, nb, d_sums + nb);
     return hipGetLastError();
 }
@@ -917,7 +933,7 @@ static hipError_t strata_count_launch(const avk_strata *st, const dpk::DpIn &in,
  * workgroups' counts the kernel writes */
 static hipError_t strata_mask_launch(const avk_strata *st, const dpk::DpIn &in, uint64_t n, uint32_t *d_mask, uint64_t *d_sums, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(avk_strata_mask_kernel, dim3(strata_blocks(n)), dim3(256), 0, s, in, strata_trees(st), (uint32_t)n, d_mask, (unsigned long long *)d_sums);
+    strata_mask_kernels(st, in, n, d_mask, d_sums, s);
     return hipGetLastError();
 }
 /* pass 2: the offsets, and with d_idx the indices (idx_cap entries of room) */

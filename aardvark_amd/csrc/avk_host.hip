@@ -41,6 +41,7 @@
 #include "avk_devpack.inl"
 #include "avk_labels.inl"
 #include "avk_strata.inl"
+#include "avk_context.inl"
 #include "avk_mergecount.inl"
 #include "avk_mergesweep.inl"
 static_assert((int)avk::ms::MS_KMAX == (int)avk::dp::DP_MERGE_KMAX, "the sweep kernel decides what the classification kernel decides");
@@ -575,7 +576,10 @@ struct StrataUse {
 };
 struct avk_strata {
     avk_ctx *ctx = nullptr;
-    uint32_t n_labels = 0, n_contigs = 0;
+    uint32_t n_labels = 0, n_contigs = 0; /* n_labels: ALL labels, the BED labels then the context labels */
+    uint32_t n_bed_labels = 0;            /* the labels the trees answer for */
+    uint32_t n_ctx_labels = 0;            /* the sequence-context labels behind them (avk_context.inl); 0: the handle queues no context kernel */
+    avk::cx::CxSpec spec{};
     uint64_t n_intervals = 0;
     uint64_t *d_tree_off = nullptr;
     uint32_t *d_start = nullptr, *d_end_max = nullptr;
@@ -3715,18 +3719,65 @@ static int strata_check(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs, con
     return 0;
 }
 
+/* the refusals of a context spec (avk_strata_upload_context, avk_context_label_name): no device involved */
+static int context_spec_check(avk_ctx *ctx, const avk_context_spec *sp) {
+    if (sp->n_gc_edges > AVK_CONTEXT_GC_EDGES_MAX || sp->n_hp_edges > AVK_CONTEXT_HP_EDGES_MAX)
+        return fail(ctx, AVK_E_ARG, "context labels: at most %d GC edges and %d run edges", AVK_CONTEXT_GC_EDGES_MAX, AVK_CONTEXT_HP_EDGES_MAX);
+    if (sp->n_gc_edges == 0 && sp->n_hp_edges == 0) return fail(ctx, AVK_E_ARG, "context labels: both families are empty");
+    if (sp->n_gc_edges == 1) return fail(ctx, AVK_E_ARG, "context labels: one GC edge makes no label");
+    if ((sp->n_gc_edges && sp->gc_pad > AVK_CONTEXT_PAD_MAX) || (sp->n_hp_edges && sp->hp_pad > AVK_CONTEXT_PAD_MAX))
+        return fail(ctx, AVK_E_ARG, "context labels: a pad above %d", AVK_CONTEXT_PAD_MAX);
+    for (uint32_t i = 0; i < sp->n_gc_edges; ++i) {
+        if (sp->gc_edges[i] > 101u) return fail(ctx, AVK_E_ARG, "context labels: GC edge %u is above 101", sp->gc_edges[i]);
+        if (i && sp->gc_edges[i] <= sp->gc_edges[i - 1]) return fail(ctx, AVK_E_ARG, "context labels: the GC edges are not strictly ascending");
+    }
+    for (uint32_t i = 0; i < sp->n_hp_edges; ++i) {
+        if (sp->hp_edges[i] == 0) return fail(ctx, AVK_E_ARG, "context labels: a run edge of 0");
+        if (i && sp->hp_edges[i] <= sp->hp_edges[i - 1]) return fail(ctx, AVK_E_ARG, "context labels: the run edges are not strictly ascending");
+    }
+    return 0;
+}
+static_assert(sizeof(avk_context_spec) == sizeof(avk::cx::CxSpec) && AVK_CONTEXT_PAD_MAX == AVK_CX_PAD_MAX && AVK_CONTEXT_GC_EDGES_MAX == AVK_CX_GC_EDGES_MAX &&
+                  AVK_CONTEXT_HP_EDGES_MAX == AVK_CX_HP_EDGES_MAX,
+              "avk_context_spec is avk::cx::CxSpec, field for field");
+
+int avk_context_label_name(const avk_context_spec *sp, uint32_t j, char *buf, size_t cap) {
+    if (!sp || !buf || !cap) return fail(nullptr, AVK_E_ARG, "context label name: spec or buffer missing");
+    if (context_spec_check(nullptr, sp)) return AVK_E_ARG;
+    const uint32_t n_gc = sp->n_gc_edges ? sp->n_gc_edges - 1u : 0u;
+    if (j >= n_gc + sp->n_hp_edges) return fail(nullptr, AVK_E_ARG, "context label name: the spec has %u labels", n_gc + sp->n_hp_edges);
+    int len;
+    if (j < n_gc) len = snprintf(buf, cap, "ctx_gc_%u_%u", sp->gc_edges[j], sp->gc_edges[j + 1]);
+    else if (j - n_gc + 1 == sp->n_hp_edges) len = snprintf(buf, cap, "ctx_hp_ge%u", sp->hp_edges[j - n_gc]);
+    else len = snprintf(buf, cap, "ctx_hp_%u_%u", sp->hp_edges[j - n_gc], sp->hp_edges[j - n_gc + 1] - 1u);
+    if (len < 0 || (size_t)len >= cap) return fail(nullptr, AVK_E_ARG, "context label name: %d bytes of room needed", len + 1);
+    return 0;
+}
+
 int avk_strata_upload(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs, const uint64_t *tree_off, const uint32_t *start, const uint32_t *end_max, avk_strata **out) {
+    return avk_strata_upload_context(ctx, n_labels, n_contigs, tree_off, start, end_max, nullptr, out);
+}
+
+int avk_strata_upload_context(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs, const uint64_t *tree_off, const uint32_t *start, const uint32_t *end_max,
+                              const avk_context_spec *spec, avk_strata **out) {
     if (!out) return fail(ctx, AVK_E_ARG, "strata: out missing");
     *out = nullptr;
     {
-        const int rc = strata_check(ctx, n_labels, n_contigs, tree_off, start, end_max);
+        int rc = strata_check(ctx, n_labels, n_contigs, tree_off, start, end_max);
+        if (!rc && spec) rc = context_spec_check(ctx, spec);
+        if (!rc && spec && !n_contigs) rc = fail(ctx, AVK_E_ARG, "context labels: n_contigs missing");
         if (rc) return rc;
     }
     if (!ctx) return fail(ctx, AVK_E_ARG, "strata: context missing");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n_trees = (uint64_t)n_labels * n_contigs, first = n_trees ? tree_off[0] : 0, total = n_trees ? tree_off[n_trees] : 0;
     avk_strata *st = new avk_strata();
-    st->ctx = ctx, st->n_labels = n_labels, st->n_contigs = n_contigs, st->n_intervals = total - first;
+    st->ctx = ctx, st->n_bed_labels = n_labels, st->n_labels = n_labels, st->n_contigs = n_contigs, st->n_intervals = total - first;
+    if (spec) { /* (a family without edges does not exist: its pad and edges are not kept) */
+        if (spec->n_gc_edges) st->spec.gc_pad = spec->gc_pad, st->spec.n_gc_edges = spec->n_gc_edges, memcpy(st->spec.gc_edges, spec->gc_edges, sizeof(uint32_t) * spec->n_gc_edges);
+        if (spec->n_hp_edges) st->spec.hp_pad = spec->hp_pad, st->spec.n_hp_edges = spec->n_hp_edges, memcpy(st->spec.hp_edges, spec->hp_edges, sizeof(uint32_t) * spec->n_hp_edges);
+        st->n_ctx_labels = avk::cx::cx_n_labels(st->spec), st->n_labels = n_labels + st->n_ctx_labels;
+    }
     int rc = dev_alloc(ctx, &st->d_tree_off, (size_t)n_trees + 1);
     if (!rc) rc = dev_alloc(ctx, &st->d_start, (size_t)total);
     if (!rc) rc = dev_alloc(ctx, &st->d_end_max, (size_t)total);
@@ -3754,6 +3805,7 @@ void avk_strata_free(avk_ctx *ctx, avk_strata *st) {
     delete st;
 }
 uint32_t avk_strata_n_labels(const avk_strata *st) { return st ? st->n_labels : 0; }
+uint32_t avk_strata_n_context_labels(const avk_strata *st) { return st ? st->n_ctx_labels : 0; }
 
 /* the lists of a resident batch in pool buffers, on the context's stream; the number of entries is read back (the resident forms size the index array with it) */
 struct StrataLists {
@@ -3786,6 +3838,11 @@ static int strata_lists_make(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *
 }
 static int strata_handle_check(avk_ctx *ctx, const avk_strata *st) {
     if (st->ctx != ctx) return fail(ctx, AVK_E_ARG, "strata: the handle was uploaded to another context");
+    if (st->n_ctx_labels) { /* the context kernel reads the reference as it is at launch time */
+        if (!ctx->d_ref || !ctx->d_ref2b || !ctx->d_refexc || !ctx->d_contig_tab) return fail(ctx, AVK_E_ARG, "context labels: avk_ref_upload has not been called");
+        if (ctx->contig_len.size() != st->n_contigs)
+            return fail(ctx, AVK_E_ARG, "context labels: the reference has %llu contigs, the handle %u", (unsigned long long)ctx->contig_len.size(), st->n_contigs);
+    }
     return 0;
 }
 

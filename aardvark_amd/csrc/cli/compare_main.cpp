@@ -38,7 +38,9 @@ void usage() {
             "  [--truth-sample S] [--query-sample S] [--compare-label L] [--strat-lists device|host] [--min-variant-gap 50] [--disable-variant-trimming]\n"
             "  [--reference-case upper|raw]  (default upper: soft-masked reference bases are compared as upper case)\n"
             "  [--max-branch-factor 50] [--enable-exact-shortcut] [--enable-haplotype-metrics] [--enable-weighted-haplotype-metrics]\n"
-            "  [--enable-record-basepair-metrics] [-s STRAT.tsv] [--output-debug DIR] [--skip N] [--take N] [--device 0 | --devices 0,1,..] [--batch-regions 4000000] [--batch-form packed|wide]\n");
+            "  [--enable-record-basepair-metrics] [-s STRAT.tsv] [--output-debug DIR] [--skip N] [--take N] [--device 0 | --devices 0,1,..] [--batch-regions 4000000] [--batch-form packed|wide]\n"
+            "  [--context-strata gc|hp|gc,hp]  (GC-content bins and homopolymer classes as further region labels, made on the GPU from the reference alone; with or without -s;\n"
+            "   packed feed and --strat-lists device only)  [--context-gc-edges 0,15,..,101] [--context-gc-pad 50] [--context-hp-edges 4,7,12,21] [--context-hp-pad 5]\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -83,6 +85,24 @@ int main(int argc, char **argv) {
     int device = 0;
     std::vector<int> devices; /* --devices: the contexts that share the region batches (the first one is `device`) */
     bool batch_given = false, want_packed = true;
+    /* --context-strata: the families asked for, and the tool's default edges and pads (overridden by --context-gc-edges / --context-hp-edges / --context-*-pad) */
+    bool cx_gc = false, cx_hp = false, cx_given = false, cx_override = false;
+    std::vector<uint32_t> cx_gc_edges = {0, 15, 20, 25, 30, 55, 60, 65, 70, 75, 80, 85, 101}, cx_hp_edges = {4, 7, 12, 21};
+    uint32_t cx_gc_pad = 50, cx_hp_pad = 5;
+    auto number_list = [](const std::string &opt, const std::string &list) {
+        std::vector<uint32_t> out;
+        for (size_t b = 0; b <= list.size();) {
+            const size_t e = list.find(',', b);
+            const std::string item = list.substr(b, e == std::string::npos ? std::string::npos : e - b);
+            char *end = nullptr;
+            const unsigned long long x = strtoull(item.c_str(), &end, 10);
+            if (item.empty() || *end || x > 0xFFFFFFFFull) die(64, ("invalid value for " + opt).c_str(), list.c_str());
+            out.push_back((uint32_t)x);
+            if (e == std::string::npos) break;
+            b = e + 1;
+        }
+        return out;
+    };
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> const char * {
@@ -141,6 +161,14 @@ int main(int argc, char **argv) {
             if (strat_lists != "device" && strat_lists != "host") die(64, "--strat-lists takes device or host", strat_lists.c_str());
         }
         else if (a == "--output-debug") debug_dir = val();
+        else if (a == "--context-strata") {
+            const std::string v = val();
+            if (v != "gc" && v != "hp" && v != "gc,hp" && v != "hp,gc") die(64, "--context-strata takes gc, hp or gc,hp", v.c_str());
+            cx_given = true, cx_gc = v.find("gc") != std::string::npos, cx_hp = v.find("hp") != std::string::npos;
+        } else if (a == "--context-gc-edges") cx_gc_edges = number_list(a, val()), cx_override = true;
+        else if (a == "--context-hp-edges") cx_hp_edges = number_list(a, val()), cx_override = true;
+        else if (a == "--context-gc-pad") cx_gc_pad = number_list(a, val())[0], cx_override = true;
+        else if (a == "--context-hp-pad") cx_hp_pad = number_list(a, val())[0], cx_override = true;
         else if (a == "-h" || a == "--help") {
             usage();
             return 0;
@@ -153,6 +181,29 @@ int main(int argc, char **argv) {
     if (gap == 0) die(78, "--min-variant-gap must be >0", "");
     if (branch == 0 || branch > 0xFFFFFFFFull) die(78, "--max-branch-factor must be >0", "");
     if (batch_regions == 0) batch_regions = 1;
+    /* The context labels exist on one route only: the packed (or escaped) feed with the lists made on the device.  Everything else is refused here, by name:
+     * there is no host route for the rule to fall back to. */
+    avk_context_spec cx_spec;
+    memset(&cx_spec, 0, sizeof(cx_spec));
+    uint32_t n_ctx_labels = 0;
+    if (cx_override && !cx_given) die(64, "--context-gc-edges, --context-hp-edges, --context-gc-pad and --context-hp-pad need --context-strata", "");
+    if (cx_given) {
+        if (strat_lists == "host") die(64, "--context-strata needs the labels listed on the GPU: it cannot be combined with --strat-lists host", "");
+        if (!want_packed) die(64, "--context-strata needs the packed feed: it cannot be combined with --batch-form wide", "");
+        if (!debug_dir.empty()) die(64, "--context-strata cannot be combined with --output-debug (the debug run solves the wide feed)", "");
+        if ((cx_gc && cx_gc_edges.size() > AVK_CONTEXT_GC_EDGES_MAX) || (cx_hp && cx_hp_edges.size() > AVK_CONTEXT_HP_EDGES_MAX)) die(64, "--context-strata: too many edges", "");
+        if (cx_gc) {
+            cx_spec.gc_pad = cx_gc_pad, cx_spec.n_gc_edges = (uint32_t)cx_gc_edges.size();
+            for (size_t k = 0; k < cx_gc_edges.size(); ++k) cx_spec.gc_edges[k] = cx_gc_edges[k];
+        }
+        if (cx_hp) {
+            cx_spec.hp_pad = cx_hp_pad, cx_spec.n_hp_edges = (uint32_t)cx_hp_edges.size();
+            for (size_t k = 0; k < cx_hp_edges.size(); ++k) cx_spec.hp_edges[k] = cx_hp_edges[k];
+        }
+        char name[64];
+        if (avk_context_label_name(&cx_spec, 0, name, sizeof(name))) die(64, "--context-strata", avk_last_error(nullptr)); /* (the library's own check of the spec) */
+        n_ctx_labels = (cx_spec.n_gc_edges ? cx_spec.n_gc_edges - 1 : 0) + cx_spec.n_hp_edges;
+    }
     if (!devices.empty()) device = devices[0];
     if (mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create output folder", out_dir.c_str());
     if (!debug_dir.empty() && mkdir(debug_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create debug folder", debug_dir.c_str());
@@ -238,7 +289,7 @@ int main(int argc, char **argv) {
 
     avf_strat *strat = nullptr;
     if (!strat_tsv.empty() && avf_strat_load(strat_tsv.c_str(), &strat)) die(74, "Error while loading stratifications", avf_last_error());
-    const uint32_t n_labels = avf_strat_n_labels(strat);
+    const uint32_t n_bed_labels = avf_strat_n_labels(strat), n_labels = n_bed_labels + n_ctx_labels; /* the sets' labels, then the context labels */
 
     /* the reference goes to the GPU (upload + 2-bit packing) while the regions are walked */
     t0 = std::chrono::steady_clock::now();
@@ -286,6 +337,7 @@ int main(int argc, char **argv) {
         if (rc_pack < 0) die(70, "cannot pack the region batch", avf_last_error());
         packed = rc_pack == 0;
     }
+    if (cx_given && !packed) die(70, "--context-strata needs the packed feed, and this call set does not fit the packed form even with escapes", "");
     const bool escaped = packed && (esc_all.n_esc_regions || esc_all.n_esc_slots || esc_all.n_esc_calls);
     /* regions [first + at, +n): as a batch in the chosen form; `out` is indexed by the feed's call arrays either way */
     auto out_for = [](avk_result_batch out, uint64_t v_first) { /* a packed part's results are indexed from its first call */
@@ -363,18 +415,20 @@ int main(int argc, char **argv) {
     std::vector<uint32_t> sx_start, sx_end_max;
     const uint32_t sx_contigs = avf_genome_n_contigs(genome);
     auto strata_upload = [&](avk_ctx *c, avk_strata **sets) -> int {
-        return avk_strata_upload(c, n_labels, sx_contigs, sx_tree_off.data(), sx_start.data(), sx_end_max.data(), sets);
+        return avk_strata_upload_context(c, n_bed_labels, sx_contigs, sx_tree_off.data(), sx_start.data(), sx_end_max.data(), cx_given ? &cx_spec : nullptr, sets);
     };
     avk_strata *strata = nullptr;
     if (strata_route) {
-        sx_tree_off.assign((size_t)n_labels * sx_contigs + 1, 0);
+        sx_tree_off.assign((size_t)n_bed_labels * sx_contigs + 1, 0);
         std::string why;
-        if (avf_strat_export(strat, genome, sx_tree_off.data(), nullptr, nullptr)) why = std::string("cannot export the stratification sets: ") + avf_last_error();
-        if (why.empty()) {
+        if (!n_bed_labels) sx_start.assign(1, 0), sx_end_max.assign(1, 0); /* (context labels alone: no sets to export) */
+        else if (avf_strat_export(strat, genome, sx_tree_off.data(), nullptr, nullptr)) why = std::string("cannot export the stratification sets: ") + avf_last_error();
+        if (why.empty() && n_bed_labels) {
             sx_start.assign(sx_tree_off.back() + 1, 0), sx_end_max.assign(sx_tree_off.back() + 1, 0);
             if (avf_strat_export(strat, genome, sx_tree_off.data(), sx_start.data(), sx_end_max.data())) why = std::string("cannot export the stratification sets: ") + avf_last_error();
         }
         if (why.empty() && strata_upload(ctx, &strata)) why = std::string("cannot upload the stratification sets: ") + avk_last_error(ctx);
+        if (!why.empty() && cx_given) die(70, "--context-strata", why.c_str()); /* (no host route makes these labels) */
         if (!why.empty()) {
             fprintf(stderr, "Warning: %s; the region labels are listed on the host instead (--strat-lists host).\n", why.c_str());
             strata_route = false;
@@ -384,9 +438,12 @@ int main(int argc, char **argv) {
     if (verbosity && compact_labels) {
         if (strata_route)
             fprintf(stderr, "Region labels: listed on the GPU (--strat-lists device, avk_compare_packed_strata): %llu intervals of %u labels uploaded once per context.\n",
-                    (unsigned long long)sx_tree_off.back(), n_labels);
+                    (unsigned long long)sx_tree_off.back(), n_bed_labels);
         else fprintf(stderr, "Region labels: listed on the host (--strat-lists host, avf_strat_batch_labels) and copied with every batch.\n");
     }
+    if (verbosity && cx_given)
+        fprintf(stderr, "Context labels: %u (%u GC bins with pad %u, %u homopolymer classes with pad %u), made on the GPU from the reference (--context-strata, avk_strata_upload_context).\n",
+                n_ctx_labels, cx_spec.n_gc_edges ? cx_spec.n_gc_edges - 1 : 0, cx_spec.gc_pad, cx_spec.n_hp_edges, cx_spec.hp_pad);
     if (verbosity && n_labels)
         fprintf(stderr, "Stratified sums: %s.\n", compact_labels ? "from the compact results on the GPU (avk_compare_packed_labels), no per-region metric blocks"
                                                      : device_labels ? "from per-region metric blocks on the GPU (avk_label_tallies)"
@@ -568,7 +625,12 @@ int main(int argc, char **argv) {
                 (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels && !compact_labels ? 1 : 0);
             }
             avk_strata *my_sets = w > 0 ? nullptr : strata;
-            if (w > 0 && strata_route && strata_upload(my, &my_sets)) { /* this worker lists its batches' labels on the host */
+            if (w > 0 && strata_route && cx_given && strata_upload(my, &my_sets)) { /* (context labels: no host route) */
+                worker_err[w] = std::string("--context-strata: cannot upload the stratification sets: ") + avk_last_error(my);
+                avk_ctx_destroy(my);
+                return;
+            }
+            if (w > 0 && strata_route && !cx_given && strata_upload(my, &my_sets)) { /* this worker lists its batches' labels on the host */
                 std::lock_guard<std::mutex> lock(log_mutex);
                 fprintf(stderr, "Warning: cannot upload the stratification sets to context %zu: %s; its region labels are listed on the host.\n", w, avk_last_error(my));
                 my_sets = nullptr;
@@ -743,7 +805,19 @@ int main(int argc, char **argv) {
     t0 = std::chrono::steady_clock::now();
     if (avf_table_close(region_table) || avf_table_close(sequence_table)) die(74, "Error while saving the debug tables", avf_last_error());
     const std::string summary = out_dir + "/summary.tsv";
-    if (avf_write_summary_stratified(summary.c_str(), label.c_str(), total.data(), strat, strat_total.data(), mask))
+    if (cx_given) { /* the sets' blocks, then the derived blocks, in label order */
+        std::vector<std::string> label_names;
+        for (uint32_t l = 0; l < n_bed_labels; ++l) label_names.push_back(avf_strat_label(strat, l));
+        for (uint32_t j = 0; j < n_ctx_labels; ++j) {
+            char name[64];
+            if (avk_context_label_name(&cx_spec, j, name, sizeof(name))) die(70, "context label name", avk_last_error(nullptr));
+            label_names.push_back(name);
+        }
+        std::vector<const char *> name_ptrs;
+        for (const std::string &n : label_names) name_ptrs.push_back(n.c_str());
+        if (avf_write_summary_named(summary.c_str(), label.c_str(), total.data(), n_labels, name_ptrs.data(), strat_total.data(), mask))
+            die(74, "Error while saving summary file", avf_last_error());
+    } else if (avf_write_summary_stratified(summary.c_str(), label.c_str(), total.data(), strat, strat_total.data(), mask))
         die(74, "Error while saving summary file", avf_last_error());
     /* the annotated VCFs (VariantCategorizer): truth.vcf.gz and query.vcf.gz with their .tbi */
     std::string command;

@@ -1898,6 +1898,17 @@ void avf_feed_free(avf_feed *f) { delete f; }
 int avf_write_summary_stratified(const char *path, const char *compare_label, const uint64_t *tally, const avf_strat *strat, const uint64_t *strat_tallies,
                                  uint32_t metrics_mask) {
     if (!path || !tally || (strat && !strat_tallies)) return fail(AVK_E_ARG, "null argument");
+    std::vector<const char *> names;
+    if (strat)
+        for (uint32_t l = 0; l < avf_strat_n_labels(strat); ++l) names.push_back(avf_strat_label(strat, l));
+    return avf_write_summary_named(path, compare_label, tally, (uint32_t)names.size(), names.data(), strat_tallies, metrics_mask);
+}
+
+int avf_write_summary_named(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names,
+                            const uint64_t *strat_tallies, uint32_t metrics_mask) {
+    if (!path || !tally || (n_labels && (!strat_tallies || !label_names))) return fail(AVK_E_ARG, "null argument");
+    for (uint32_t l = 0; l < n_labels; ++l)
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
     const std::string p(path);
     const char delim = p.size() >= 4 && p.compare(p.size() - 4, 4, ".csv") == 0 ? ',' : '\t';
     FILE *fp = fopen(path, "w");
@@ -1975,11 +1986,10 @@ int avf_write_summary_stratified(const char *path, const char *compare_label, co
         }
     };
     write_group(tally); /* the ALL group first (summary.rs:196-201) */
-    if (strat)
-        for (uint32_t l = 0; l < avf_strat_n_labels(strat); ++l) {
-            region_label = csv_field(avf_strat_label(strat, l), delim);
-            write_group(strat_tallies + (size_t)l * AVK_TALLY_LEN);
-        }
+    for (uint32_t l = 0; l < n_labels; ++l) {
+        region_label = csv_field(label_names[l], delim);
+        write_group(strat_tallies + (size_t)l * AVK_TALLY_LEN);
+    }
     const bool bad = ferror(fp) != 0;
     if (fclose(fp) != 0 || bad) return fail(AVK_E_ARG, "write error on %s", path);
     return 0;

@@ -71,6 +71,7 @@ def load_library():
     lib.avf_strat_export.argtypes = [vp, vp, C.POINTER(C.c_uint64), u32p, u32p]
     lib.avf_strat_batch_labels.argtypes = [vp, vp, C.POINTER(AvkRegionBatch), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), u32p]
     lib.avf_write_summary_stratified.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), vp, C.POINTER(C.c_uint64), C.c_uint32]
+    lib.avf_write_summary_named.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32]
     lib.avf_region_summary_open.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(vp)]
     lib.avf_region_summary_rows.argtypes = [vp, vp, C.POINTER(AvkRegionBatch), C.c_uint64, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     lib.avf_region_sequences_open.argtypes = [C.c_char_p, C.POINTER(vp)]
@@ -397,6 +398,16 @@ def write_summary_stratified(path, tally, strat, strat_tallies, compare_label="c
     st = np.ascontiguousarray(strat_tallies, dtype=np.uint64).reshape(-1)
     _check(lib, lib.avf_write_summary_stratified(os.fsencode(path), compare_label.encode(), t.ctypes.data_as(C.POINTER(C.c_uint64)), strat.handle,
                                                  st.ctypes.data_as(C.POINTER(C.c_uint64)), metrics))
+
+
+def write_summary_named(path, tally, names, strat_tallies, compare_label="compare", metrics=METRIC_GT | METRIC_BASEPAIR):
+    """avf_write_summary_named: write_summary_stratified with the labels' names as a list (the sets' labels, then e.g. ContextSpec.names())"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    t = np.ascontiguousarray(tally, dtype=np.uint64)
+    st = np.ascontiguousarray(strat_tallies, dtype=np.uint64).reshape(-1)
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names]) if names else None
+    _check(lib, lib.avf_write_summary_named(os.fsencode(path), compare_label.encode(), t.ctypes.data_as(u64p), len(names), arr, st.ctypes.data_as(u64p), metrics))
 
 
 def write_debug_tables(summary_path, sequences_path, genome, batch, result, metrics=METRIC_GT | METRIC_BASEPAIR):

@@ -600,6 +600,39 @@ int  avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, cons
 int  avk_compare_packed_submit_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata,
                                       const avk_compare_config *cfg, avk_result_batch *out, uint64_t *label_tallies, avk_ticket **ticket);
 
+/* SEQUENCE-CONTEXT labels (avk_context.inl): labels that are functions of the reference sequence alone, made by kernel from the reference avk_ref_upload left in
+ * HBM — a stratified job needs no BED set for them.  The rule is this project's own (the reference has no such labels):
+ *   window   a region's query is the one the interval sets get, [first, last] on its contig; a family's window is [first - pad, last + 1 + pad), clamped to the
+ *            contig.  A region without a query (see avk_strata_upload) has no context label.
+ *   bases    a base counts when its byte is an upper-case A, C, G or T; every other byte is left out of every count and ends a run.
+ *   GC       n_gc_edges percent values in 0..101, strictly ascending, make n_gc_edges - 1 labels.  g = C or G bases of the window, a = counted bases: label i
+ *            is set when a > 0 and gc_edges[i] * a <= 100 * g < gc_edges[i + 1] * a (integers).
+ *   runs     n_hp_edges run lengths >= 1, strictly ascending, make n_hp_edges labels.  L = the longest run of one counted base inside the window (cut at its
+ *            edges): label i is set when hp_edges[i] <= L < hp_edges[i + 1], the last one when L >= hp_edges[n_hp_edges - 1].
+ * A family with no edges does not exist; a region gets at most one label per family.  In a handle the context labels follow the BED labels: context label j
+ * (GC labels first, then the run labels) is label n_bed + j of every list, mask and sum. */
+#define AVK_CONTEXT_PAD_MAX 1024
+#define AVK_CONTEXT_GC_EDGES_MAX 17
+#define AVK_CONTEXT_HP_EDGES_MAX 16
+typedef struct avk_context_spec {
+    uint32_t gc_pad, n_gc_edges, gc_edges[AVK_CONTEXT_GC_EDGES_MAX];
+    uint32_t hp_pad, n_hp_edges, hp_edges[AVK_CONTEXT_HP_EDGES_MAX];
+} avk_context_spec;
+/* avk_strata_upload plus the context labels of `spec` behind its n_labels BED labels.  spec == NULL: avk_strata_upload.  n_labels == 0 with a spec: a handle of
+ * context labels only (n_contigs is still required: it must be the uploaded reference's).  AVK_E_ARG, with nothing allocated (no device needed: ctx may be NULL):
+ * edges that are not strictly ascending, a GC edge above 101, a run edge of 0, n_gc_edges == 1 or above 17, n_hp_edges above 16, a pad above 1024, both families
+ * empty.  Every entry point that takes a handle takes this one; each refuses it with AVK_E_ARG, before anything is queued and with the caller's sums untouched,
+ * when the context has no reference or its reference has another number of contigs than the handle.  The reference is read where the kernel is queued, on the
+ * batch's own stream for a submitted batch: as for the solver kernels, avk_ref_upload must not be called while tickets are in flight.  A handle without context
+ * labels queues exactly the launches avk_strata_upload's does. */
+int  avk_strata_upload_context(avk_ctx *ctx, uint32_t n_labels, uint32_t n_contigs, const uint64_t *tree_off, const uint32_t *start, const uint32_t *end_max,
+                               const avk_context_spec *spec, avk_strata **out);
+/* the number of context labels of a handle (avk_strata_n_labels is the total) */
+uint32_t avk_strata_n_context_labels(const avk_strata *strata);
+/* host only: the stable name of context label j of a spec into buf (NUL-terminated, cut at cap): ctx_gc_<lo>_<hi> (percent, hi exclusive), ctx_hp_<lo>_<hi - 1>
+ * (run lengths, inclusive), ctx_hp_ge<lo> for the open-ended last one.  AVK_E_ARG: an invalid spec, j beyond its labels, no room. */
+int  avk_context_label_name(const avk_context_spec *spec, uint32_t j, char *buf, size_t cap);
+
 /* Merge path (src/merge_solver.rs:137-143): for pair p, optimize_sequences(set a, set b) and
  * report all_opt_haps[0].is_exact_match().  Pair p compares variant ranges
  * [t_off,t_cnt) vs [q_off,q_cnt) of region p of `batch` exactly like a CompareRegion. */

@@ -151,6 +151,11 @@ void avf_strat_free(avf_strat *s);
  * avf_strat_n_labels(s) blocks of AVK_TALLY_LEN words, block l = the sum over the regions label l contains */
 int avf_write_summary_stratified(const char *path, const char *compare_label, const uint64_t *tally, const avf_strat *s, const uint64_t *strat_tallies,
                                  uint32_t metrics_mask);
+/* the same with the labels' names given as an array — a job whose labels do not all come from BED sets (the sequence-context labels of
+ * avk_strata_upload_context follow the sets' labels): strat_tallies holds n_labels blocks of AVK_TALLY_LEN words, block l is written under label_names[l].
+ * avf_write_summary_stratified is this function with the names of the sets. */
+int avf_write_summary_named(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names,
+                            const uint64_t *strat_tallies, uint32_t metrics_mask);
 
 /* One of the two annotated VCFs of `compare` (VariantCategorizer, src/writers/variant_categorizer.rs:41-230; source 0 =
  * truth.vcf.gz, 1 = query.vcf.gz): the meta lines of input_vcf, the aardvark_version / aardvark_command lines and the
