@@ -33,6 +33,7 @@
 #include "avk_pack_chunks.h"
 #include "avk_counters.h"
 #include "avk_step_plan.h"
+#include "avk_step_geometry.h"
 #include "avk_solver.inl"
 #include "avk_lane.inl"
 #include "avk_quad.inl"
@@ -383,7 +384,7 @@ struct avk_ctx {
     int64_t solo_min_variants = 5; /* regions with at least this many variants go to solo waves (0 = no solo waves) */
     int64_t solo_blocks_max = 128;
     int64_t timing_events = 1; /* record the events avk_last_kernel_ms / avk_last_solver_ms read (three per call) */
-    bool lds_attr_set = false;
+    bool kernel_attrs_set = false; /* ensure_kernel_attrs has run */
     int64_t static_pct = AVK_STATIC_PCT; /* share of a launch's work list dealt statically; the rest is claimed */
     int64_t claim = AVK_CLAIM;           /* regions per claim */
     int64_t class_c_below = 16384; /* a batch with lane launches and at most this many regions outside them plans those regions as class C: the wide kernel (0: no such rule) */
@@ -467,9 +468,7 @@ struct avk_ctx {
     int64_t wide_blocks = 512;                        /* most one-wave workgroups of its class C launch */
     int64_t wide_lane_handbacks = 1;                  /* what the one- and two-call lane classes hand back goes through avk_wide.inl too, ahead of the LDS launch */
     int64_t wide_lazy_blocks = 512;                   /* one-wave workgroups of its launch for what the three-call lane class hands back (a short list, its length known on the device only) */
-    bool wide_attr_set = false;
     uint64_t last_wide_solved = 0;
-    bool lane_attr_set = false;
     uint64_t last_lane_solved = 0;
     int last_one_shot = 0; /* the last avk_compare_batch / avk_optimize_pairs_batch packed its batch on the device */
     int n_cus = 0;
@@ -483,11 +482,9 @@ struct avk_ctx {
     hipEvent_t ev_lane = nullptr; /* after the lane-kernel launches of a step */
     bool ev_lane_valid = false;
     hipStream_t lane_stream = nullptr, lane_stream2 = nullptr; /* the lane-kernel launches run beside the wave-per-region launches: two-call classes / one-call classes */
-    hipEvent_t ev_lane_fork = nullptr, ev_lane_join = nullptr, ev_lane_join2 = nullptr;
+    hipEvent_t ev_lane_fork = nullptr;
     hipStream_t lane_stream3 = nullptr; /* the three-call class: long tiles, few of them, beside everything else */
-    hipEvent_t ev_lane_join3 = nullptr, ev_lane_done = nullptr;
     hipStream_t lane_stream4 = nullptr; /* the head launches of the two-call classes (long: beside the rest of their class, not ahead of it) */
-    hipEvent_t ev_lane_join4 = nullptr, ev_lane_early = nullptr;
     hipEvent_t ev_hb[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; /* ends of the lane classes' head launches (handback_chains) */
     hipEvent_t ev_tl[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; /* AVK_TIMING only: marks of a boundary call on the context's stream (first copy, last copy, work order, writers, results)
                                                                                      and, [5], behind the region pass on whichever stream it ran */
@@ -497,15 +494,16 @@ struct avk_ctx {
     hipStream_t side_stream = nullptr, side_stream2 = nullptr; /* solo launches (LDS, HBM): one stream each, they run side by side */
     hipStream_t spare_stream[16] = {nullptr}; /* never used: see avk_ctx_create */
     int n_placeholders = 0;                   /* how many of them avk_ctx_create made (and destroyed again) */
-    hipStream_t wide_stream = nullptr; /* the class C records that are not for the wide kernel (run_internal) */
-    /* the step's plan (avk_step_plan.h): which stream each launch chain of run_internal is queued on */
+    hipStream_t wide_stream = nullptr; /* the class C records that are not for the wide kernel (the step, avk_step.inl) */
+    /* the step's plan (avk_step_plan.h): which stream each launch chain of the step is queued on */
     int64_t step_queues = 0;       /* option: 0 by the process's hardware queues (step_folded_auto), 4 the folded plan, 8 a stream per chain */
     bool step_folded_auto = false; /* GPU_MAX_HW_QUEUES below AVK_STEP_QUEUES_WIDE when the context was made */
     hipStream_t fold_stream[AVK_STEP_SLOTS_FOLDED - 1] = {nullptr, nullptr, nullptr}; /* the folded plan's streams beside the caller's */
-    bool last_step_chains = false; /* the last step ran with hand-back chains (it recorded no ev_lane_done) */
+    bool last_step_chains = false; /* the last step ran with hand-back chains (it recorded no AVK_END_DONE) */
     std::thread reaper; /* releases the buffers of the last large batch behind the caller (avk_batch_free) */
     std::mutex reaper_mutex;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_wide = nullptr;
+    hipEvent_t ev_fork = nullptr;
+    hipEvent_t ev_end[AVK_N_ENDS] = {nullptr}; /* the ends of the step's chains, by AvkStepEnd (avk_step_plan.h) */
     bool ev_valid = false;
     uint64_t last_tiers[5] = {0, 0, 0, 0, 0};
     uint64_t last_phase[16] = {0};
@@ -770,14 +768,10 @@ int avk_ctx_create(int device_id, avk_ctx **out) {
     hipStream_t *all[7] = {&ctx->side_stream, &ctx->side_stream2, &ctx->wide_stream, &ctx->lane_stream, &ctx->lane_stream2, &ctx->lane_stream3, &ctx->lane_stream4};
     for (hipStream_t *st : all) /* (a letter the order left out) */
         if (ok && !*st) ok = hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_high) == hipSuccess;
+    for (hipEvent_t &ev : ctx->ev_end)
+        if (ok) ok = hipEventCreateWithFlags(&ev, evf) == hipSuccess;
     if (!ok ||
-        hipEventCreateWithFlags(&ctx->ev_join2, evf) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_wide, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_lane_join2, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_lane_join3, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_lane_done, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_lane_join4, evf) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_hb[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_hb[1], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_hb[2], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_hb[3], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_hb[4], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_hb[5], hipEventDisableTiming) != hipSuccess ||
@@ -787,10 +781,7 @@ int avk_ctx_create(int device_id, avk_ctx **out) {
         hipEventCreateWithFlags(&ctx->ev_copy_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_copy_mid, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_copy_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_lane_early, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_lane_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_lane_join, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_join, evf) != hipSuccess) {
+        hipEventCreateWithFlags(&ctx->ev_lane_fork, hipEventDisableTiming) != hipSuccess) {
         avk_ctx_destroy(ctx);
         return fail(nullptr, AVK_E_HIP, "cannot create the side streams / events of the context");
     }
@@ -838,19 +829,13 @@ void avk_ctx_destroy(avk_ctx *ctx) {
     if (ctx->evk1) (void)hipEventDestroy(ctx->evk1);
     if (ctx->ev_lane) (void)hipEventDestroy(ctx->ev_lane);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_wide) (void)hipEventDestroy(ctx->ev_wide);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-    if (ctx->ev_join2) (void)hipEventDestroy(ctx->ev_join2);
     if (ctx->d_pair_tab) (void)hipFree(ctx->d_pair_tab);
     if (ctx->d_pair_aux) (void)hipFree(ctx->d_pair_aux);
     if (ctx->ev_lane_fork) (void)hipEventDestroy(ctx->ev_lane_fork);
-    if (ctx->ev_lane_join) (void)hipEventDestroy(ctx->ev_lane_join);
-    if (ctx->ev_lane_join2) (void)hipEventDestroy(ctx->ev_lane_join2);
     if (ctx->lane_stream) (void)hipStreamDestroy(ctx->lane_stream);
     if (ctx->lane_stream2) (void)hipStreamDestroy(ctx->lane_stream2);
-    if (ctx->ev_lane_join3) (void)hipEventDestroy(ctx->ev_lane_join3);
-    if (ctx->ev_lane_done) (void)hipEventDestroy(ctx->ev_lane_done);
-    if (ctx->ev_lane_join4) (void)hipEventDestroy(ctx->ev_lane_join4);
+    for (hipEvent_t e : ctx->ev_end)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_hb)
         if (e) (void)hipEventDestroy(e);
     if (ctx->ev_cp0) (void)hipEventDestroy(ctx->ev_cp0);
@@ -859,7 +844,6 @@ void avk_ctx_destroy(avk_ctx *ctx) {
     if (ctx->ev_copy_fork) (void)hipEventDestroy(ctx->ev_copy_fork);
     if (ctx->ev_copy_mid) (void)hipEventDestroy(ctx->ev_copy_mid);
     if (ctx->ev_copy_join) (void)hipEventDestroy(ctx->ev_copy_join);
-    if (ctx->ev_lane_early) (void)hipEventDestroy(ctx->ev_lane_early);
     if (ctx->lane_stream4) (void)hipStreamDestroy(ctx->lane_stream4);
     if (ctx->lane_stream3) (void)hipStreamDestroy(ctx->lane_stream3);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
@@ -1382,904 +1366,8 @@ void avk_batch_free(avk_ctx *ctx, avk_dev_batch *db) {
     delete db;
 }
 
-/* tile width of a lane launch (options lane_width_one / lane_width_two: 64, 32 or 16 records per wave at a time) */
-static uint32_t lane_width_log2(const avk_ctx *ctx, uint32_t maxv) {
-    const int64_t w = maxv > 2 ? ctx->lane_width_three : (maxv > 1 ? ctx->lane_width_two : ctx->lane_width_one);
-    return w <= 1 ? 0u : (w <= 2 ? 1u : (w <= 4 ? 2u : (w <= 8 ? 3u : (w <= 16 ? 4u : (w <= 32 ? 5u : 6u)))));
-}
-/* LDS bytes of a one-wave workgroup of the lane kernel (0: does not fit) and the grid that fills the machine: the per-lane arrays of
- * `width` lanes plus a tally of its own; as many workgroups per CU as the LDS and the wave slots hold */
-static uint32_t head_width_log2(const avk_ctx *ctx, uint32_t head_regions) {
-    int64_t w = ctx->lane_head_width;
-    if (ctx->lane_head_auto && w > 4) { /* lanes that diverge take turns: a head that cannot fill the machine's lane waves 16 wide is spread over more, narrower waves */
-        const int64_t fit = head_regions < 8192u ? 4 : (head_regions < 24576u ? 8 : 16);
-        if (fit < w) w = fit;
-    }
-    return w <= 1 ? 0u : (w <= 2 ? 1u : (w <= 4 ? 2u : (w <= 8 ? 3u : (w <= 16 ? 4u : (w <= 32 ? 5u : 6u)))));
-}
-/* which of the two kernels a lane launch runs: four lanes per region when the launch is narrow (option lane_quad) */
-static bool lane_launch_is_quad(const avk_ctx *ctx, const avk::lane::LaneArgs &la) { return ctx->lane_quad && la.lanes_log2 <= 4; }
-static size_t lane_launch_geometry(const avk_ctx *ctx, const avk::lane::LaneArgs &la, uint32_t *grid) {
-    const uint32_t rows = (1 + 2 * (la.nm - 1)) * (la.W + 1) + ((lane_launch_is_quad(ctx, la) ? 4 : 3) + 2 * la.pool) * ((2 * la.ed_max + 2 + 3) / 4) + la.qcap + (la.nm == 2 ? 4 : 8); /* lane_rows / quad_rows */
-    const size_t lds = (size_t)rows * (4u << la.lanes_log2) + 288 * 4;
-    uint32_t per_cu = (uint32_t)((160 * 1024) / lds);
-    if (per_cu < 1) return 0;
-    uint32_t cap = la.lanes_log2 < 4 ? 32u : (uint32_t)(ctx->lane_waves_per_cu > 0 ? ctx->lane_waves_per_cu : 12); /* very narrow tiles: every wave slot */
-    if (la.nm > 4 && ctx->lane_waves_three > 0) cap = (uint32_t)ctx->lane_waves_three; /* the three-call class: 17 KB per wave */
-    if (per_cu > cap) per_cu = cap;
-    const uint32_t claims = la.n_tiles * (64u >> la.lanes_log2);
-    uint32_t g = (uint32_t)ctx->n_cus * per_cu;
-    if (g > claims) g = claims;
-    *grid = g;
-    return lds;
-}
-/* a launch of a lane class: one lane per region, or four (lane_launch_is_quad) */
-/* done: an event that fires when THIS launch ends (bound to the launch's own completion signal: an event recorded behind the launch is a packet of its own in the
- * stream, and the next launch of the chain started 55-60 us later for it) */
-static void launch_lane_class(const avk_ctx *ctx, uint32_t grid, size_t lds, hipStream_t s, const AvkKernelArgs &f, const avk::lane::LaneArgs &la, hipEvent_t done = nullptr) {
-    if (lane_launch_is_quad(ctx, la)) {
-        if (lds * 8 > 160 * 1024) hipExtLaunchKernelGGL(avk_quad_kernel_wide_regs, dim3(grid), dim3(64), lds, s, nullptr, done, 0, f, la); /* fewer than eight workgroups per CU by LDS: registers to spare */
-        else hipExtLaunchKernelGGL(avk_quad_kernel, dim3(grid), dim3(64), lds, s, nullptr, done, 0, f, la);
-    }
-    else hipExtLaunchKernelGGL(avk_lane_kernel, dim3(grid), dim3(64), lds, s, nullptr, done, 0, f, la);
-}
-
-/* The table of avk_pairs.inl for this max_branch_factor, on `s`: sixteen probe regions through the lane kernel, outputs redirected into the table.
- * Words of d_pair_aux: [0, 768) probe records, [768, 784) probe reference, [784, 792) its exception bitmap (zeros), [792, 812) BASEPAIR offsets 0, 2, .. 32,
- * [812] tile counter, [813] overflow count, [816, 880) overflow list, [896, 896 + 2 * AVK_TALLY_STRIDE) a partial tally nobody reads. */
-static int ensure_pair_table(avk_ctx *ctx, uint32_t max_branch_factor, hipStream_t s) {
-    enum { AUX_WORDS = 896 + 2 * AVK_TALLY_STRIDE };
-    if (!ctx->d_pair_tab) {
-        AVK_HIP(ctx, hipMalloc((void **)&ctx->d_pair_tab, sizeof(avk::pairs::PairTable)));
-        AVK_HIP(ctx, hipMalloc((void **)&ctx->d_pair_aux, (size_t)AUX_WORDS * 4));
-        std::vector<uint32_t> aux(AUX_WORDS, 0);
-        avk::pairs::pair_probe_records(aux.data(), aux.data() + 768);
-        for (uint32_t k = 0; k <= avk::pairs::N_SIG; ++k) aux[792 + k] = 2 * k;
-        AVK_HIP(ctx, hipMemcpy(ctx->d_pair_aux, aux.data(), (size_t)AUX_WORDS * 4, hipMemcpyHostToDevice));
-        ctx->pair_tab_mbf = -1;
-    }
-    if (ctx->pair_tab_mbf == (int64_t)max_branch_factor) return AVK_E_OK;
-    AVK_HIP(ctx, hipMemsetAsync(ctx->d_pair_tab, 0xFF, sizeof(avk::pairs::PairTable), s));
-    AVK_HIP(ctx, hipMemsetAsync(ctx->d_pair_aux + 812, 0, (size_t)(AUX_WORDS - 812) * 4, s));
-    AvkKernelArgs f;
-    memset(&f, 0, sizeof(f));
-    f.ref_2bit = ctx->d_pair_aux + 768;
-    f.ref_exc = ctx->d_pair_aux + 784;
-    f.n_regions = avk::pairs::N_SIG;
-    f.max_branch_factor = max_branch_factor;
-    f.region_out = &ctx->d_pair_tab->region[0][0];
-    f.var_out = &ctx->d_pair_tab->var[0][0];
-    f.group_metrics = &ctx->d_pair_tab->gm[0][0];
-    f.bp_off = ctx->d_pair_aux + 792;
-    f.bp_out = &ctx->d_pair_tab->bp[0][0];
-    f.tally = (uint64_t *)(ctx->d_pair_aux + 896);
-    f.overflow_list = ctx->d_pair_aux + 816;
-    f.overflow_count = ctx->d_pair_aux + 813;
-    avk::lane::LaneArgs la;
-    memset(&la, 0, sizeof(la));
-    const AvkFastClass &cl = AVK_FAST_CLASS[0];
-    la.recs = ctx->d_pair_aux;
-    la.rec_words = AVK_FAST_WORDS_OF(1);
-    la.n_tiles = 1;
-    la.tile_counter = ctx->d_pair_aux + 812;
-    la.W = cl.W, la.nm = 2, la.ed_max = cl.ed_max, la.qcap = cl.qcap;
-    la.lanes_log2 = 6;
-    la.max_nodes = 250;
-    uint32_t grid = 0;
-    const size_t lds = lane_launch_geometry(ctx, la, &grid);
-    if (!ctx->lane_attr_set) {
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_lane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel_wide_regs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->lane_attr_set = true;
-    }
-    hipLaunchKernelGGL(avk_lane_kernel, dim3(1), dim3(64), lds, s, f, la);
-    AVK_HIP(ctx, hipGetLastError());
-    ctx->pair_tab_mbf = (int64_t)max_branch_factor;
-    return AVK_E_OK;
-}
-
-/* workgroups (x 4 waves x ws_bytes_per_wave of HBM) of the main HBM-tier launch of a batch that has lane launches.  Every wave of the grid needs a slice, and fresh device
- * memory is scrubbed when it is handed out (75 ms per GB): n_cus x 3 workgroups were 3 of the 4.8 GB a process's first whole-genome call waited 0.39 s for
- * (profiles/r05_first_solve.txt); the step does not notice the difference (profiles/r05_quad_sweeps.txt) */
-#define AVK_HBM_BLOCKS_BESIDE_LANES 192u
-static int run_internal(avk_ctx *ctx, const CallSpec &spec, avk_dev_batch *db, const avk_compare_config *cfg, void *tally_dev, uint32_t mode) {
-    if (!ctx || !db || !cfg) return AVK_E_ARG;
-    AVK_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t n = db->n_regions;
-    if (ctx->lds2_bytes_per_wave * 4 > 160 * 1024) return fail(ctx, AVK_E_ARG, "lds2_bytes_per_wave too large");
-    /* sequences: allocate the output arena on first use */
-    if (cfg->enable_sequences && !db->d_seq) {
-        int rc = db->dev_packed ? pool_alloc_t(ctx, db, &db->d_seq, (size_t)db->seq_total + 16) : dev_alloc(ctx, &db->d_seq, (size_t)db->seq_total + 16);
-        if (rc) return rc;
-    }
-    /* up to four launches, one per workspace tier; each consumes the overflow list of the one
-     * before it (its length is read on the device, so nothing comes back to the host in between) */
-    const bool use[4] = {ctx->lds_bytes_per_wave > 0, ctx->lds2_bytes_per_wave > 0, ctx->ws_bytes_per_wave > 0, ctx->big_ws_bytes > 0};
-    /* which tiers get a launch of their own: the large LDS slices normally only serve the solo launch (their
-     * overflow pass runs one workgroup per CU and measured slower than handing the overflow to the HBM tier,
-     * which runs twice the waves), and the big HBM slices are claimed in place by the tier-2 launch */
-    const bool launch[4] = {use[0], use[1] && (ctx->lds2_overflow_pass || !use[0]), use[2], use[3] && !use[2]};
-    int last = -1;
-    for (int t = 0; t < 4; ++t)
-        if (launch[t]) last = t;
-    if (last < 0) return fail(ctx, AVK_E_ARG, "every workspace tier is disabled");
-    /* The lane-per-region kernel takes the fast segments at the end of the work order (WorkPlan::fast_base); what it cannot finish it
-     * appends to the list the first HBM launch reads.  Without such a launch, with sequence output (the haplotype bytes are never
-     * materialised there) or with the exact-match shortcut the wave-per-region bulk launch covers those records itself. */
-
-    /* which classes go to the lanes was decided with the work order (plan_work_order, option lane_min_regions at upload time) */
-    const int lane_k = AVK_FAST_CLASSES;
-    const uint32_t n_lane_regions = db->plan.n_fast_total;
-    /* the lanes read the 2-bit reference only: with use_packed_reference off (a.ref_2bit == NULL) the wave-per-region kernels take every record */
-    const bool use_fast = ctx->lane_kernel && launch[0] && !launch[1] && launch[2] && !launch[3] && db->d_fast && n_lane_regions && !cfg->enable_sequences &&
-                          !cfg->enable_exact_shortcut && n && ctx->use_packed_reference && ctx->d_ref2b;
-    const uint32_t n_fast = use_fast ? n_lane_regions : 0u;
-    /* the wave-cooperative kernel of avk_wide.inl takes class C and what the three-call lane class hands back ahead of the HBM-tier launches (which get what it
-     * cannot take); like the lanes it reads the 2-bit reference and writes no sequences */
-    const bool use_wide = ctx->wide_kernel && launch[0] && !launch[1] && launch[2] && !launch[3] && !cfg->enable_sequences && !cfg->enable_exact_shortcut && n &&
-                          ctx->use_packed_reference && ctx->d_ref2b;
-    avk::wide::WideArgs wa;
-    wa.lds_words = (uint32_t)(ctx->wide_lds_bytes / 4);
-    wa.skip_static = 0;
-    if (use_wide && !ctx->wide_attr_set) {
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_wide_kernel_lazy, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        ctx->wide_attr_set = true;
-    }
-    if (db->dev_packed && !use_fast) { /* the wave-per-region launches take every record: write the ones the packer left for later */
-        const int rf = ensure_all_records(ctx, db, ctx->stream);
-        if (rf) return rf;
-    }
-    /* geometry */
-    const uint32_t waves_per_block = 4;
-    uint64_t want_waves = (uint64_t)ctx->n_cus * (uint64_t)ctx->waves_per_cu;
-    if (want_waves > n - n_fast) want_waves = n - n_fast;
-    uint32_t blocks = (uint32_t)((want_waves + waves_per_block - 1) / waves_per_block);
-    if (blocks == 0) blocks = 1;
-    /* the HBM launches: no more workgroups than can be resident (three per CU at the kernel's register count) — later ones would find
-     * the work list empty anyway, and every wave of the grid needs a slice of HBM (fresh device memory is scrubbed when it is handed
-     * out: 13 GB of workspaces cost 0.25 s at the first call of a process, 4 GB a third of that) */
-    uint32_t hbm_blocks = (uint32_t)ctx->n_cus * 3u;
-    if (use_fast && n - n_fast <= 16384 && hbm_blocks > AVK_HBM_BLOCKS_BESIDE_LANES) hbm_blocks = AVK_HBM_BLOCKS_BESIDE_LANES; /* lane launches that leave the other kernels a few thousand regions leave this tier a few dozen (a genome: 27) */
-    if (hbm_blocks > blocks) hbm_blocks = blocks;
-    /* the HBM solo launch runs beside the main stream's HBM launch: its (at most 64) workgroups have slices of their own, after the others */
-    uint32_t hbm_solo_max = (uint32_t)(ctx->hbm_solo_blocks > 0 ? ctx->hbm_solo_blocks : 128);
-    uint32_t hbm_early_max = (uint32_t)(ctx->hbm_early_blocks > 0 ? ctx->hbm_early_blocks : 64); /* workgroups of the launch behind the three-call lane class (its hand-backs), slices of their own too */
-    /* the per-wave slice: the option, or what the packer's prediction asks for (device-packed batches of large windows: upload_device_packed); large
-     * slices mean fewer waves per launch (option ws_budget_bytes) and more of the shared big slices for what still overflows */
-    const int64_t ws_bytes = db->ws_bytes_eff > ctx->ws_bytes_per_wave ? db->ws_bytes_eff : ctx->ws_bytes_per_wave;
-    const int64_t big_waves = ws_bytes > ctx->ws_bytes_per_wave && ctx->big_waves < 64 ? 64 : ctx->big_waves;
-    {
-        const double total = (double)(hbm_blocks + hbm_solo_max + hbm_early_max) * waves_per_block * (double)ws_bytes;
-        if (total > (double)ctx->ws_budget_bytes) {
-            const double f = (double)ctx->ws_budget_bytes / total;
-            auto shrink = [&](uint32_t b) { const uint32_t x = (uint32_t)(b * f); return x < 8 ? (b < 8 ? b : 8u) : x; };
-            hbm_blocks = shrink(hbm_blocks), hbm_solo_max = shrink(hbm_solo_max), hbm_early_max = shrink(hbm_early_max);
-        }
-    }
-    const uint32_t n_waves = hbm_blocks * waves_per_block;
-    const size_t ws_need = (size_t)(n_waves + (hbm_solo_max + hbm_early_max) * waves_per_block) * (size_t)ws_bytes;
-    const auto t_ws = std::chrono::steady_clock::now();
-    const bool ws_grows = ws_need > ctx->ws_alloc;
-    if (ws_need > ctx->ws_alloc) {
-        if (ctx->d_ws) {
-            AVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->d_ws);
-            ctx->d_ws = nullptr;
-            ctx->ws_alloc = 0;
-        }
-        AVK_HIP(ctx, hipMalloc((void **)&ctx->d_ws, ws_need + 256));
-        ctx->ws_alloc = ws_need;
-    }
-    const uint32_t big_blocks = (uint32_t)((big_waves + waves_per_block - 1) / waves_per_block);
-    const int64_t big_bytes = db->big_bytes_eff > ctx->big_ws_bytes && ctx->big_ws_bytes > 0 ? db->big_bytes_eff : ctx->big_ws_bytes;
-    const size_t big_need = (size_t)big_blocks * waves_per_block * (size_t)big_bytes;
-    if (big_need > ctx->big_alloc) {
-        if (ctx->d_big) {
-            AVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->d_big);
-            ctx->d_big = nullptr;
-            ctx->big_alloc = 0;
-        }
-        AVK_HIP(ctx, hipMalloc((void **)&ctx->d_big, big_need + 256));
-        ctx->big_alloc = big_need;
-    }
-
-    if (getenv("AVK_TIMING") && (ws_grows || big_need > 0))
-        fprintf(stderr, "avk run: workspaces (%.1f GB per-wave slices%s, %.1f GB shared slices) %.3f ms\n", (double)ws_need / 1e9, ws_grows ? ", allocated now" : "",
-                (double)big_need / 1e9, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_ws).count());
-    if (!db->scratch_clean) { /* normally left clean by avk_tally_reduce of the previous call */
-        AVK_HIP(ctx, hipMemsetAsync(db->d_partials, 0, (size_t)AVK_TALLY_STRIDE * AVK_TALLY_COPIES * sizeof(uint64_t), ctx->stream));
-        AVK_HIP(ctx, hipMemsetAsync(db->d_counters, 0, AVK_N_COUNTERS * sizeof(uint32_t), ctx->stream));
-    }
-    db->scratch_clean = false;
-    if (spec.emit_bp && mode == 0 && !db->d_bp && db->d_bp_off) {
-        int rc = db->dev_packed ? pool_alloc_t(ctx, db, &db->d_bp, (size_t)db->n_bp_groups * 4 + 4) : dev_alloc(ctx, &db->d_bp, (size_t)db->n_bp_groups * 4 + 4);
-        if (rc) return rc;
-    }
-    if (spec.emit_gm && !db->d_gm) {
-        int rc = db->dev_packed ? pool_alloc_t(ctx, db, &db->d_gm, (size_t)n * AVK_N_GROUPS * AVK_N_FIELDS + 4) : dev_alloc(ctx, &db->d_gm, (size_t)n * AVK_N_GROUPS * AVK_N_FIELDS);
-        if (rc) return rc;
-    }
-
-    AvkKernelArgs a;
-    memset(&a, 0, sizeof(a));
-    a.regions = db->d_regions;
-    a.blob = db->d_blob;
-    a.ref_bytes = ctx->d_ref;
-    a.ref_2bit = ctx->use_packed_reference ? ctx->d_ref2b : nullptr;
-    a.ref_exc = ctx->d_refexc;
-    a.n_regions = (uint32_t)n;
-    a.max_branch_factor = cfg->max_branch_factor;
-    a.enable_exact_shortcut = cfg->enable_exact_shortcut ? 1u : 0u;
-    a.mode = mode;
-    a.tier[0].ws_bytes = (uint64_t)ctx->lds_bytes_per_wave;
-    a.tier[0].ed_cap = (uint32_t)ctx->lds_ed_cap;
-    a.tier[1].ws_bytes = (uint64_t)ctx->lds2_bytes_per_wave;
-    a.tier[1].ed_cap = (uint32_t)ctx->lds2_ed_cap;
-    a.tier[2].ws_bytes = (uint64_t)ws_bytes;
-    a.tier[2].ed_cap = ctx->hbm_ed_cap > 0 ? ((uint32_t)ctx->hbm_ed_cap | AVK_CAP_BOUND_ONLY) : 0u;
-    a.tier[3].ws_bytes = (uint64_t)big_bytes;
-    a.tier[3].ed_cap = 0;
-    a.region_out = db->d_region_out;
-    a.group_metrics = spec.emit_gm ? db->d_gm : nullptr;
-    a.var_out = db->d_var_out;
-    a.seq_bytes = cfg->enable_sequences ? db->d_seq : nullptr;
-    a.seq_len = cfg->enable_sequences ? db->d_seqlen : nullptr;
-    a.tally = db->d_partials;
-    if (spec.emit_bp && mode == 0 && db->d_bp) {
-        a.bp_off = db->d_bp_off;
-        a.bp_out = db->d_bp;
-    }
-    if (db->dev_packed && !db->records_full) { /* (only the launches for handed-back regions ever meet an index >= lazy_from) */
-        a.lazy_dp = db->d_dp_args;
-        a.lazy_from = db->lazy_from;
-    }
-
-    if (cfg->max_branch_factor == 0) return fail(ctx, AVK_E_ARG, "max_branch_factor must be greater than 0 (query_optimizer.rs:177)");
-
-    if (!ctx->lds_attr_set) {
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_region_kernel_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_region_kernel_lds_lazy, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->lds_attr_set = true;
-    }
-    const bool timed = ctx->timing_events != 0;
-    if (timed) AVK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    ctx->ev_lane_valid = false;
-    /* ---- the step's plan: the launches below name chains (avk_step_plan.h), the plan gives each chain its stream.  Two chains on one stream follow each other in the
-     * order they are queued here, and the events between them are dropped:
-     *   fork      a stream waits for the caller's stream once, ahead of the first chain queued on it
-     *   end/join  the end of every chain is recorded as today; the caller's stream waits per STREAM, for the last end recorded on it, and not again for an earlier one */
-    const bool folded = ctx->step_queues ? ctx->step_queues < AVK_STEP_QUEUES_WIDE : ctx->step_folded_auto;
-    AvkStepPlan plan = avk_step_plan(folded ? AVK_STEP_SLOTS_FOLDED : AVK_STEP_QUEUES_WIDE, use_fast);
-    if (folded) {
-        AvkStepPlan trial;
-        if (use_fast && avk_step_plan_parse(getenv("AVK_STEP_PLAN"), &trial)) plan = trial; /* (measurements: another assignment, a digit per chain) */
-        AVK_HIP(ctx, ensure_fold_streams(ctx));
-    }
-    hipStream_t slot_stream[AVK_N_CHAINS] = {ctx->stream, ctx->side_stream, ctx->wide_stream, ctx->side_stream2, ctx->lane_stream, ctx->lane_stream2, ctx->lane_stream3, ctx->lane_stream4};
-    if (folded)
-        for (int k = 1; k < AVK_STEP_SLOTS_FOLDED; ++k) slot_stream[k] = ctx->fold_stream[k - 1];
-    auto S = [&](int chain) { return slot_stream[plan.slot[chain]]; };
-    auto same_stream = [&](int c1, int c2) { return plan.slot[c1] == plan.slot[c2]; };
-    bool slot_forked[AVK_N_CHAINS] = {true, false, false, false, false, false, false, false};
-    auto fork = [&](int chain, hipEvent_t ev) { /* ev: recorded on the caller's stream */
-        const int s = plan.slot[chain];
-        if (s == 0 || (folded && slot_forked[s])) return hipSuccess;
-        slot_forked[s] = true;
-        return hipStreamWaitEvent(slot_stream[s], ev, 0);
-    };
-    struct ChainEnd {
-        hipEvent_t ev;
-        int slot, seq;
-    };
-    enum { END_LDS_SOLO, END_CLASS_C, END_NOT_WIDE, END_LANE0, END_LANE1, END_LANE2, END_LANE3, END_EARLY, END_DONE, N_ENDS };
-    ChainEnd ends[N_ENDS];
-    int end_seq = 0, slot_joined[AVK_N_CHAINS] = {0, 0, 0, 0, 0, 0, 0, 0}; /* per stream: the latest end the caller's stream already waits for */
-    auto record_end = [&](int id, hipEvent_t ev, int chain) {
-        ends[id] = {ev, plan.slot[chain], ++end_seq};
-        return hipEventRecord(ev, S(chain));
-    };
-    auto join = [&](const int *ids, int k) { /* the caller's stream waits for these ends (the plan with a stream per chain: each of them, in this order) */
-        int order[N_ENDS];
-        for (int i = 0; i < k; ++i) order[i] = ids[i];
-        if (folded) std::sort(order, order + k, [&](int x, int y) { return ends[x].seq > ends[y].seq; });
-        for (int i = 0; i < k; ++i) {
-            const ChainEnd &e = ends[order[i]];
-            if (e.slot == 0 || (folded && slot_joined[e.slot] >= e.seq)) continue;
-            if (slot_joined[e.slot] < e.seq) slot_joined[e.slot] = e.seq;
-            const hipError_t r = hipStreamWaitEvent(ctx->stream, e.ev, 0);
-            if (r != hipSuccess) return r;
-        }
-        return hipSuccess;
-    };
-    auto join1 = [&](int id) { return join(&id, 1); };
-    const uint32_t big_slots =use[2] && use[3] ? (uint32_t)(big_waves < (int64_t)AVK_CTR_BIG_BUSY_LEN ? big_waves : (int64_t)AVK_CTR_BIG_BUSY_LEN) : 0u;
-    const uint32_t *list = nullptr, *count = nullptr; /* first launch: the records themselves are in work order */
-    uint32_t *lists[4] = {db->d_overflow, db->d_overflow2, db->d_overflow3, db->d_overflow4};
-    int nlist = 0;
-    bool solo_pending = false, hbm_solo_pending = false, deferred_pending = false, early_pending = false, hbm_shared = false, wide_x_pending = false, chains = false;
-    int chain_join[4] = {0, 0, 0, 0}; /* handback_chains: the ends of the lane chains, and the launch that follows them at the end of the step */
-    int n_chain_join = 0;
-    bool chains_flushed = false;
-    AvkKernelArgs chain_d;
-    uint32_t chain_dblocks = 0;
-    memset(&chain_d, 0, sizeof(chain_d));
-    auto flush_chains = [&]() { /* what the chains' launches of avk_wide.inl left (d_overflow7): behind the ends of the lane chains, once per step */
-        chains_flushed = true;
-        const hipError_t r = join(chain_join, n_chain_join);
-        if (r != hipSuccess) return r;
-        hipLaunchKernelGGL(avk_region_kernel_lds_lazy, dim3(chain_dblocks), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ctx->stream, chain_d);
-        return hipGetLastError();
-    };
-    uint32_t hbm_shared_base = 0; /* records of class C ahead of the shared list (a team launch has them) */
-    for (int t = 0; t < 4 && n; ++t) {
-        if (!launch[t]) continue;
-        a.pass_tier = (uint32_t)t;
-        a.work_list = list;
-        a.work_base = 0;
-        a.n_work_dev = count;
-        a.work_counter = db->d_counters + avk_ctr_tier_cursors((uint32_t)t);
-        if (t != last) {
-            a.overflow_list = lists[nlist];
-            a.overflow_count = db->d_counters + avk_ctr_overflow_count((uint32_t)nlist);
-        } else {
-            a.overflow_list = nullptr;
-            a.overflow_count = nullptr;
-        }
-        const bool first_launch = list == nullptr; /* ev0 sits right before it */
-        if (t >= 2) { /* the HBM launches read the list the LDS solo launch appends to; the tier-1 launch does not */
-            if (deferred_pending && chains && !chains_flushed) AVK_HIP(ctx, flush_chains()); /* ahead of the waits for the long solo launches, which it does not depend on */
-            if (solo_pending) AVK_HIP(ctx, join1(END_LDS_SOLO));
-            solo_pending = false;
-            /* the tier-3 launch of its own (big_slots == 0) reads the list the HBM solo launch appends to */
-            if (t == 3 && hbm_solo_pending) {
-                AVK_HIP(ctx, join1(END_CLASS_C));
-                hbm_solo_pending = false;
-            }
-        }
-        a.n_work = (uint32_t)n - (t == 0 ? n_fast : 0u);
-        a.high_priority = 0;
-        a.esc_bytes = 0;
-        a.esc_enabled = 0;
-        /* pairs of a merge batch: the bulk launch is long (200,000 regions beside 10 M in the lanes) and its 40 KB workgroups do not all become resident while the
-         * lane launches keep taking the LDS that comes free; a statically dealt share would wait for workgroups that start when the lanes are done
-         * (12 or 22 ms per whole-genome merge, from call to call) — everything is claimed there */
-        /* the same for every short list — the bulk beside the lane classes (a few thousand regions) and the overflow lists of the later tiers: same step,
-         * fewer slow calls (tools/gpu_static_ab.py); a static share is for the first launch of a batch that goes through the wave-per-region kernels as a whole */
-        a.static_pct = mode == 0 && t == 0 && a.n_work >= 16384u ? (uint32_t)ctx->static_pct : 0u; /* (50,000 single-call regions through the bulk: 0.40 ms with the static share, 0.43 without) */
-        a.n_shards = 8;
-        a.claim = (uint32_t)ctx->claim;
-        if (t == 0) {
-            a.hbm_ws = nullptr;
-            /* Solo launches: the regions the host predicted to outgrow the small slice are solved AT THE SAME TIME, on the
-             * side stream, launched just before the bulk, so the long searches overlap with the bulk instead of forming
-             * the tail of a later launch:
-             *   class B (WorkPlan::n_hard): one-wave workgroups with a tier-1 LDS slice each; a solo workgroup's LDS
-             *           displaces exactly one bulk workgroup;
-             *   class C (WorkPlan::n_hbm):  predicted to outgrow tier 1 too: a small HBM-tier launch (its registers
-             *           displace about two bulk workgroups per workgroup).
-             * Both hand what they cannot hold to the list the first HBM launch of the main stream reads. */
-            const bool solo_ok = ctx->solo_blocks_max && blocks >= 8;
-            const bool hbm_solo_ok = solo_ok && launch[2] && db->plan.n_hbm;
-            const uint32_t n_c = hbm_solo_ok ? db->plan.n_hbm : 0u;          /* regions of the HBM solo launch */
-            const uint32_t n_front = db->plan.n_hbm + db->plan.n_hard - n_c; /* predicted-hard records after them */
-            uint32_t solo = 0, solo_regions = 0, hbm_solo = 0;
-            if (solo_ok && use[1] && n_front &&
-                (size_t)ctx->lds2_bytes_per_wave <= 2 * (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave) {
-                solo = n_front < (uint32_t)ctx->solo_blocks_max ? n_front : (uint32_t)ctx->solo_blocks_max;
-                if (solo > blocks / 4) solo = blocks / 4;
-                const uint64_t cap = (uint64_t)solo * (uint64_t)ctx->solo_regions_per_wave;
-                solo_regions = n_front < cap ? n_front : (uint32_t)cap; /* the others lead the bulk list */
-            }
-            if (n_c) {
-                hbm_solo = (n_c + 3) / 4;
-                if (hbm_solo > hbm_solo_max) hbm_solo = hbm_solo_max;
-            }
-            const int solo_list = launch[1] ? 1 : 0; /* the list the first HBM launch reads */
-            const bool later = last > solo_list;
-            if (solo || hbm_solo) AVK_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream)); /* after the memsets */
-            if (hbm_solo && use_wide && db->plan.n_hbm_notwide && 2u * (db->plan.n_hbm_notwide < n_c ? db->plan.n_hbm_notwide : n_c) <= n_c && !db->notwide_ready) { /* (only the class's wide launch with its companion reads the list) */
-                /* the list of the class C records that are not avk_wide.inl's: once per batch, and the FIRST thing queued behind the fork — made behind the class's
-                 * wide launch its 20-170 workgroups waited for a place among the step's persistent waves (0.2 ms in a queued shard step, 1.2 ms in a merge call) */
-                AVK_HIP(ctx, fork(AVK_CH_NOT_WIDE, ctx->ev_fork));
-                AVK_HIP(ctx, hipMemsetAsync(db->d_notwide + n + 1, 0, sizeof(uint32_t), S(AVK_CH_NOT_WIDE)));
-                hipLaunchKernelGGL(avk_notwide_list_kernel, dim3((n_c + 255u) / 256u), dim3(256), 0, S(AVK_CH_NOT_WIDE), db->d_regions, n_c, db->d_notwide, db->d_notwide + n + 1);
-                AVK_HIP(ctx, hipGetLastError());
-                db->notwide_ready = true;
-            }
-            bool wide_c = false, wide_x = false;
-            if (hbm_solo) {
-                const uint32_t *c_list = nullptr, *c_left = nullptr; /* what the launches of avk_wide.inl leave of class C (without them: the class's records themselves) */
-                AVK_HIP(ctx, fork(AVK_CH_CLASS_C, ctx->ev_fork));
-                /* how many of them are not the wide kernel's by their own record (a long window, many calls on a side): none or few in a genome, all of them in a
-                 * batch of large windows (--min-variant-gap 1000) — which then keeps the launches of round 3: every HBM wave on the whole list */
-                const uint32_t n_nw = db->plan.n_hbm_notwide < n_c ? db->plan.n_hbm_notwide : n_c;
-                if (use_wide && 2u * n_nw <= n_c) { /* class C through avk_wide.inl first; the HBM launch behind it on this stream takes the list of what that could not take */
-                    AvkKernelArgs w = a;
-                    w.work_list = nullptr;
-                    w.n_work_dev = nullptr;
-                    w.work_base = 0;
-                    w.n_work = n_c;
-                    w.work_counter = db->d_counters + AVK_CTR_WIDE_C_CURSOR;
-                    w.overflow_list = db->d_overflow5;
-                    w.overflow_count = db->d_counters + AVK_CTR_WIDE_C_LEFT;
-                    /* (512 one-wave workgroups for a genome's 6,000-15,000 records; a merge job's 42,000 lasted 7.2 ms on them, the longest launch of its step: one
-                     * workgroup per 32 records up to four times as many — profiles/r06_merge_step.txt) */
-                    uint32_t wb = (uint32_t)ctx->wide_blocks;
-                    if (!getenv("AVK_WIDE_BLOCKS") && n_c / 32u > wb) wb = n_c / 32u < 4u * wb ? n_c / 32u : 4u * wb;
-                    uint32_t wg = n_c < wb ? n_c : wb;
-                    /* workgroups of the launch for the records that are not the wide kernel's: slices from the END of the solo launch's share, which keeps at least half of
-                     * it — a batch with large per-wave slices (adaptive_ws under its budget) may have a share of eight workgroups, and the two launches must never meet on
-                     * a slice (they did: xb == hbm_solo_max left the solo launch one workgroup ON the other's first slices — wrong results in a fuzz case where every
-                     * region was planned as class C, profiles/r04_gpu_fuzz_classc.txt) */
-                    /* (a wave for each of these records and more: they lead the list, most calls first, and a wave that claimed four of them at a time solved four long
-                     * searches one after the other — 1.4 ms at the end of a rank's shard whose lanes were done after 0.8, profiles/r05_small_batches.txt) */
-                    uint32_t xb = n_nw;
-                    xb = xb < hbm_solo ? xb : hbm_solo;
-                    xb = xb < 64u ? xb : 64u;
-                    if (2u * xb > hbm_solo_max) xb = hbm_solo_max / 2u;
-                    avk::wide::WideArgs wc = wa;
-                    wc.skip_static = n_nw && xb ? 1u : 0u; /* (without the launch below such a record is handed over like any other) */
-                    hipLaunchKernelGGL(avk_wide_kernel, dim3(wg), dim3(64), (size_t)ctx->wide_lds_bytes, S(AVK_CH_CLASS_C), w, wc);
-                    AVK_HIP(ctx, hipGetLastError());
-                    if (n_nw && xb) { /* the records of class C that are not for the wide kernel by what they say themselves (avk_wide_static_ok: a long window, many calls on a
-                       * side) start at the same time, on the HBM-tier kernel and a stream of their own: they are few and each of them is long */
-                        /* a wave per record, one claim each, from a list made just ahead of the launch (walking the whole class in claims of four, a wave solved the
-                         * records of a claim one after the other: 2.06 -> 1.91 ms for the genome's 27, 0.96 -> 0.90 for a shard's 7) */
-                        AvkKernelArgs x = avk_list_reader_args(a, db->d_notwide, db->d_notwide + n + 1, db->d_counters + AVK_CTR_TEAM_CURSOR);
-                        x.pass_tier = 2;
-                        x.high_priority = 1;
-                        x.n_waves = xb * waves_per_block;
-                        x.hbm_ws = ctx->d_ws + (size_t)(n_waves + (hbm_solo_max - xb) * waves_per_block) * (size_t)ws_bytes; /* the last slices of the solo launch's share (that launch gets the others) */
-                        avk_big_slice_args(x, ctx->d_big, db->d_counters, big_slots);
-                        AVK_HIP(ctx, fork(AVK_CH_NOT_WIDE, ctx->ev_fork));
-                        /* (a wave per region here: these long windows hold a handful of calls, their searches are short chains where a team's hand-overs cost more
-                         * than its parallel pieces give — shard 1.19 -> 1.31 ms, dense mix 2.29 -> 2.53 with teams, profiles/r06_team.txt) */
-                        hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(xb), dim3(256), 0, S(AVK_CH_NOT_WIDE), x);
-                        AVK_HIP(ctx, hipGetLastError());
-                        AVK_HIP(ctx, record_end(END_NOT_WIDE, ctx->ev_wide, AVK_CH_NOT_WIDE));
-                        wide_x = true;
-                        if (hbm_solo > hbm_solo_max - xb) hbm_solo = hbm_solo_max - xb; /* (at least half of the share: xb <= hbm_solo_max / 2) */
-                    }
-                    wide_c = true;
-                    c_list = db->d_overflow5;
-                    c_left = db->d_counters + AVK_CTR_WIDE_C_LEFT;
-                    if (ctx->wide_retry_lds_bytes > ctx->wide_lds_bytes) {
-                        /* what it hands over at run time is nearly always a search that outgrew the 16 KB (nodes, wavefront blocks): once more with the LDS of a
-                         * whole workgroup, a few waves — the wave-per-region kernel needs 2 ms for such a region, at the end of this chain */
-                        AvkKernelArgs w2 = w;
-                        w2.work_list = db->d_overflow5;
-                        w2.n_work_dev = db->d_counters + AVK_CTR_WIDE_C_LEFT;
-                        w2.work_base = 0;
-                        w2.n_work = 0;
-                        w2.work_counter = db->d_counters + AVK_CTR_WIDE_RETRY_CURSOR;
-                        w2.overflow_list = db->d_overflow8;
-                        w2.overflow_count = db->d_counters + AVK_CTR_WIDE_RETRY_LEFT;
-                        avk::wide::WideArgs wb = wa;
-                        wb.lds_words = (uint32_t)(ctx->wide_retry_lds_bytes / 4);
-                        hipLaunchKernelGGL(avk_wide_kernel, dim3(32), dim3(64), (size_t)ctx->wide_retry_lds_bytes, S(AVK_CH_CLASS_C), w2, wb);
-                        AVK_HIP(ctx, hipGetLastError());
-                        c_list = db->d_overflow8;
-                        c_left = db->d_counters + AVK_CTR_WIDE_RETRY_LEFT;
-                    }
-                }
-                uint32_t team_head = 0; /* records at the front of class C (most calls first) that a team launch takes */
-                if (!wide_c && ctx->team_long_windows && ctx->team_head_regions > 0 && n_c > 1) {
-                    /* a batch of large windows (--min-variant-gap 1000: every region is class C and none is the wide kernel's): its step is as long as its few longest
-                     * searches — 0.25 s on one wave for 92 calls on 20 kbp while the other 49,000 regions need 0.05 s of the whole chip — so the head of the class, which
-                     * is sorted most calls first, gets a workgroup per region; the other launches start behind it in the list */
-                    uint32_t xb = n_c / 2u < (uint32_t)ctx->team_head_regions ? n_c / 2u : (uint32_t)ctx->team_head_regions;
-                    if (xb > hbm_solo_max / 2u) xb = hbm_solo_max / 2u;
-                    if (xb) {
-                        AvkKernelArgs x = avk_list_reader_args(a, nullptr, nullptr, db->d_counters + AVK_CTR_TEAM_CURSOR); /* (no list: the first xb records) */
-                        x.n_work = xb;
-                        x.pass_tier = 2;
-                        x.team = (uint32_t)ctx->team_long_windows;
-                        x.high_priority = 1;
-                        x.n_waves = xb * waves_per_block;
-                        x.hbm_ws = ctx->d_ws + (size_t)(n_waves + (hbm_solo_max - xb) * waves_per_block) * (size_t)ws_bytes; /* the last slices of the solo launch's share */
-                        avk_big_slice_args(x, ctx->d_big, db->d_counters, big_slots);
-                        AVK_HIP(ctx, fork(AVK_CH_NOT_WIDE, ctx->ev_fork));
-                        hipLaunchKernelGGL(avk_region_kernel_team, dim3(xb), dim3(256), 0, S(AVK_CH_NOT_WIDE), x);
-                        AVK_HIP(ctx, hipGetLastError());
-                        AVK_HIP(ctx, record_end(END_NOT_WIDE, ctx->ev_wide, AVK_CH_NOT_WIDE));
-                        wide_x = true;
-                        team_head = xb;
-                        if (hbm_solo > hbm_solo_max - xb) hbm_solo = hbm_solo_max - xb;
-                    }
-                }
-                AvkKernelArgs s = avk_list_reader_args(a, c_list, c_left, db->d_counters + AVK_CTR_HBM_SOLO_TICKET);
-                s.work_base = team_head;
-                s.n_work = n_c - team_head;
-                s.pass_tier = 2;
-                s.high_priority = 1;
-                s.n_waves = hbm_solo * waves_per_block;
-                s.hbm_ws = ctx->d_ws + (size_t)n_waves * (size_t)ws_bytes; /* its own slices: the main stream's HBM launch may run beside it */
-                avk_big_slice_args(s, ctx->d_big, db->d_counters, big_slots);
-                /* same capacities as the last tier: what does not fit fails with CAPACITY */
-                if (!big_slots && launch[3]) { /* the big tier has a launch of its own */
-                    s.overflow_list = lists[launch[1] ? 2 : 1];
-                    s.overflow_count = db->d_counters + avk_ctr_overflow_count(launch[1] ? 2 : 1);
-                }
-                hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(hbm_solo), dim3(256), 0, S(AVK_CH_CLASS_C), s);
-                AVK_HIP(ctx, hipGetLastError());
-                AVK_HIP(ctx, record_end(END_CLASS_C, ctx->ev_join2, AVK_CH_CLASS_C));
-                hbm_solo_pending = true;
-                hbm_shared = !wide_c; /* (the records of class C are the wide launch's: the main stream's HBM launch has nothing to share) */
-                hbm_shared_base = team_head;
-                wide_x_pending = wide_x;
-            }
-            if (solo) {
-                AvkKernelArgs s = a;
-                s.pass_tier = 1;
-                s.work_base = n_c;
-                s.n_work = solo_regions;
-                s.work_counter = db->d_counters + AVK_CTR_LDS_SOLO_CURSOR;
-                s.static_pct = 0;
-                s.n_shards = 1;
-                s.claim = 1;
-                s.n_waves = solo;
-                s.high_priority = 1;
-                s.overflow_list = later ? lists[solo_list] : nullptr;
-                s.overflow_count = later ? db->d_counters + avk_ctr_overflow_count((uint32_t)solo_list) : nullptr;
-                AVK_HIP(ctx, fork(AVK_CH_LDS_SOLO, ctx->ev_fork));
-                hipLaunchKernelGGL(avk_region_kernel_lds, dim3(solo), dim3(64), (size_t)ctx->lds2_bytes_per_wave, S(AVK_CH_LDS_SOLO), s);
-                AVK_HIP(ctx, hipGetLastError());
-                AVK_HIP(ctx, record_end(END_LDS_SOLO, ctx->ev_join, AVK_CH_LDS_SOLO));
-                solo_pending = true;
-            }
-            if (solo || hbm_solo) {
-                a.work_base = n_c + solo_regions;
-                a.n_work = (uint32_t)n - n_fast - n_c - solo_regions;
-            }
-            /* ---- the lane-per-region launches (avk_lane.inl): the classes with two calls per side (long, latency-bound tiles at low
-             * occupancy) on a stream of their own, the one-call classes on the caller's stream ahead of the bulk.  What a lane cannot
-             * finish goes to the DEFERRED list, solved after the bulk by an LDS launch of the wave-per-region kernel. */
-            /* lane chains: 0 the two-call classes, 1 the one-call classes, 2 the three-call class, 3 the heads of the two-call classes */
-            enum { N_LS = 4 };
-            const int lchain[N_LS] = {AVK_CH_TWO_CALL, AVK_CH_ONE_CALL, AVK_CH_THREE_CALL, AVK_CH_HEAD_HANDBACKS};
-            hipStream_t lstream[N_LS] = {S(lchain[0]), S(lchain[1]), S(lchain[2]), S(lchain[3])};
-            hipEvent_t ljoin[N_LS] = {ctx->ev_lane_join, ctx->ev_lane_join2, ctx->ev_lane_join3, ctx->ev_lane_join4};
-            const int lend[N_LS] = {END_LANE0, END_LANE1, END_LANE2, END_LANE3};
-            bool lused[N_LS] = {false, false, false, false}, ljoined[N_LS] = {false, false, false, false}, early_used = false;
-            if (use_fast) {
-                if (!ctx->lane_attr_set) {
-                    AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_lane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel_wide_regs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    ctx->lane_attr_set = true;
-                }
-                AvkKernelArgs f = a;
-                f.overflow_list = lists[2];
-                f.overflow_count = db->d_counters + avk_ctr_overflow_count(AVK_CTR_DEFERRED_LIST);
-                AVK_HIP(ctx, hipEventRecord(ctx->ev_lane_fork, ctx->stream));
-                /* hand-backs per chain: the launches of a lane stream append to a list of the stream's own, a head launch to one of its own; a list is read by a launch
-                 * of avk_wide.inl that follows its writers in stream order (the chain's list: on the chain's stream, no event; a head's: on the fourth lane stream,
-                 * behind the head's event, while the rest of the class runs).  One launch for one list behind ALL lane streams started 60-130 us after the last lane
-                 * launch (three event waits) and lasted as long as its longest region — a head's hand-back, 160-340 us — at the very end of the step. */
-                chains = use_wide && ctx->wide_lane_handbacks && !ctx->lane_head_stream;
-                struct HbSeg {
-                    uint32_t *list, *count, *cursor;
-                };
-                uint32_t hb_off = 0;
-                int hb_n = 0, hb_heads = 0;
-                auto hb_new = [&](uint32_t cap) {
-                    HbSeg g = {lists[2] + hb_off, db->d_counters + AVK_CTR_HB_COUNTS + hb_n, db->d_counters + AVK_CTR_HB_CURSORS + hb_n}; /* (hb_n < AVK_CTR_HB_SEGS: two chains, the staged heads, the pairs' list) */
-                    hb_off += cap;
-                    hb_n += 1;
-                    return g;
-                };
-                auto hb_consume = [&](hipStream_t st, const HbSeg &g) {
-                    AvkKernelArgs w = a;
-                    w.work_list = g.list;
-                    w.n_work_dev = g.count;
-                    w.work_base = 0;
-                    w.n_work = 0;
-                    w.work_counter = g.cursor;
-                    w.overflow_list = db->d_overflow7;
-                    w.overflow_count = db->d_counters + AVK_CTR_WIDE_LANES_LEFT;
-                    hipLaunchKernelGGL(avk_wide_kernel_lazy, dim3((uint32_t)ctx->wide_lazy_blocks), dim3(64), (size_t)ctx->wide_lds_bytes, st, w, wa);
-                    return hipGetLastError();
-                };
-                HbSeg chain_seg[2] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-                if (chains) {
-                    uint32_t cap[2] = {0, 0};
-                    for (int fc = 0; fc < lane_k; ++fc) {
-                        const uint32_t mv = fc == AVK_FAST_PAIR ? 1u : AVK_FAST_CLASS[fc].maxv;
-                        if (db->fast_tiles[fc] && mv <= 2) cap[mv == 2 ? 0 : 1] += db->fast_tiles[fc] * 64u;
-                    }
-                    chain_seg[0] = hb_new(cap[0]);
-                    chain_seg[1] = hb_new(cap[1]);
-                }
-                for (int fc = lane_k - 1; fc >= 0; --fc) {
-                    if (!db->fast_tiles[fc]) continue;
-                    if (fc == AVK_FAST_PAIR && mode == 0 && ctx->lane_pairs) {
-                        /* looked up, not searched (avk_pairs.inl): first on the stream of the one-call classes, BESIDE everything else.  (Alone it needs 0.18 ms;
-                         * beside the persistent waves of the other launches its workgroups wait for wave slots and it lasts 1.1 ms — in their shadow, which
-                         * measured better than 0.18 ms ahead of them: 3.95 against 4.2 ms per whole-genome step.) */
-                        /* (AVK_PAIRS_OWN_STREAM=1: on the fourth lane stream with a hand-back list of its own, the one-call chain not waiting for it — a shard's step
-                         * 1.04 -> 1.00 ms, a genome's 2.33 -> 2.39: profiles/r06_handback_chains.txt) */
-                        const int li = chains && getenv("AVK_PAIRS_OWN_STREAM") ? 3 : 1;
-                        if (!lused[li]) {
-                            AVK_HIP(ctx, fork(lchain[li], ctx->ev_lane_fork));
-                            lused[li] = true;
-                        }
-                        const int rt = ensure_pair_table(ctx, cfg->max_branch_factor, lstream[li]);
-                        if (rt) return rt;
-                        avk::pairs::PairArgs pa;
-                        pa.recs = db->d_fast + db->fast_word_base[fc];
-                        pa.n_tiles = db->fast_tiles[fc];
-                        pa.gen_base = db->plan.fast_base[fc];
-                        pa.tab = ctx->d_pair_tab;
-                        pa.tile_counter = db->d_counters + AVK_CTR_LANE_TILES + fc;
-                        uint32_t pg = (uint32_t)ctx->n_cus * (uint32_t)(ctx->pair_blocks_per_cu > 0 ? ctx->pair_blocks_per_cu : 1);
-                        const uint32_t claims = (pa.n_tiles + avk::pairs::PAIR_CLAIM - 1) / avk::pairs::PAIR_CLAIM;
-                        if (pg > (claims + 3u) / 4u) pg = (claims + 3u) / 4u;
-                        AvkKernelArgs fp = f;
-                        HbSeg pseg = chain_seg[1];
-                        if (chains && li == 3) pseg = hb_new(pa.n_tiles * 64u);
-                        if (chains) fp.overflow_list = pseg.list, fp.overflow_count = pseg.count;
-                        hipLaunchKernelGGL(avk_pair_kernel, dim3(pg), dim3(256), 0, lstream[li], fp, pa);
-                        AVK_HIP(ctx, hipGetLastError());
-                        if (chains && li == 3) AVK_HIP(ctx, hb_consume(lstream[li], pseg));
-                        continue;
-                    }
-                    /* (the looked-up class in merge mode or with the option off: its records are those of a one-call class) */
-                    const AvkFastClass &cl = fc == AVK_FAST_PAIR ? AVK_FAST_CLASS[1] : AVK_FAST_CLASS[fc];
-                    avk::lane::LaneArgs la;
-                    la.recs = db->d_fast + db->fast_word_base[fc];
-                    la.rec_words = AVK_FAST_WORDS_OF(cl.maxv);
-                    la.n_tiles = db->fast_tiles[fc];
-                    la.tile_counter = db->d_counters + AVK_CTR_LANE_TILES + fc;
-                    la.W = cl.W;
-                    la.nm = 1u << cl.maxv;
-                    la.ed_max = cl.ed_max;
-                    la.qcap = cl.qcap;
-                    la.gen_base = db->plan.fast_base[fc];
-                    la.lanes_log2 = lane_width_log2(ctx, cl.maxv);
-                    /* kept node states: where the expensive searches are — the three-call class and the heads of the others (16 records per wave: half a KB of LDS per
-                     * slot; in the 64-wide launches of the regions without estimated edits a slot would be 2 KB) */
-                    const uint32_t pool_heavy = ctx->lane_pool < 0 ? (la.nm == 2 ? 2u : (la.nm == 4 ? 4u : 6u)) /* lane_pool_default */ : (uint32_t)ctx->lane_pool;
-                    la.pool = ctx->lane_pool < 0 ? (cl.maxv > 2 ? pool_heavy : 0u) : (uint32_t)ctx->lane_pool;
-                    la.max_nodes = cl.maxv > 2 ? (uint32_t)ctx->lane_node_cap : 250u;
-                    la.max_ed_c = (uint32_t)ctx->lane_metrics_ed_cap;
-                    uint32_t grid = 0;
-                    const size_t lds = lane_launch_geometry(ctx, la, &grid);
-                    if (!lds) return fail(ctx, AVK_E_ARG, "lane kernel class %d does not fit the LDS", fc);
-                    const int li = cl.maxv == 2 ? 0 : (cl.maxv == 1 ? 1 : 2);
-                    if (!lused[li]) {
-                        AVK_HIP(ctx, fork(lchain[li], ctx->ev_lane_fork));
-                        lused[li] = true;
-                    }
-                    if (cl.maxv > 2) {
-                        /* The three-call class gives up early on large searches (la.max_nodes): those regions are for whole wavefronts.
-                         * They get a list of their own and an HBM-tier launch right behind the class on its stream, so that they are
-                         * being solved while the other lane classes still run, not after them. */
-                        AvkKernelArgs f3 = f;
-                        f3.overflow_list = lists[3];
-                        f3.overflow_count = db->d_counters + AVK_CTR_HB3_COUNT;
-                        hipStream_t es = lstream[li]; /* where the launch for the handed-back regions goes */
-                        launch_lane_class(ctx, grid, lds, lstream[li], f3, la);
-                        AVK_HIP(ctx, hipGetLastError());
-                        /* the launch for what ALL lanes hand back waits for the lane launches only, not for the launch behind this class */
-                        AVK_HIP(ctx, record_end(lend[li], ljoin[li], lchain[li]));
-                        ljoined[li] = true;
-                        AvkKernelArgs e = avk_list_reader_args(a, lists[3], db->d_counters + AVK_CTR_HB3_COUNT, db->d_counters + AVK_CTR_HB3_CURSOR);
-                        e.pass_tier = 2;
-                        e.high_priority = 0;
-                        e.hbm_ws = ctx->d_ws + (size_t)(n_waves + hbm_solo_max * waves_per_block) * (size_t)ws_bytes;
-                        avk_big_slice_args(e, ctx->d_big, db->d_counters, big_slots);
-                        uint32_t eb = hbm_blocks < hbm_early_max ? hbm_blocks : hbm_early_max;
-                        if (use_wide) { /* large searches on small windows: avk_wide.inl first, the HBM-tier launch takes what is left */
-                            AvkKernelArgs w = e;
-                            w.work_counter = db->d_counters + AVK_CTR_WIDE_HB3_CURSOR;
-                            w.overflow_list = db->d_overflow6;
-                            w.overflow_count = db->d_counters + AVK_CTR_WIDE_HB3_LEFT;
-                            hipLaunchKernelGGL(avk_wide_kernel_lazy, dim3((uint32_t)ctx->wide_lazy_blocks), dim3(64), (size_t)ctx->wide_lds_bytes, es, w, wa);
-                            AVK_HIP(ctx, hipGetLastError());
-                            e.work_list = db->d_overflow6;
-                            e.n_work_dev = db->d_counters + AVK_CTR_WIDE_HB3_LEFT;
-                        }
-                        e.n_waves = eb * waves_per_block;
-                        hipLaunchKernelGGL(avk_region_kernel_hbm_lazy, dim3(eb), dim3(256), 0, es, e);
-                        AVK_HIP(ctx, hipGetLastError());
-                        AVK_HIP(ctx, record_end(END_EARLY, ctx->ev_lane_early, lchain[li])); /* the caller's stream waits for this one at the end */
-                        early_used = true;
-                        continue;
-                    }
-                    /* The head of the class — the tiles of regions with estimated edits, which the cost key puts first — in narrow tiles
-                     * of its own: lanes that diverge take turns, so 64 expensive regions in one wave take 64 turns; 16 per wave, four times as
-                     * many waves.  Same records, same stream, a launch ahead of the rest of the class. */
-                    const uint32_t head_tiles = ctx->lane_head_width ? (db->plan.n_fast_heavy[fc] + 63u) / 64u : 0u;
-                    if (head_tiles > 0 && head_tiles < la.n_tiles && (uint32_t)ctx->lane_head_width < (1u << la.lanes_log2)) {
-                        avk::lane::LaneArgs hd = la;
-                        hd.n_tiles = head_tiles;
-                        hd.tile_counter = db->d_counters + AVK_CTR_HEAD_TILES + fc;
-                        hd.lanes_log2 = head_width_log2(ctx, db->plan.n_fast_heavy[fc]);
-                        hd.pool = pool_heavy;
-                        uint32_t hgrid = 0;
-                        const size_t hlds = lane_launch_geometry(ctx, hd, &hgrid);
-                        const int hi = (cl.maxv == 2 && ctx->lane_head_stream) ? 3 : li; /* a long head runs beside the rest of its class */
-                        if (!lused[hi]) {
-                            AVK_HIP(ctx, fork(lchain[hi], ctx->ev_lane_fork));
-                            lused[hi] = true;
-                        }
-                        AvkKernelArgs fh = f;
-                        HbSeg hseg = {nullptr, nullptr, nullptr};
-                        static_assert(sizeof(ctx->ev_hb) / sizeof(ctx->ev_hb[0]) == AVK_CTR_HB_HEADS, "an event per staged head");
-                        const bool staged = chains && hb_heads < (int)AVK_CTR_HB_HEADS && (cl.maxv == 2 || getenv("AVK_STAGE_ALL_HEADS")); /* (the one-call heads are short: their hand-backs wait for the chain's end) */
-                        if (staged) {
-                            hseg = hb_new(head_tiles * 64u);
-                            fh.overflow_list = hseg.list, fh.overflow_count = hseg.count;
-                        } else if (chains) {
-                            fh.overflow_list = chain_seg[li].list, fh.overflow_count = chain_seg[li].count;
-                        }
-                        const bool hb_follows = same_stream(lchain[hi], lchain[3]); /* the consumer follows its head in stream order: no event */
-                        launch_lane_class(ctx, hgrid, hlds, lstream[hi], fh, hd, staged && !hb_follows ? ctx->ev_hb[hb_heads] : nullptr);
-                        AVK_HIP(ctx, hipGetLastError());
-                        if (staged) { /* its hand-backs: solved beside the rest of the class */
-                            if (!hb_follows) AVK_HIP(ctx, hipStreamWaitEvent(lstream[3], ctx->ev_hb[hb_heads], 0));
-                            slot_forked[plan.slot[lchain[3]]] = true;
-                            lused[3] = true; /* (its first command waits for an event behind ev_lane_fork) */
-                            AVK_HIP(ctx, hb_consume(lstream[3], hseg));
-                            hb_heads += 1;
-                        }
-                        la.recs += (size_t)head_tiles * la.rec_words * 64u;
-                        la.n_tiles -= head_tiles;
-                        la.gen_base += head_tiles * 64u;
-                        if (grid > la.n_tiles) grid = la.n_tiles;
-                    }
-                    AvkKernelArgs fr = f;
-                    if (chains) fr.overflow_list = chain_seg[li].list, fr.overflow_count = chain_seg[li].count;
-                    launch_lane_class(ctx, grid, lds, lstream[li], fr, la);
-                    AVK_HIP(ctx, hipGetLastError());
-                }
-                if (chains)
-                    for (int li = 0; li < 2; ++li)
-                        if (lused[li]) AVK_HIP(ctx, hb_consume(lstream[li], chain_seg[li]));
-                for (int li = 0; li < N_LS; ++li) {
-                    if (!lused[li]) continue;
-                    if (!ljoined[li]) AVK_HIP(ctx, record_end(lend[li], ljoin[li], lchain[li]));
-                }
-                if (lused[1] && timed) { /* end of the one-call classes' launches */
-                    AVK_HIP(ctx, hipEventRecord(ctx->ev_lane, lstream[1]));
-                    ctx->ev_lane_valid = true;
-                }
-            }
-            /* the three launches are sized so that all their workgroups CAN be resident at once; with lane launches beside them they are not (a 40 KB LDS
-             * allocation waits for a contiguous hole) — nothing waits for a workgroup to start, late ones find the claimed part of the list empty */
-            uint32_t bulk = blocks > solo + 2 * hbm_solo + blocks / 4 ? blocks - solo - 2 * hbm_solo : blocks / 4; /* (a large class C launch: the bulk keeps a quarter of its workgroups) */
-            if (bulk < 1) bulk = 1;
-            if (bulk > blocks) bulk = blocks;
-            if (ctx->bulk_full_grid) bulk = blocks;
-            const uint32_t bulk_unfit = bulk; /* (the launch for the lanes' hand-backs below is sized by this) */
-            if (ctx->bulk_fit && !ctx->bulk_full_grid) {
-                const uint32_t fit = (a.n_work + waves_per_block - 1) / waves_per_block;
-                if (bulk > fit) bulk = fit < 1 ? 1 : fit;
-            }
-            a.n_waves = bulk * waves_per_block;
-            const uint64_t slice0 = a.tier[0].ws_bytes;
-            if (ctx->lds_bytes_per_wave >= 1024) { /* slices shrink to make room for the workgroup's tail */
-                a.tier[0].ws_bytes = avk::bulk_slice_bytes((uint64_t)ctx->lds_bytes_per_wave);
-                a.esc_bytes = (uint32_t)(waves_per_block * a.tier[0].ws_bytes);
-                a.esc_enabled = ctx->lds_escalation ? 1u : 0u;
-            }
-            hipLaunchKernelGGL(avk_region_kernel_lds, dim3(bulk), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ctx->stream, a);
-            if (use_fast) {
-                /* The regions the lanes handed over: small ones, so the LDS tier with its in-workgroup escalation — on the one-call lane
-                 * stream, behind the lane launches, BESIDE the bulk and the HBM launch of this stream.  What overflows there (rare) goes to a
-                 * list of its own, read by one more HBM launch at the very end (normally empty: 10 us). */
-                AVK_HIP(ctx, hipGetLastError());
-                const int di = lused[1] ? 1 : (lused[0] ? 0 : 2);
-                hipStream_t ds = lstream[di];
-                if (chains) { /* every list has been through avk_wide.inl on its own stream; what that left is for the caller's stream at the end of the step (below) */
-                    for (int li = 0; li < N_LS; ++li)
-                        if (lused[li]) chain_join[n_chain_join++] = lend[li];
-                } else {
-                    for (int li = 0; li < N_LS; ++li)
-                        if (li != di && lused[li] && !same_stream(lchain[li], lchain[di])) AVK_HIP(ctx, hipStreamWaitEvent(ds, ljoin[li], 0));
-                }
-                AvkKernelArgs d = a;
-                d.work_list = chains ? db->d_overflow7 : lists[2];
-                d.n_work_dev = db->d_counters + (chains ? AVK_CTR_WIDE_LANES_LEFT : avk_ctr_overflow_count(AVK_CTR_DEFERRED_LIST));
-                d.work_base = 0;
-                d.n_work = 0;
-                d.work_counter = db->d_counters + AVK_CTR_DEFERRED_CURSORS;
-                if (!chains && use_wide && ctx->wide_lane_handbacks) { /* small windows, whatever made the lanes give up: avk_wide.inl first, the LDS launch takes what is left */
-                    AvkKernelArgs w = d;
-                    w.work_counter = db->d_counters + AVK_CTR_WIDE_LANES_CURSOR;
-                    w.overflow_list = db->d_overflow7;
-                    w.overflow_count = db->d_counters + AVK_CTR_WIDE_LANES_LEFT;
-                    hipLaunchKernelGGL(avk_wide_kernel_lazy, dim3((uint32_t)ctx->wide_lazy_blocks), dim3(64), (size_t)ctx->wide_lds_bytes, ds, w, wa);
-                    AVK_HIP(ctx, hipGetLastError());
-                    d.work_list = db->d_overflow7;
-                    d.n_work_dev = db->d_counters + AVK_CTR_WIDE_LANES_LEFT;
-                }
-                uint32_t dblocks = bulk_unfit < (uint32_t)ctx->n_cus ? bulk_unfit : (uint32_t)ctx->n_cus; /* one workgroup per CU: the list is short */
-                d.n_waves = dblocks * waves_per_block;
-                d.overflow_list = lists[1];
-                d.overflow_count = db->d_counters + avk_ctr_overflow_count(1);
-                if (chains) {
-                    chain_d = d;
-                    chain_dblocks = dblocks;
-                } else {
-                    hipLaunchKernelGGL(avk_region_kernel_lds_lazy, dim3(dblocks), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds_bytes_per_wave, ds, d);
-                    AVK_HIP(ctx, hipGetLastError());
-                    AVK_HIP(ctx, record_end(END_DONE, ctx->ev_lane_done, lchain[di])); /* everything of the lane chains is behind this record */
-                }
-                deferred_pending = true;
-                early_pending = early_used;
-            }
-            a.tier[0].ws_bytes = slice0;
-        } else if (t == 1) { /* one workgroup per CU, four large slices */
-            a.hbm_ws = nullptr;
-            uint32_t b2 = (uint32_t)ctx->n_cus < blocks ? (uint32_t)ctx->n_cus : blocks;
-            a.n_waves = b2 * waves_per_block;
-            hipLaunchKernelGGL(avk_region_kernel_lds, dim3(b2), dim3(256), (size_t)waves_per_block * (size_t)ctx->lds2_bytes_per_wave, ctx->stream, a);
-        } else if (t == 2) {
-            a.hbm_ws = ctx->d_ws;
-            avk_big_slice_args(a, ctx->d_big, db->d_counters, big_slots);
-            a.n_waves = hbm_blocks * waves_per_block;
-            if (hbm_solo_pending && hbm_shared) { /* class C records the solo launch has not started yet: every wave of this launch helps (same ticket counter) */
-                a.extra_counter = db->d_counters + AVK_CTR_HBM_SOLO_TICKET;
-                a.extra_base = hbm_shared_base;
-                a.extra_n = db->plan.n_hbm - hbm_shared_base;
-            }
-            hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(hbm_blocks), dim3(256), 0, ctx->stream, a);
-        } else {
-            a.hbm_ws = ctx->d_big;
-            a.big_slots = 0;
-            a.n_waves = big_blocks * waves_per_block;
-            hipLaunchKernelGGL(avk_region_kernel_hbm, dim3(big_blocks), dim3(256), 0, ctx->stream, a);
-        }
-        AVK_HIP(ctx, hipGetLastError());
-        a.extra_counter = nullptr;
-        a.extra_n = 0;
-        if (first_launch && timed) AVK_HIP(ctx, hipEventRecord(ctx->evk1, ctx->stream));
-
-        if (t != last) {
-            list = lists[nlist];
-            count = db->d_counters + avk_ctr_overflow_count((uint32_t)nlist);
-            nlist += 1;
-        }
-    }
-    /* (no launch of an HBM tier's own — both tiers off — has flushed the chains: never with lanes today, use_fast asks for the tier-2 launch) */
-    if (deferred_pending && chains && !chains_flushed) AVK_HIP(ctx, flush_chains());
-    { /* the end of the step: every stream that still has a chain the caller's stream has not waited for */
-        int pending[5], k = 0;
-        if (solo_pending) pending[k++] = END_LDS_SOLO;
-        if (hbm_solo_pending) pending[k++] = END_CLASS_C;
-        if (wide_x_pending) pending[k++] = END_NOT_WIDE;
-        if (deferred_pending && !chains) pending[k++] = END_DONE;
-        if (deferred_pending && early_pending) pending[k++] = END_EARLY;
-        AVK_HIP(ctx, join(pending, k));
-    }
-    ctx->last_step_chains = chains;
-    if (deferred_pending) { /* the lane chains (lane launches, then the handed-back regions) have joined; what even the escalation could not hold */
-        AvkKernelArgs h = avk_list_reader_args(a, lists[1], db->d_counters + avk_ctr_overflow_count(1), db->d_counters + AVK_CTR_LAST_CURSOR);
-        h.pass_tier = 2;
-        h.high_priority = 0;
-        h.hbm_ws = ctx->d_ws;
-        avk_big_slice_args(h, ctx->d_big, db->d_counters, big_slots);
-        const uint32_t hb = hbm_blocks < 64 ? hbm_blocks : 64;
-        h.n_waves = hb * waves_per_block;
-        hipLaunchKernelGGL(avk_region_kernel_hbm_lazy, dim3(hb), dim3(256), 0, ctx->stream, h);
-        AVK_HIP(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(avk_tally_reduce, dim3((AVK_TALLY_STRIDE + 63) / 64), dim3(64), 0, ctx->stream, db->d_partials, db->d_tally,
-                       (uint64_t *)tally_dev, db->d_counters, (unsigned)AVK_N_COUNTERS, ctx->accumulate_tally ? 1u : 0u);
-    AVK_HIP(ctx, hipGetLastError());
-    db->scratch_clean = true;
-    db->last_cfg = *cfg;
-    db->last_mode = mode;
-    db->has_run = true;
-    db->bp_valid = spec.emit_bp && mode == 0 && db->d_bp != nullptr;
-    if (timed) AVK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    ctx->ev_valid = timed;
-    return 0;
-}
+/* the solver step: Step, run_internal, the lane launches' helpers, ensure_kernel_attrs, ensure_pair_table */
+#include "avk_step.inl"
 
 int avk_compare_resident(avk_ctx *ctx, avk_dev_batch *db, const avk_compare_config *cfg, void *tally_dev) {
     return ctx ? run_internal(ctx, call_spec(ctx), db, cfg, tally_dev, 0) : AVK_E_ARG;
@@ -3347,31 +2435,27 @@ int avk_ctx_warmup(avk_ctx *ctx, uint64_t n_regions_hint, uint64_t n_variants_hi
     hipLaunchKernelGGL(avk_tally_reduce, dim3((AVK_TALLY_STRIDE + 63) / 64), dim3(64), 0, ctx->stream, parts, parts + (size_t)AVK_TALLY_STRIDE * AVK_TALLY_COPIES, (uint64_t *)nullptr,
                        (uint32_t *)(parts + (size_t)AVK_TALLY_STRIDE * (AVK_TALLY_COPIES + 1)), (unsigned)AVK_N_COUNTERS, 0u);
     AVK_HIP(ctx, hipGetLastError());
-    if (!ctx->lane_attr_set) {
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_lane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        AVK_HIP(ctx, hipFuncSetAttribute((const void *)avk_quad_kernel_wide_regs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->lane_attr_set = true;
-    }
+    rc = ensure_kernel_attrs(ctx);
+    if (rc) return rc;
     if (ctx->lane_kernel && ctx->lane_pairs) {
         rc = ensure_pair_table(ctx, 50, ctx->stream);
         if (rc) return rc;
     }
     if (n_regions_hint >= 65536 && ctx->ws_bytes_per_wave > 0) {
-        /* The workspaces run_internal sizes for a batch of a genome's size, allocated HERE, on the thread that runs beside the caller's parsing: hipMalloc of the
+        /* The workspaces the step (avk_step_geometry.h) sizes for a batch of a genome's size, allocated HERE, on the thread that runs beside the caller's parsing: hipMalloc of the
          * 4.8 + 2.1 GB they were until round 5 took 0.39 s (device memory is scrubbed when it is handed out).  Round 4 took and released as many bytes instead, counting on memory the process has
          * held once to come back at once: it does in two runs of three — in the third the first call's own hipMalloc paid the 0.39 s inside the tool's solve stage
          * (profiles/r05_first_solve.txt: "avk run: workspaces (.. allocated now ..) 387 ms"). */
-        const size_t main_blocks = (size_t)ctx->n_cus * 3u < AVK_HBM_BLOCKS_BESIDE_LANES ? (size_t)ctx->n_cus * 3u : (size_t)AVK_HBM_BLOCKS_BESIDE_LANES; /* (a genome has lane launches) */
-        const size_t waves = (main_blocks + (size_t)(ctx->hbm_solo_blocks > 0 ? ctx->hbm_solo_blocks : 128) + (size_t)(ctx->hbm_early_blocks > 0 ? ctx->hbm_early_blocks : 64)) * 4u;
-        const size_t ws_need = waves * (size_t)ctx->ws_bytes_per_wave;
-        if (ws_need > ctx->ws_alloc && (double)ws_need <= (double)ctx->ws_budget_bytes) {
+        /* (a genome has lane launches, which leave the other kernels a few thousand regions) */
+        const AvkStepGeometryIn gin = {ctx->n_cus, ctx->waves_per_cu, 16384, 0, true, ctx->ws_bytes_per_wave, ctx->ws_budget_bytes, ctx->hbm_solo_blocks, ctx->hbm_early_blocks, ctx->big_waves, ctx->big_ws_bytes};
+        const AvkStepGeometry geo = avk_step_geometry(gin);
+        const size_t ws_need = geo.ws_need, big_need = geo.big_need;
+        if (ws_need > ctx->ws_alloc && !geo.shrunk) { /* (slices past the budget: the step that has them sizes them) */
             if (ctx->d_ws) (void)hipFree(ctx->d_ws);
             ctx->d_ws = nullptr, ctx->ws_alloc = 0;
             if (hipMalloc((void **)&ctx->d_ws, ws_need + 256) == hipSuccess) ctx->ws_alloc = ws_need;
             else ctx->d_ws = nullptr, (void)hipGetLastError(); /* (the first call asks again, and reports) */
         }
-        const size_t big_need = (size_t)((ctx->big_waves + 3) / 4) * 4u * (size_t)ctx->big_ws_bytes;
         if (ctx->big_ws_bytes > 0 && big_need > ctx->big_alloc) {
             if (ctx->d_big) (void)hipFree(ctx->d_big);
             ctx->d_big = nullptr, ctx->big_alloc = 0;
@@ -3912,13 +2996,11 @@ static void packed_timeline_print(avk_ctx *ctx) {
     else
         (void)hipGetLastError();
     /* where each chain of the launch graph ended, from the first solver launch (events of this call only when the batch used the chain) */
-    const struct { const char *what; hipEvent_t ev; } chains[] = {{"LDS solo", ctx->ev_join}, {"HBM solo", ctx->ev_join2}, {"wide", ctx->ev_wide}, {"lane stream 1", ctx->ev_lane_join},
-        {"lane stream 2", ctx->ev_lane_join2}, {"lane stream 3", ctx->ev_lane_join3}, {"lane stream 4", ctx->ev_lane_join4}, {"early hand-backs", ctx->ev_lane_early},
-        {"hand-back launches", ctx->last_step_chains ? nullptr : ctx->ev_lane_done}}; /* (a step with hand-back chains records no such end) */
     fprintf(stderr, "avk compare packed, chains end (ms after the first solver launch):");
-    for (const auto &c : chains) {
+    for (int id = 0; id < AVK_N_ENDS; ++id) {
         float t = 0;
-        if (c.ev && hipEventElapsedTime(&t, ctx->ev0, c.ev) == hipSuccess) fprintf(stderr, " %s %.3f;", c.what, t);
+        const bool none = id == AVK_END_DONE && ctx->last_step_chains; /* (a step with hand-back chains records no such end) */
+        if (!none && hipEventElapsedTime(&t, ctx->ev0, ctx->ev_end[id]) == hipSuccess) fprintf(stderr, " %s %.3f;", AVK_STEP_END_NAME[id], t);
         else (void)hipGetLastError();
     }
     fprintf(stderr, " all %.3f\n", c5 - c4);

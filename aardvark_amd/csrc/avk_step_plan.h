@@ -1,11 +1,11 @@
-/* The launch chains of a solver step (run_internal) and the stream each of them is queued on.
+/* The launch chains of a solver step (Step, avk_step.inl) and the stream each of them is queued on.
  *
- * A chain is a run of launches that follow each other in stream order; chains run beside each other.  run_internal names chains only; the plan says which of the
+ * A chain is a run of launches that follow each other in stream order; chains run beside each other.  The step names chains only; the plan says which of the
  * context's streams ("slots") a chain is queued on.  Two plans:
  *
  *   wide    one stream per chain (slot == chain).  For processes with eight or more hardware queues (GPU_MAX_HW_QUEUES): every chain has a queue of its own.
  *   folded  the caller's stream and three more.  For processes with fewer queues, where streams that share a queue run in turn anyway and WHICH of them share one
- *           is left to the runtime: here whole chains are queued one behind the other on a stream, in the order run_internal queues them, and the events that
+ *           is left to the runtime: here whole chains are queued one behind the other on a stream, in the order the step queues them, and the events that
  *           forked and joined two chains of one stream are dropped (stream order does their work).
  *
  * Plain C++, no HIP types: tests/native/step_plan_check.cpp compiles this header for the CPU. */
@@ -24,6 +24,23 @@ enum AvkStepChain {
     AVK_N_CHAINS
 };
 
+/* The ends of the chains: each is an event (avk_ctx::ev_end) recorded behind the last launch of a chain — or, for the three-call class, behind its lane launch
+ * (AVK_END_LANE2) and again behind the launches for what it handed back (AVK_END_EARLY).  The caller's stream waits for them; AVK_TIMING prints when each fired. */
+enum AvkStepEnd {
+    AVK_END_LDS_SOLO,
+    AVK_END_CLASS_C,
+    AVK_END_NOT_WIDE,
+    AVK_END_LANE0, /* the lane chains, in the order of AvkStepChain: two-call, one-call, three-call, the heads' hand-backs */
+    AVK_END_LANE1,
+    AVK_END_LANE2,
+    AVK_END_LANE3,
+    AVK_END_EARLY,
+    AVK_END_DONE, /* a step without hand-back chains: the launch for everything the lanes handed back */
+    AVK_N_ENDS
+};
+static const char *const AVK_STEP_END_NAME[AVK_N_ENDS] = {"LDS solo",      "HBM solo",      "wide",           "lane stream 1",     "lane stream 2",
+                                                          "lane stream 3", "lane stream 4", "early hand-backs", "hand-back launches"};
+
 enum { AVK_STEP_SLOTS_FOLDED = 4, AVK_STEP_QUEUES_WIDE = 8 /* from this many hardware queues on: a stream per chain */ };
 
 struct AvkStepPlan {
@@ -31,7 +48,7 @@ struct AvkStepPlan {
     int n_slots;            /* slots in use: AVK_N_CHAINS or AVK_STEP_SLOTS_FOLDED */
 };
 
-/* chain -> slot of the folded plan.  Queue order on a slot is run_internal's: the solo chains ahead of the lane chains (class C, then the one-call classes, ahead of the
+/* chain -> slot of the folded plan.  Queue order on a slot is the step's: the solo chains ahead of the lane chains (class C, then the one-call classes, ahead of the
  * bulk on the caller's stream; the LDS solo launch ahead of the two-call classes; the long launch of the records that are not the wide kernel's ahead of the heads'
  * hand-backs, which wait for their head anyway).  By the chains' durations in a four-queue trace this is the best split into four (2.46 ms on the longest stream);
  * profiles/step_four_queues.txt has the trace and the three assignments that were measured. */
