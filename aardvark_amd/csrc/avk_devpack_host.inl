@@ -1,5 +1,7 @@
 /*
  * avk_devpack_host.inl — the kernels around avk_devpack.inl and the host side of a device-packed batch.  Included by avk_host.hip.
+ * Here: the kernels, the context's buffer pool, the copies in and out (copy_in, the copy kernel, the engines' rate check), the strata launches and the download.
+ * The upload itself is avk_upload.inl (its forms and argument checks: avk_upload_forms.h), included right behind this file.
  *
  * The host's part of avk_batch_upload / avk_compare_batch is now: queue the copies of the caller's arrays (straight from the caller's memory
  * when it is pinned — avk_host_alloc —, through a pinned bounce buffer filled by the host threads when it is not), queue a dozen
@@ -967,13 +969,6 @@ struct PackedOnDevice {
     uint64_t *lab_off;
     uint32_t *lab_idx;
 };
-/* an avk_packed_escapes that lists something, with every array it needs */
-static inline bool esc_present(const avk_packed_escapes *e) { return e && (e->n_esc_regions || e->n_esc_slots || e->n_esc_calls); }
-static inline bool esc_arrays_ok(const avk_packed_escapes *e) {
-    if (!esc_present(e)) return true;
-    return (!e->n_esc_regions || (e->esc_region && e->esc_len)) && (!e->n_esc_slots || (e->esc_slot && e->esc_cnt)) &&
-           (!e->n_esc_calls || (e->esc_call && e->esc_rel_pos && e->esc_a0_len && e->esc_a1_len));
-}
 /* host: the narrow per-entry fields of a packed batch with its escapes applied — for the host-side utilities (shards, merge counts, the merge path's host
  * fallback).  cnt[] has one entry per count slot: 2r / 2r + 1 = t_cnt / q_cnt of region r (compare form, cnt_b given), or in_cnt as it is (multi form, cnt_b NULL).
  * false: a list is not ascending or names an entry outside the batch, or a listed entry's narrow field is not 0 (the rule of avk_packed_escapes; the device refuses
@@ -1012,699 +1007,6 @@ static bool packed_widen_host(const uint16_t *len, uint64_t n, const uint8_t *cn
         w.rel[v] = esc->esc_rel_pos[p], w.a0[v] = esc->esc_a0_len[p], w.a1[v] = esc->esc_a1_len[p];
     }
     return true;
-}
-/* allele offsets and lengths of a packed batch's calls on the host, escapes honoured (only made for the few calls whose edit distance is left to the host) */
-static void packed_host_alleles(const uint8_t *l0, const uint8_t *l1, uint64_t nv, const avk_packed_escapes *esc, std::vector<uint64_t> &aoff, std::vector<uint32_t> &w0,
-                                std::vector<uint32_t> &w1) {
-    aoff.resize(nv + 1), w0.resize(nv + 1), w1.resize(nv + 1);
-    for (uint64_t v = 0; v < nv; ++v) w0[v] = l0[v], w1[v] = l1[v];
-    if (esc_present(esc))
-        for (uint64_t p = 0; p < esc->n_esc_calls; ++p) {
-            const uint64_t v = esc->esc_call[p] - esc->first_call;
-            if (v < nv) w0[v] = esc->esc_a0_len[p], w1[v] = esc->esc_a1_len[p];
-        }
-    uint64_t run = 0;
-    for (uint64_t v = 0; v < nv; ++v) aoff[v] = run, run += (uint64_t)w0[v] + w1[v];
-    aoff[nv] = run;
-}
-
-/* b: the batch in the wide form, or NULL and cb: the batch in the compact form (avk_compact_batch: half the bytes over PCIe, widened on the device) */
-/* mb: a batch of MultiRegions (the merge path): one region per input pair is made on the device (dp_expand_pairs) */
-/* (pm: the packed form of a multi batch; `mb` then only carries n_regions, n_inputs, n_variants, allele_bytes and allele_bytes_len) */
-static int upload_device_packed(avk_ctx *ctx, const CallSpec &spec, const avk_region_batch *b, const avk_compact_batch *cb, bool pairs_mode, avk_dev_batch **out, const avk_multi_batch *mb = nullptr,
-                                const avk_packed_batch *pk = nullptr, const avk_packed_multi_batch *pm = nullptr, const PackedOnDevice *pre = nullptr,
-                                const avk_packed_escapes *esc = nullptr) {
-    const bool has_esc = (pk || pm) && esc_present(esc);
-    if (has_esc && !esc_arrays_ok(esc)) return fail(ctx, AVK_E_ARG, "escape arrays missing");
-    const uint32_t mk = mb ? mb->n_inputs : 0, mppr = mk * (mk - (mk ? 1u : 0u)) / 2;
-    const uint64_t n = pk ? pk->n_regions : (b ? b->n_regions : (cb ? cb->n_regions : mb->n_regions * mppr)), nv = pk ? pk->n_variants : (b ? b->n_variants : (cb ? cb->n_variants : mb->n_variants)),
-                   alen = pk ? pk->allele_bytes_len : (b ? b->allele_bytes_len : (cb ? cb->allele_bytes_len : mb->allele_bytes_len));
-    if (pk && n && (!pk->start || !pk->len || !pk->t_cnt || !pk->q_cnt)) return fail(ctx, AVK_E_ARG, "region arrays missing");
-    if (pk && nv && (!pk->var_rel_pos || !pk->var_type_zyg || !pk->a0_len || !pk->a1_len || !pk->allele_bytes)) return fail(ctx, AVK_E_ARG, "variant arrays missing");
-    if (pm && pm->n_regions && (!pm->start || !pm->len || !pm->in_cnt)) return fail(ctx, AVK_E_ARG, "region arrays missing");
-    if (pm && nv && (!pm->var_rel_pos || !pm->var_type_zyg || !pm->a0_len || !pm->a1_len || !pm->allele_bytes)) return fail(ctx, AVK_E_ARG, "variant arrays missing");
-    if (mb && !pm && mb->n_regions && (!mb->start || !mb->end || !mb->in_off || !mb->in_cnt)) return fail(ctx, AVK_E_ARG, "region arrays missing");
-    if (mb && !pm && nv && (!mb->var_pos || !mb->var_type || !mb->var_zyg || !mb->a0_off || !mb->a0_len || !mb->a1_off || !mb->a1_len || !mb->allele_bytes)) return fail(ctx, AVK_E_ARG, "variant arrays missing");
-    if (n > 0x7FFFFFFFull || nv > 0x7FFFFFFFull) return fail(ctx, AVK_E_ARG, "batch too large (more than 2^31 regions or variants); split it");
-    if (b && n && (!b->start || !b->end || !b->t_off || !b->t_cnt || !b->q_off || !b->q_cnt)) return fail(ctx, AVK_E_ARG, "region arrays missing");
-    if (b && nv && (!b->var_pos || !b->var_type || !b->var_zyg || !b->a0_off || !b->a0_len || !b->a1_off || !b->a1_len || !b->allele_bytes)) return fail(ctx, AVK_E_ARG, "variant arrays missing");
-    if (cb && n && (!cb->start || !cb->len || !cb->v_off || !cb->t_cnt || !cb->q_cnt)) return fail(ctx, AVK_E_ARG, "region arrays missing");
-    if (cb && nv && (!cb->var_pos || !cb->var_type_zyg || !cb->a_off || !cb->a0_len || !cb->a1_len || !cb->allele_bytes)) return fail(ctx, AVK_E_ARG, "variant arrays missing");
-    if (cb && alen > 0xFFFFFFFFull) return fail(ctx, AVK_E_ARG, "the compact form holds at most 2^32 allele bytes");
-    const bool has_contig = pm ? pm->contig_idx != nullptr : (pk ? pk->contig_idx != nullptr : (b ? b->contig_idx != nullptr : (cb ? cb->contig_idx != nullptr : mb->contig_idx != nullptr))),
-               has_raw = pm ? pm->var_raw_space != nullptr : (pk ? pk->var_raw_space != nullptr : (b ? b->var_raw_space != nullptr : (cb ? cb->var_raw_space != nullptr : mb->var_raw_space != nullptr)));
-    const uint8_t *host_alleles = pk ? pk->allele_bytes : (b ? b->allele_bytes : (cb ? cb->allele_bytes : mb->allele_bytes));
-    const bool timing = getenv("AVK_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-    const auto t_start = now();
-    hipStream_t s = spec.up_stream ? spec.up_stream : ctx->stream; /* (the asynchronous boundary packs on a stream of its own, beside the solve of the batch before) */
-    uint64_t *pk_totals = nullptr; /* packed form: device words {sum of the call counts, sum of the allele lengths} */
-    avk_dev_batch *db = new avk_dev_batch();
-    db->dev_packed = true;
-    db->n_regions = n;
-    db->n_variants_host = nv;
-    std::vector<void *> temps; /* released (to the pool) at the end of the upload */
-    int rc = 0;
-    auto tmp = [&](size_t bytes) -> void * {
-        void *p = nullptr;
-        if (!rc) rc = pool_alloc(ctx, &p, bytes);
-        if (p) temps.push_back(p);
-        return p;
-    };
-    auto kept = [&](size_t bytes) -> void * {
-        void *p = nullptr;
-        if (!rc) rc = pool_alloc(ctx, &p, bytes);
-        if (p) db->pooled.push_back(p);
-        return p;
-    };
-    auto bail = [&](int code) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamSynchronize((spec.up_side ? spec.up_side : ctx->lane_stream4)); /* (the side stream of the upload: prefix sums, widening, the cleared scratch) */
-        for (void *p : temps) pool_release(ctx, p);
-        release_pooled(ctx, db);
-        delete db;
-        return code;
-    };
-    /* the caller's arrays in HBM; the four that dp_unpack reads after the solve stay with the batch */
-    dpk::DpArgs a;
-    memset(&a, 0, sizeof(a));
-    /* (the inputs and the packer's intermediates stay with the batch: region records of lane regions are written when a launch needs them) */
-    /* a compare batch in the packed form is read from the packed arrays themselves (DpIn::pk_*, round 6): no wide arrays, no widening pass */
-    const bool packed_src = pk != nullptr && ctx->packed_source && !has_esc; /* (a batch with escapes is widened first: dp_widen_packed_esc) */
-    bool early_variant = false, variant_done = false; /* dp_variant queued on the side stream of a packed upload, under its copies */
-    avk::pc::ChunkPlan chunk_plan = avk::pc::plan_chunks(0, 0, 0, 0); /* k > 0: the chunked route (option pack_chunks): the region pass runs on the side stream, group by group */
-    bool region_done = false;     /* ... and has been queued there: the first round of region_passes launches none */
-    bool queue_early = false;     /* the side stream's steps are queued from inside copy_in (option pack_queue_early, and always on the chunked route) */
-    ctx->last_region_launches = 0, ctx->tl_region_valid = false;
-    auto tmp_or_kept = [&](size_t bytes) -> void * { return kept(bytes); };
-    auto wide = [&](size_t bytes) -> void * { return packed_src ? nullptr : kept(bytes); };
-    uint64_t *d_start = (uint64_t *)wide((n + 1) * 8), *d_end = (uint64_t *)wide((n + 1) * 8);
-    db->d_in_t_off = (uint64_t *)wide((n + 1) * 8), db->d_in_q_off = (uint64_t *)wide((n + 1) * 8);
-    db->d_in_t_cnt = (uint32_t *)wide((n + 1) * 4), db->d_in_q_cnt = (uint32_t *)wide((n + 1) * 4);
-    uint32_t *d_contig = has_contig ? (uint32_t *)wide((n + 1) * 4) : nullptr;
-    uint64_t *d_pos = (uint64_t *)wide((nv + 1) * 8), *d_a0o = (uint64_t *)wide((nv + 1) * 8), *d_a1o = (uint64_t *)wide((nv + 1) * 8);
-    uint32_t *d_a0l = (uint32_t *)wide((nv + 1) * 4), *d_a1l = (uint32_t *)wide((nv + 1) * 4);
-    uint32_t *d_raw = has_raw ? (pre ? pre->raw : (uint32_t *)tmp_or_kept((nv + 1) * 4)) : nullptr;
-    uint8_t *d_type = (uint8_t *)wide(nv + 16), *d_zyg = (uint8_t *)wide(nv + 16), *d_alleles = pre ? pre->alleles : (uint8_t *)tmp_or_kept(alen + 16);
-    /* intermediates */
-    const uint32_t n_blocks = (uint32_t)((n + 255) / 256);
-    a.vinfo = (dpk::DpVarInfo *)kept((nv + 1) * sizeof(dpk::DpVarInfo));
-    a.rinfo = (dpk::DpRegionInfo *)kept((n + 1) * sizeof(dpk::DpRegionInfo));
-    a.st = (dpk::DpState *)kept(sizeof(dpk::DpState));
-    a.pending = (uint32_t *)tmp((nv + 1) * 4);
-    a.slots = (dpk::DpSlot *)tmp((nv + 1) * sizeof(dpk::DpSlot));
-    a.bucket16 = (uint16_t *)tmp((n + 16) * 2);
-    db->d_voff = (uint32_t *)kept((n + 1) * 4);
-    a.v_off = db->d_voff;
-    a.blob_off8 = (uint32_t *)kept((n + 1) * 4);
-    a.seq_off = (uint64_t *)kept((n + 1) * 8);
-    db->d_bp_off = (uint32_t *)kept((n + 2) * 4);
-    a.bp_off = db->d_bp_off;
-    if (db->d_bp_off) (void)hipMemsetAsync(db->d_bp_off, 0, 8, s); /* (an empty batch: bp_off[0] = 0) */
-    a.order = (uint32_t *)kept((n + 1) * 4);
-    a.big_list = (uint32_t *)kept((n + 1) * 4);
-    uint64_t *d_block_sums = (uint64_t *)tmp(((size_t)n_blocks + 1) * AVK_DP_BS * 8);
-    if (!ctx->h_dpstate && !rc) {
-        hipError_t e = hipHostMalloc((void **)&ctx->h_dpstate, sizeof(dpk::DpState) + 32, hipHostMallocDefault);
-        if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "pinned state block: %s", hipGetErrorString(e));
-    }
-    if (!ctx->d_contig_tab && !rc) rc = fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
-    if (rc) return bail(rc);
-    const auto t_alloc = now();
-    auto mark = [&](int k) { /* AVK_TIMING: a mark of the call's device timeline on the context's stream */
-        if (!timing) return;
-        if (!ctx->ev_tl[k] && hipEventCreate(&ctx->ev_tl[k]) != hipSuccess) {
-            ctx->ev_tl[k] = nullptr;
-            (void)hipGetLastError();
-            return;
-        }
-        (void)hipEventRecord(ctx->ev_tl[k], s);
-    };
-    mark(0);
-    /* the escape lists of a packed batch in HBM (a staging slot's, or copied with the batch's arrays), and the two exclusive sums over their values */
-    dpk::DpEsc de;
-    memset(&de, 0, sizeof(de));
-    std::vector<CopySeg> esc_segs;
-    if (has_esc) {
-        const uint64_t er = esc->n_esc_regions, es = esc->n_esc_slots, ec = esc->n_esc_calls;
-        uint64_t *x_region = pre ? pre->esc_region : (uint64_t *)tmp((er + 1) * 8), *x_slot = pre ? pre->esc_slot : (uint64_t *)tmp((es + 1) * 8),
-                 *x_call = pre ? pre->esc_call : (uint64_t *)tmp((ec + 1) * 8);
-        uint32_t *x_len = pre ? pre->esc_len : (uint32_t *)tmp((er + 1) * 4), *x_cnt = pre ? pre->esc_cnt : (uint32_t *)tmp((es + 1) * 4), *x_rel = pre ? pre->esc_rel : (uint32_t *)tmp((ec + 1) * 4),
-                 *x_a0 = pre ? pre->esc_a0 : (uint32_t *)tmp((ec + 1) * 4), *x_a1 = pre ? pre->esc_a1 : (uint32_t *)tmp((ec + 1) * 4);
-        de.region = x_region, de.slot = x_slot, de.call = x_call, de.len = x_len, de.cnt = x_cnt, de.rel = x_rel, de.a0 = x_a0, de.a1 = x_a1;
-        de.cnt_before = (uint64_t *)tmp((es + 1) * 8), de.bytes_before = (uint64_t *)tmp((ec + 1) * 8);
-        de.n_regions = er, de.n_slots = es, de.n_calls = ec, de.first_region = esc->first_region, de.first_slot = esc->first_slot, de.first_call = esc->first_call;
-        if (rc) return bail(rc);
-        if (!pre)
-            esc_segs = {{esc->esc_region, x_region, er * 8}, {esc->esc_len, x_len, er * 4}, {esc->esc_slot, x_slot, es * 8}, {esc->esc_cnt, x_cnt, es * 4}, {esc->esc_call, x_call, ec * 8},
-                        {esc->esc_rel_pos, x_rel, ec * 4}, {esc->esc_a0_len, x_a0, ec * 4}, {esc->esc_a1_len, x_a1, ec * 4}};
-    }
-    /* (side stream, behind the sums over the narrow arrays and the lists' copies) the lists are checked and summed; totals[0..1] gain what the narrow sums lack, totals[2] is the error word */
-    auto esc_scans = [&](hipStream_t side, uint64_t *totals, uint64_t n_slots_all, uint64_t n_calls_all, uint64_t n_regions_all, const dpk::DpEscNarrow &z_slot,
-                         const dpk::DpEscNarrow &z_call, const dpk::DpEscNarrow &z_region) {
-        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.slot, de.cnt, (const uint32_t *)nullptr, de.n_slots, de.first_slot, de.first_slot + n_slots_all,
-                           z_slot, (uint64_t *)de.cnt_before, totals, totals + 2);
-        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.call, de.a0, de.a1, de.n_calls, de.first_call, de.first_call + n_calls_all, z_call,
-                           (uint64_t *)de.bytes_before, totals + 1, totals + 2);
-        hipLaunchKernelGGL(avk_esc_scan_kernel, dim3(1), dim3(1024), 0, side, de.region, (const uint32_t *)nullptr, (const uint32_t *)nullptr, de.n_regions, de.first_region,
-                           de.first_region + n_regions_all, z_region, (uint64_t *)nullptr, (uint64_t *)nullptr, totals + 2);
-    };
-    auto fill_args = [&] { /* the caller's arrays (the wide ones: NULL for a batch read from its packed source) and the context's options, as the packing kernels take them */
-        a.in.contig_idx = d_contig, a.in.start = d_start, a.in.end = d_end, a.in.t_off = db->d_in_t_off, a.in.q_off = db->d_in_q_off, a.in.t_cnt = db->d_in_t_cnt,
-        a.in.q_cnt = db->d_in_q_cnt, a.in.var_pos = d_pos, a.in.var_type = d_type, a.in.var_zyg = d_zyg, a.in.var_raw = d_raw, a.in.a0_off = d_a0o, a.in.a1_off = d_a1o,
-        a.in.a0_len = d_a0l, a.in.a1_len = d_a1l, a.in.alleles = d_alleles, a.in.n_regions = n, a.in.n_variants = nv, a.in.alleles_len = alen,
-        a.in.contig_base = ctx->d_contig_tab, a.in.contig_len = ctx->d_contig_tab + ctx->contig_len.size(), a.in.n_contigs = (uint32_t)ctx->contig_len.size(),
-        a.in.pairs_mode = pairs_mode ? 1u : 0u;
-        const bool lanes = ctx->lane_kernel && ctx->use_packed_reference && ctx->d_ref2b;
-        a.opt.tier0_bytes = avk::bulk_slice_bytes((uint64_t)ctx->lds_bytes_per_wave), a.opt.tier0_ed_cap = (uint32_t)ctx->lds_ed_cap, a.opt.tier1_bytes = (uint64_t)ctx->lds2_bytes_per_wave,
-        a.opt.tier1_ed_cap = (uint32_t)ctx->lds2_ed_cap, a.opt.solo_min_variants = pairs_mode && !ctx->pair_classes ? 0u : (uint32_t)ctx->solo_min_variants, a.opt.max_branch = 50,
-        a.opt.class_c_nodes_x2 = (uint32_t)ctx->class_c_nodes_x2, a.opt.lane_min_regions = lanes ? (uint64_t)ctx->lane_min_regions : 0xFFFFFFFFull,
-        a.opt.lane_max_calls = (uint32_t)ctx->lane_max_calls, a.opt.lane_min_batch = (uint64_t)ctx->lane_min_batch, a.opt.lane_max_est = (uint32_t)ctx->lane_max_est;
-        a.opt.stripe_w = ctx->lane_stripe ? (uint32_t)ctx->lane_head_width : 0u;
-        a.opt.lane_pairs = ctx->lane_pairs ? 1u : 0u;
-        a.opt.head_est = (uint32_t)ctx->lane_head_est, a.opt.het_min = (uint32_t)ctx->het_search_min;
-        a.opt.class_c_below = (uint64_t)ctx->class_c_below;
-    };
-    if (pk) { /* the packed arrays as they are, two prefix sums for the offsets they leave out, one kernel that writes the wide arrays */
-        /* (the packed arrays stay with the batch when they are what the packer and the later record writers read; a staging slot's stay with its ticket) */
-        auto src = [&](size_t bytes) -> void * { return packed_src ? kept(bytes) : tmp(bytes); };
-        uint16_t *p_contig = has_contig ? (pre ? pre->contig : (uint16_t *)src((n + 1) * 2)) : nullptr, *p_len = pre ? pre->len : (uint16_t *)src((n + 1) * 2),
-                 *p_rel = pre ? pre->rel_pos : (uint16_t *)src((nv + 1) * 2);
-        uint32_t *p_start = pre ? pre->start : (uint32_t *)src((n + 1) * 4);
-        uint8_t *p_tc = pre ? pre->t_cnt : (uint8_t *)src(n + 16), *p_qc = pre ? pre->q_cnt : (uint8_t *)src(n + 16), *p_tz = pre ? pre->var_type_zyg : (uint8_t *)src(nv + 16),
-                *p_a0 = pre ? pre->a0_len : (uint8_t *)src(nv + 16), *p_a1 = pre ? pre->a1_len : (uint8_t *)src(nv + 16);
-        const uint32_t nb_r = (uint32_t)((n + AVK_PS_BLOCK - 1) / AVK_PS_BLOCK), nb_v = (uint32_t)((nv + AVK_PS_BLOCK - 1) / AVK_PS_BLOCK);
-        uint64_t *p_voff = (uint64_t *)src((n + 1) * 8), *p_aoff = (uint64_t *)src((nv + 1) * 8), *p_sums = (uint64_t *)tmp(((size_t)nb_r + nb_v + 4) * 8);
-        if (rc) return bail(rc);
-        /* All copies on the context's stream, counts and lengths first; the two prefix sums (which need nothing else) and the widening kernel (everything but the
-         * allele bytes) run on a stream of their own beside the copies that follow: dp_variant, the first kernel that needs every byte, starts 0.24 ms earlier.
-         * (The copies themselves stay on ONE stream: a large copy queued on a second stream now and then blocks the host for 7 to 9 ms inside hipMemcpyAsync —
-         * the runtime bringing up another copy engine — which made one call in fifty 16 ms long.) */
-        hipStream_t side = (spec.up_side ? spec.up_side : ctx->lane_stream4);
-        auto side_fail = [&](int code) { /* nothing of this call may still be in flight on the side stream when its buffers go back */
-            (void)hipStreamSynchronize(side);
-            return bail(code);
-        };
-        /* The chunked route (option pack_chunks) is for the synchronous call on pinned arrays that is read from its packed source and copies by engine: a staging slot's
-         * arrays are there already, a batch with escapes is widened first, pageable arrays cross piece by piece through the bounce buffer, and avk_copy_kernel occupies
-         * the compute units the region pass would run on.  Everything else keeps the old order, launch for launch. */
-        auto all_pinned = [&] {
-            return is_pinned(pk->t_cnt, n) && is_pinned(pk->q_cnt, n) && is_pinned(pk->a0_len, nv) && is_pinned(pk->a1_len, nv) && is_pinned(pk->allele_bytes, alen) &&
-                   is_pinned(pk->start, n * 4) && is_pinned(pk->len, n * 2) && is_pinned(pk->contig_idx, n * 2) && is_pinned(pk->var_rel_pos, nv * 2) &&
-                   is_pinned(pk->var_type_zyg, nv) && is_pinned(pk->var_raw_space, nv * 4);
-        };
-        const bool eligible = (ctx->pack_chunks > 0 || ctx->pack_queue_early) && packed_src && nv && !pre && !spec.up_stream && !copies_by_kernel(ctx) && all_pinned();
-        queue_early = eligible;
-        if (eligible && ctx->pack_chunks > 0) {
-            chunk_plan = avk::pc::plan_chunks(n, nv, ctx->pack_chunks, (uint64_t)ctx->pack_chunk_floor);
-            for (uint32_t j = 0; j + 1 < chunk_plan.k && !rc; ++j)
-                if (!ctx->ev_pack_group[j] && hipEventCreateWithFlags(&ctx->ev_pack_group[j], hipEventDisableTiming) != hipSuccess) {
-                    ctx->ev_pack_group[j] = nullptr;
-                    rc = fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(hipGetLastError()));
-                }
-            if (rc) return bail(rc);
-        }
-        auto queue_sums = [&]() -> hipError_t { /* the two prefix sums, on the side stream behind the counts and lengths */
-            hipError_t ec = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0); /* (also orders the side stream behind everything queued on the context's stream before) */
-            if (ec != hipSuccess) return ec;
-            if (has_esc && hipMemsetAsync(p_sums + nb_r + nb_v, 0, 32, side) != hipSuccess) return hipGetLastError();
-            if (n) {
-                hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_tc, (const uint8_t *)p_qc, n, p_sums);
-                hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums, nb_r, p_sums + nb_r + nb_v);
-                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_tc, (const uint8_t *)p_qc, n, (const uint64_t *)p_sums, p_voff);
-            }
-            if (nv) {
-                hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, p_sums + nb_r);
-                hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums + nb_r, nb_v, p_sums + nb_r + nb_v + 1);
-                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, (const uint64_t *)(p_sums + nb_r), p_aoff);
-            }
-            return hipGetLastError();
-        };
-        /* Variant::alt_ed for every call, on the side stream behind the prefix sums and the allele bytes, while the region arrays still cross the bus: the state
-         * block is cleared here (dp_variant counts the calls it leaves to the host); the context's stream waits for ev_copy_join below as before */
-        auto queue_variant = [&]() -> hipError_t {
-            a.in.pk_a0 = p_a0, a.in.pk_a1 = p_a1, a.in.pk_aoff = p_aoff, a.in.pk_start = p_start; /* (what dp_variant reads of the packed source; the rest follows below) */
-            a.in.alleles = d_alleles, a.in.n_variants = nv, a.in.alleles_len = alen, a.in.n_regions = n;
-            hipError_t ev = hipMemsetAsync(a.st, 0, sizeof(dpk::DpState), side);
-            if (ev == hipSuccess) ev = hipStreamWaitEvent(side, ctx->ev_copy_alleles, 0);
-            if (ev == hipSuccess) {
-                hipLaunchKernelGGL(avk_dp_variant_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, side, a);
-                ev = hipGetLastError();
-            }
-            return ev;
-        };
-        /* The chunked route's region pass: launch j on the side stream behind dp_variant, the prefix sums and the event of group j; each block is run by exactly one
-         * launch (pc_launch_of_block), the catch-all behind the last group runs what none took.  block_sums and the region info are what the one launch writes.
-         *
-         * WHEN these are queued matters as much as what they wait for.  The runtime maps the context's streams onto a few hardware queues, a queue takes its packets in
-         * order, and every event recorded behind a copy is a packet that holds its queue until that copy is done.  Queued after copy_in has returned, the side stream's
-         * kernels sit — where the side stream shares the copy stream's queue — behind the packet of the LAST copy and start when it ends: a kernel trace of the old
-         * order shows the prefix sums and dp_variant starting 18 us after the last copy, whatever their events say (profiles/pack_chunks_ab.txt).  So each step is queued
-         * from copy_in itself, right behind the record of the event it waits for (CopySeg::then_call): in a shared queue it then stands in front of the later copies'
-         * packets, in a queue of its own nothing changes. */
-        hipError_t hook_err = hipSuccess;
-        auto queue_chunk = [&](uint32_t j) {
-            if (hook_err != hipSuccess) return;
-            hook_err = hipStreamWaitEvent(side, j + 1 == chunk_plan.k ? ctx->ev_copy_mid : ctx->ev_pack_group[j], 0);
-            for (uint32_t l = j; l <= (j + 1 == chunk_plan.k ? j + 1 : j) && hook_err == hipSuccess; ++l) { /* (behind the last group: the catch-all, l = k) */
-                const uint32_t grid = l < chunk_plan.k ? chunk_plan.block_cut[l + 1] : n_blocks;
-                hipLaunchKernelGGL(avk_dp_region_chunk_kernel, dim3(grid ? grid : 1u), dim3(256), 0, side, a, d_block_sums, chunk_plan, l, n_blocks);
-                hook_err = hipGetLastError();
-                ctx->last_region_launches += 1;
-            }
-            if (j + 1 != chunk_plan.k || hook_err != hipSuccess) return;
-            if (timing) {
-                if (!ctx->ev_tl[5] && hipEventCreate(&ctx->ev_tl[5]) != hipSuccess) ctx->ev_tl[5] = nullptr, (void)hipGetLastError();
-                if (ctx->ev_tl[5] && hipEventRecord(ctx->ev_tl[5], side) == hipSuccess) ctx->tl_region_valid = true;
-            }
-            hook_err = hipEventRecord(ctx->ev_copy_join, side);
-            region_done = hook_err == hipSuccess;
-        };
-        if (pre) { /* the arrays are in a staging slot already (or on their way there on the copy stream) */
-            hipError_t ep = hipStreamWaitEvent(s, pre->ready, 0);
-            if (ep == hipSuccess) ep = hipEventRecord(ctx->ev_copy_fork, s);
-            if (ep == hipSuccess) ep = hipEventRecord(ctx->ev_copy_mid, s);
-            if (ep == hipSuccess) ep = hipEventRecord(ctx->ev_copy_alleles, s);
-            if (ep != hipSuccess) rc = fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ep));
-        } else
-        /* (round 6: the allele bytes cross right behind the lengths — dp_variant needs nothing else, and runs on the side stream under the copies that follow) */
-        if (chunk_plan.k) { /* the chunked route: counts, lengths and allele bytes as below, then group by group: region range j of the per-region arrays, call chunk j of the
-                             * per-call arrays, an event; the last group's event is ev_copy_mid */
-            fill_args(); /* (the launches are queued from inside copy_in: everything dp_region reads is named now) */
-            a.in.pk_start = p_start, a.in.pk_len = p_len, a.in.pk_contig = p_contig, a.in.pk_rel = p_rel, a.in.pk_tc = p_tc, a.in.pk_qc = p_qc, a.in.pk_tz = p_tz, a.in.pk_a0 = p_a0,
-            a.in.pk_a1 = p_a1, a.in.pk_voff = p_voff, a.in.pk_aoff = p_aoff, a.in.v_lo = 0, a.in.v_hi = nv;
-            std::vector<CopySeg> segs = {{pk->t_cnt, p_tc, n}, {pk->q_cnt, p_qc, n}, {pk->a0_len, p_a0, nv}, {pk->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork},
-                                         {pk->allele_bytes, d_alleles, alen, nullptr, ctx->ev_copy_alleles}};
-            segs[3].then_call = [&] { hook_err = queue_sums(); };
-            segs[4].then_call = [&] {
-                if (hook_err == hipSuccess) hook_err = queue_variant();
-                variant_done = hook_err == hipSuccess;
-            };
-            for (uint32_t j = 0; j < chunk_plan.k; ++j) {
-                const avk::pc::Range rr = avk::pc::pc_region_range(chunk_plan, j), cr = avk::pc::pc_call_range(chunk_plan, j);
-                segs.push_back({pk->start + rr.first, p_start + rr.first, rr.count * 4});
-                segs.push_back({pk->len + rr.first, p_len + rr.first, rr.count * 2});
-                segs.push_back({has_contig ? pk->contig_idx + rr.first : nullptr, has_contig ? p_contig + rr.first : nullptr, has_contig ? rr.count * 2 : 0});
-                segs.push_back({pk->var_rel_pos + cr.first, p_rel + cr.first, cr.count * 2});
-                segs.push_back({pk->var_type_zyg + cr.first, p_tz + cr.first, cr.count});
-                segs.push_back({has_raw ? pk->var_raw_space + cr.first : nullptr, has_raw ? d_raw + cr.first : nullptr, has_raw ? cr.count * 4 : 0, nullptr,
-                                j + 1 == chunk_plan.k ? ctx->ev_copy_mid : ctx->ev_pack_group[j]});
-                segs.back().then_call = [&queue_chunk, j] { queue_chunk(j); };
-            }
-            for (CopySeg &sg : segs) sg.direct = true;
-            rc = copy_in(ctx, segs, spec.up_stream != nullptr);
-        } else
-        { /* (the escape lists, when there are any, in front of the array whose event releases the widening; none: the order of the copies is what it was) */
-            std::vector<CopySeg> segs = {{pk->t_cnt, p_tc, n}, {pk->q_cnt, p_qc, n}, {pk->a0_len, p_a0, nv}, {pk->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork},
-                                         {pk->allele_bytes, d_alleles, alen, nullptr, ctx->ev_copy_alleles}, {pk->start, p_start, n * 4}, {pk->len, p_len, n * 2},
-                                         {pk->contig_idx, p_contig, has_contig ? n * 2 : 0}, {pk->var_rel_pos, p_rel, nv * 2}};
-            segs.insert(segs.end(), esc_segs.begin(), esc_segs.end());
-            segs.push_back({pk->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid});
-            segs.push_back({pk->var_raw_space, d_raw, has_raw ? nv * 4 : 0});
-            if (queue_early) { /* the old order of the copies, the prefix sums and dp_variant queued behind their events as on the chunked route */
-                segs[3].then_call = [&] { hook_err = queue_sums(); };
-                segs[4].then_call = [&] {
-                    if (hook_err == hipSuccess) hook_err = queue_variant();
-                    variant_done = hook_err == hipSuccess;
-                };
-                for (CopySeg &sg : segs) sg.direct = true;
-            }
-            rc = copy_in(ctx, segs, spec.up_stream != nullptr);
-        }
-        early_variant = packed_src && nv != 0;
-        mark(1);
-        if (rc) return side_fail(rc);
-        hipError_t ec = queue_early ? hook_err : queue_sums(); /* (queued early: they stand behind the lengths' copy already) */
-        if (ec != hipSuccess) return side_fail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ec)));
-        /* the totals must be what the caller said: n_variants calls, allele_bytes_len bytes (two words back, with the packer's state block) */
-        pk_totals = p_sums + nb_r + nb_v;
-        dpk::DpPacked c;
-        memset(&c, 0, sizeof(c));
-        c.contig_idx = p_contig, c.len = p_len, c.rel_pos = p_rel, c.start = p_start, c.var_raw = d_raw, c.t_cnt = p_tc, c.q_cnt = p_qc, c.var_type_zyg = p_tz, c.a0_len = p_a0, c.a1_len = p_a1,
-        c.v_off = p_voff, c.a_off = p_aoff, c.n_regions = n, c.n_variants = nv;
-        c.w_contig = d_contig, c.w_t_cnt = db->d_in_t_cnt, c.w_q_cnt = db->d_in_q_cnt, c.w_a0_len = d_a0l, c.w_a1_len = d_a1l, c.w_raw = nullptr, c.w_start = d_start, c.w_end = d_end,
-        c.w_t_off = db->d_in_t_off, c.w_q_off = db->d_in_q_off, c.w_pos = d_pos, c.w_a0_off = d_a0o, c.w_a1_off = d_a1o, c.w_type = d_type, c.w_zyg = d_zyg;
-        const uint64_t m = n > nv ? n : nv;
-        hipError_t ew = hipSuccess;
-        if (early_variant && !queue_early) {
-            ew = queue_variant();
-            variant_done = ew == hipSuccess;
-        }
-        if (queue_early && !(variant_done && (region_done || !chunk_plan.k)) && ew == hipSuccess) ew = hipErrorUnknown; /* (dp_variant and the chunked region launches were queued from copy_in) */
-        if (ew == hipSuccess && !chunk_plan.k) ew = hipStreamWaitEvent(side, ctx->ev_copy_mid, 0); /* (chunked: the side stream waits group by group, below) */
-        if (packed_src) { /* the packer reads these as they are */
-            a.in.pk_start = p_start, a.in.pk_len = p_len, a.in.pk_contig = p_contig, a.in.pk_rel = p_rel, a.in.pk_tc = p_tc, a.in.pk_qc = p_qc, a.in.pk_tz = p_tz, a.in.pk_a0 = p_a0,
-            a.in.pk_a1 = p_a1, a.in.pk_voff = p_voff, a.in.pk_aoff = p_aoff;
-            db->d_pk_voff = p_voff, db->d_pk_tc = p_tc, db->d_pk_qc = p_qc;
-        } else if (has_esc && ew == hipSuccess) {
-            esc_scans(side, pk_totals, 2 * n, nv, n, dpk::DpEscNarrow{p_tc, p_qc, nullptr, 1u}, dpk::DpEscNarrow{p_a0, p_a1, p_rel, 0u}, dpk::DpEscNarrow{nullptr, nullptr, p_len, 0u});
-            if (m) hipLaunchKernelGGL(avk_dp_widen_packed_esc_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, side, c, de);
-            ew = hipGetLastError();
-        } else if (m && ew == hipSuccess) {
-            hipLaunchKernelGGL(avk_dp_widen_packed_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, side, c);
-            ew = hipGetLastError();
-        }
-        if (ew == hipSuccess && !chunk_plan.k) ew = hipEventRecord(ctx->ev_copy_join, side); /* (chunked: recorded behind the catch-all launch) */
-        if (ew == hipSuccess) ew = hipStreamWaitEvent(s, ctx->ev_copy_join, 0); /* from here on the context's stream has the wide arrays (and, being behind its own copies, the allele bytes) */
-        if (ew != hipSuccess) return side_fail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(ew)));
-    } else if (b) {
-        std::vector<CopySeg> segs = {
-            {b->start, d_start, n * 8}, {b->end, d_end, n * 8}, {b->t_off, db->d_in_t_off, n * 8}, {b->q_off, db->d_in_q_off, n * 8},
-            {b->t_cnt, db->d_in_t_cnt, n * 4}, {b->q_cnt, db->d_in_q_cnt, n * 4}, {b->contig_idx, d_contig, b->contig_idx ? n * 4 : 0},
-            {b->var_pos, d_pos, nv * 8}, {b->a0_off, d_a0o, nv * 8}, {b->a1_off, d_a1o, nv * 8}, {b->a0_len, d_a0l, nv * 4}, {b->a1_len, d_a1l, nv * 4},
-            {b->var_raw_space, d_raw, b->var_raw_space ? nv * 4 : 0}, {b->var_type, d_type, nv}, {b->var_zyg, d_zyg, nv}, {b->allele_bytes, d_alleles, alen}};
-        rc = copy_in(ctx, segs, spec.up_stream != nullptr);
-        if (rc) return bail(rc);
-    } else if (mb) { /* the MultiRegions as they are, one kernel that writes a region per input pair; the call arrays are shared by all pairs */
-        const uint64_t nm = mb->n_regions;
-        uint32_t *m_contig = has_contig ? (uint32_t *)tmp((nm + 1) * 4) : nullptr;
-        uint64_t *m_start = (uint64_t *)tmp((nm + 1) * 8), *m_end = (uint64_t *)tmp((nm + 1) * 8);
-        db->d_m_in_off = (uint64_t *)kept((nm * mk + 1) * 8);
-        db->d_m_in_cnt = (uint32_t *)kept((nm * mk + 1) * 4);
-        db->d_in_zyg = d_zyg, db->d_in_type = d_type;
-        db->n_multi = nm, db->m_inputs = mk;
-        if (rc) return bail(rc);
-        if (pm) { /* the packed arrays as they are; in_off and a_off by prefix sums; one kernel writes the wide MultiRegion arrays the pair expansion reads */
-            const uint64_t ni = nm * mk;
-            uint16_t *p_contig = has_contig ? (uint16_t *)tmp((nm + 1) * 2) : nullptr, *p_len = (uint16_t *)tmp((nm + 1) * 2), *p_rel = (uint16_t *)tmp((nv + 1) * 2);
-            uint32_t *p_start = (uint32_t *)tmp((nm + 1) * 4);
-            uint8_t *p_ic = (uint8_t *)tmp(ni + 16), *p_tz = (uint8_t *)tmp(nv + 16), *p_a0 = (uint8_t *)tmp(nv + 16), *p_a1 = (uint8_t *)tmp(nv + 16);
-            const uint32_t nb_r = (uint32_t)((ni + AVK_PS_BLOCK - 1) / AVK_PS_BLOCK), nb_v = (uint32_t)((nv + AVK_PS_BLOCK - 1) / AVK_PS_BLOCK);
-            uint64_t *p_aoff = (uint64_t *)tmp((nv + 1) * 8), *p_sums = (uint64_t *)tmp(((size_t)nb_r + nb_v + 4) * 8);
-            uint64_t *p_ioff = has_esc ? (uint64_t *)tmp((ni + 1) * 8) : db->d_m_in_off; /* (with escapes: the sums over the narrow counts; the widening writes the true offsets) */
-            if (rc) return bail(rc);
-            hipStream_t side = (spec.up_side ? spec.up_side : ctx->lane_stream4); /* as for avk_packed_batch: copies on the context's stream, counts first; prefix sums and widening beside them */
-            auto side_fail = [&](int code) {
-                (void)hipStreamSynchronize(side);
-                return bail(code);
-            };
-            {
-                std::vector<CopySeg> segs = {{pm->in_cnt, p_ic, ni}, {pm->a0_len, p_a0, nv}, {pm->a1_len, p_a1, nv, nullptr, ctx->ev_copy_fork}, {pm->start, p_start, nm * 4}, {pm->len, p_len, nm * 2},
-                                             {pm->contig_idx, p_contig, has_contig ? nm * 2 : 0}, {pm->var_rel_pos, p_rel, nv * 2}};
-                segs.insert(segs.end(), esc_segs.begin(), esc_segs.end()); /* (none without escapes: the order of the copies is what it was) */
-                segs.push_back({pm->var_type_zyg, p_tz, nv, nullptr, ctx->ev_copy_mid});
-                segs.push_back({pm->var_raw_space, d_raw, has_raw ? nv * 4 : 0});
-                segs.push_back({pm->allele_bytes, d_alleles, alen});
-                rc = copy_in(ctx, segs, spec.up_stream != nullptr);
-            }
-            if (rc) return bail(rc);
-            hipError_t ec = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0);
-            if (ec != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(ec)));
-            if (has_esc && hipMemsetAsync(p_sums + nb_r + nb_v, 0, 32, side) != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "packed upload: %s", hipGetErrorString(hipGetLastError())));
-            if (ni) {
-                hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_ic, (const uint8_t *)nullptr, ni, p_sums);
-                hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums, nb_r, p_sums + nb_r + nb_v);
-                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_r), dim3(256), 0, side, (const uint8_t *)p_ic, (const uint8_t *)nullptr, ni, (const uint64_t *)p_sums, p_ioff);
-            }
-            if (nv) {
-                hipLaunchKernelGGL(avk_ps_block_sums_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, p_sums + nb_r);
-                hipLaunchKernelGGL(avk_ps_scan_sums_kernel, dim3(1), dim3(1024), 0, side, p_sums + nb_r, nb_v, p_sums + nb_r + nb_v + 1);
-                hipLaunchKernelGGL(avk_ps_apply_kernel, dim3(nb_v), dim3(256), 0, side, (const uint8_t *)p_a0, (const uint8_t *)p_a1, nv, (const uint64_t *)(p_sums + nb_r), p_aoff);
-            }
-            pk_totals = p_sums + nb_r + nb_v;
-            dpk::DpPackedMulti w;
-            memset(&w, 0, sizeof(w));
-            w.contig_idx = p_contig, w.len = p_len, w.rel_pos = p_rel, w.start = p_start, w.var_raw = d_raw, w.in_cnt = p_ic, w.var_type_zyg = p_tz, w.a0_len = p_a0, w.a1_len = p_a1,
-            w.in_off = p_ioff, w.a_off = p_aoff, w.n_multi = nm, w.n_variants = nv, w.k = mk;
-            w.w_contig = m_contig, w.w_in_cnt = db->d_m_in_cnt, w.w_a0_len = d_a0l, w.w_a1_len = d_a1l, w.w_raw = nullptr, w.w_start = m_start, w.w_end = m_end, w.w_pos = d_pos,
-            w.w_a0_off = d_a0o, w.w_a1_off = d_a1o, w.w_type = d_type, w.w_zyg = d_zyg;
-            const uint64_t mx = nm > nv ? nm : nv;
-            hipError_t ew = hipStreamWaitEvent(side, ctx->ev_copy_mid, 0);
-            if (has_esc && ew == hipSuccess) {
-                esc_scans(side, pk_totals, ni, nv, nm, dpk::DpEscNarrow{p_ic, nullptr, nullptr, 0u}, dpk::DpEscNarrow{p_a0, p_a1, p_rel, 0u}, dpk::DpEscNarrow{nullptr, nullptr, p_len, 0u});
-                if (mx) hipLaunchKernelGGL(avk_dp_widen_packed_multi_esc_kernel, dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, side, w, de, db->d_m_in_off);
-                ew = hipGetLastError();
-            } else if (mx && ew == hipSuccess) {
-                hipLaunchKernelGGL(avk_dp_widen_packed_multi_kernel, dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, side, w);
-                ew = hipGetLastError();
-            }
-            if (ew == hipSuccess) ew = hipEventRecord(ctx->ev_copy_join, side);
-            if (ew == hipSuccess) ew = hipStreamWaitEvent(s, ctx->ev_copy_join, 0);
-            if (ew != hipSuccess) return side_fail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(ew)));
-        } else {
-        std::vector<CopySeg> segs = {{mb->start, m_start, nm * 8}, {mb->end, m_end, nm * 8}, {mb->in_off, db->d_m_in_off, nm * mk * 8}, {mb->in_cnt, db->d_m_in_cnt, nm * mk * 4},
-                                     {mb->contig_idx, m_contig, has_contig ? nm * 4 : 0}, {mb->var_pos, d_pos, nv * 8}, {mb->a0_off, d_a0o, nv * 8}, {mb->a1_off, d_a1o, nv * 8},
-                                     {mb->a0_len, d_a0l, nv * 4}, {mb->a1_len, d_a1l, nv * 4}, {mb->var_raw_space, d_raw, has_raw ? nv * 4 : 0}, {mb->var_type, d_type, nv},
-                                     {mb->var_zyg, d_zyg, nv}, {mb->allele_bytes, d_alleles, alen}};
-        rc = copy_in(ctx, segs, spec.up_stream != nullptr);
-        if (rc) return bail(rc);
-        }
-        dpk::DpPairs c;
-        memset(&c, 0, sizeof(c));
-        c.contig_idx = m_contig, c.start = m_start, c.end = m_end, c.in_off = db->d_m_in_off, c.in_cnt = db->d_m_in_cnt, c.n_multi = nm, c.k = mk, c.ppr = mppr;
-        c.w_contig = d_contig, c.w_t_cnt = db->d_in_t_cnt, c.w_q_cnt = db->d_in_q_cnt, c.w_start = d_start, c.w_end = d_end, c.w_t_off = db->d_in_t_off, c.w_q_off = db->d_in_q_off;
-        if (n) {
-            hipLaunchKernelGGL(avk_dp_expand_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c);
-            hipError_t ew = hipGetLastError();
-            if (ew != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(ew)));
-        }
-    } else { /* the compact arrays as they are, then one kernel that writes the wide ones */
-        dpk::DpCompact c;
-        memset(&c, 0, sizeof(c));
-        uint32_t *c_contig = has_contig ? (uint32_t *)tmp((n + 1) * 4) : nullptr, *c_start = (uint32_t *)tmp((n + 1) * 4), *c_len = (uint32_t *)tmp((n + 1) * 4),
-                 *c_voff = (uint32_t *)tmp((n + 1) * 4), *c_pos = (uint32_t *)tmp((nv + 1) * 4), *c_aoff = (uint32_t *)tmp((nv + 1) * 4);
-        uint16_t *c_tc = (uint16_t *)tmp((n + 1) * 2), *c_qc = (uint16_t *)tmp((n + 1) * 2);
-        uint8_t *c_tz = (uint8_t *)tmp(nv + 16);
-        if (rc) return bail(rc);
-        /* a0_len / a1_len / raw_space have the wide arrays' type: they are copied straight into them */
-        std::vector<CopySeg> segs = {{cb->start, c_start, n * 4}, {cb->len, c_len, n * 4}, {cb->v_off, c_voff, n * 4}, {cb->t_cnt, c_tc, n * 2}, {cb->q_cnt, c_qc, n * 2},
-                                     {cb->contig_idx, c_contig, has_contig ? n * 4 : 0}, {cb->var_pos, c_pos, nv * 4}, {cb->a_off, c_aoff, nv * 4}, {cb->var_type_zyg, c_tz, nv},
-                                     {cb->a0_len, d_a0l, nv * 4}, {cb->a1_len, d_a1l, nv * 4}, {cb->var_raw_space, d_raw, has_raw ? nv * 4 : 0}, {cb->allele_bytes, d_alleles, alen}};
-        rc = copy_in(ctx, segs, spec.up_stream != nullptr);
-        if (rc) return bail(rc);
-        c.contig_idx = c_contig, c.start = c_start, c.len = c_len, c.v_off = c_voff, c.t_cnt = c_tc, c.q_cnt = c_qc, c.var_pos = c_pos, c.a_off = c_aoff, c.a0_len = d_a0l, c.a1_len = d_a1l,
-        c.var_raw = nullptr, c.var_type_zyg = c_tz, c.n_regions = n, c.n_variants = nv;
-        c.w_contig = d_contig, c.w_t_cnt = db->d_in_t_cnt, c.w_q_cnt = db->d_in_q_cnt, c.w_a0_len = d_a0l, c.w_a1_len = d_a1l, c.w_raw = nullptr, c.w_start = d_start, c.w_end = d_end,
-        c.w_t_off = db->d_in_t_off, c.w_q_off = db->d_in_q_off, c.w_pos = d_pos, c.w_a0_off = d_a0o, c.w_a1_off = d_a1o, c.w_type = d_type, c.w_zyg = d_zyg;
-        const uint64_t m = n > nv ? n : nv;
-        if (m) {
-            hipLaunchKernelGGL(avk_dp_widen_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, c);
-            hipError_t ew = hipGetLastError();
-            if (ew != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(ew)));
-        }
-    }
-    const auto t_copy = now();
-    fill_args();
-    { /* the calls this batch owns, guessed from its first and last region (batches of one job may share the call arrays: compare_main.cpp);
-       * dp_region notes any region outside the guess */
-        uint64_t lo = 0, hi = 0;
-        if (pk) {
-            hi = nv; /* the packed form owns its calls by construction */
-        } else if (n && b) {
-            const uint64_t a0 = b->t_cnt[0] ? b->t_off[0] : b->q_off[0], a1 = b->q_cnt[0] ? b->q_off[0] : b->t_off[0];
-            lo = a0 < a1 ? a0 : a1;
-            const uint64_t e0 = b->t_off[n - 1] + b->t_cnt[n - 1], e1 = b->q_off[n - 1] + b->q_cnt[n - 1];
-            hi = e0 > e1 ? e0 : e1;
-        } else if (n && cb) {
-            lo = cb->v_off[0];
-            hi = (uint64_t)cb->v_off[n - 1] + cb->t_cnt[n - 1] + cb->q_cnt[n - 1];
-        } else
-            hi = nv; /* (the pair form has no per-call outputs) */
-        if (hi > nv) hi = nv;
-        if (lo > hi) lo = hi;
-        a.in.v_lo = lo, a.in.v_hi = hi;
-        if ((b || cb) && !pairs_mode && hi > lo) { /* explicit offsets: ownership is counted (DpIn::owned) */
-            a.in.owned = (uint8_t *)tmp(hi - lo + 16);
-            if (rc) return bail(rc);
-            if (hipMemsetAsync(a.in.owned, 0, hi - lo, s) != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(hipGetLastError())));
-        }
-    }
-    hipError_t e = variant_done ? hipSuccess : hipMemsetAsync(a.st, 0, sizeof(dpk::DpState), s);
-    if (e == hipSuccess && nv && !variant_done) {
-        hipLaunchKernelGGL(avk_dp_variant_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, a);
-        e = hipGetLastError();
-    }
-    dpk::DpState *hs = (dpk::DpState *)ctx->h_dpstate;
-    auto region_passes = [&]() -> hipError_t { /* everything that depends on alt_ed, up to the state block on the host */
-        hipError_t x = hipSuccess;
-        if (n) {
-            if (!region_done) {
-                hipLaunchKernelGGL(avk_dp_region_kernel, dim3(n_blocks), dim3(256), 0, s, a, d_block_sums);
-                ctx->last_region_launches += 1;
-                if (timing) {
-                    if (!ctx->ev_tl[5] && hipEventCreate(&ctx->ev_tl[5]) != hipSuccess) ctx->ev_tl[5] = nullptr, (void)hipGetLastError();
-                    if (ctx->ev_tl[5] && hipEventRecord(ctx->ev_tl[5], s) == hipSuccess) ctx->tl_region_valid = true;
-                }
-            }
-            region_done = false; /* (a second round, behind the host's edit distances, runs the whole range in one launch) */
-            if (a.in.owned && a.in.v_hi > a.in.v_lo)
-                hipLaunchKernelGGL(avk_dp_count_owned_kernel, dim3((unsigned)((a.in.v_hi - a.in.v_lo + 4095) / 4096)), dim3(256), 0, s, (const uint8_t *)a.in.owned, a.in.v_hi - a.in.v_lo, a.st);
-            hipLaunchKernelGGL(avk_dp_scan_blocks_kernel, dim3(AVK_DP_BS), dim3(1024), 0, s, d_block_sums, n_blocks, a.st);
-            hipLaunchKernelGGL(avk_dp_scan_apply_kernel, dim3(n_blocks), dim3(256), 0, s, a, (const uint64_t *)d_block_sums);
-            hipLaunchKernelGGL(avk_dp_lane_switch_kernel, dim3(1), dim3(64), 0, s, a);
-            hipLaunchKernelGGL(avk_dp_hist_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, s, a);
-            hipLaunchKernelGGL(avk_dp_bucket_bases_kernel, dim3(1), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(avk_dp_scatter_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, s, a);
-            x = hipGetLastError();
-        }
-        StrataJob *sj = n && spec.strata && !spec.strata->counted ? spec.strata : nullptr; /* (once: the lists do not depend on alt_ed, a second round of the passes leaves them) */
-        const bool sj_total = sj && !sj->mask_only;
-        if (x == hipSuccess && sj) x = sj_total ? strata_count_launch(sj->st, a.in, n, sj->d_mask, sj->d_sums, s) : strata_mask_launch(sj->st, a.in, n, sj->d_mask, sj->d_sums, s);
-        mark(2);
-        if (x == hipSuccess) x = hipMemcpyAsync(hs, a.st, sizeof(dpk::DpState), hipMemcpyDeviceToHost, s);
-        if (x == hipSuccess && pk_totals) x = hipMemcpyAsync(hs + 1, pk_totals, has_esc ? 24 : 16, hipMemcpyDeviceToHost, s); /* (the packed forms' two sums ride along: 16 bytes behind the state block) */
-        if (x == hipSuccess && sj_total) x = hipMemcpyAsync((uint8_t *)(hs + 1) + 24, sj->d_sums + strata_blocks(n), 8, hipMemcpyDeviceToHost, s); /* (and the lists' size behind those) */
-        if (x == hipSuccess) x = hipStreamSynchronize(s);
-        if (x == hipSuccess && sj_total) memcpy(&sj->total, (const uint8_t *)(hs + 1) + 24, 8);
-        if (x == hipSuccess && sj) sj->counted = true;
-        if (x == hipSuccess) engine_rate_check(ctx);
-        return x;
-    };
-    if (e == hipSuccess) e = region_passes();
-    if (e == hipSuccess && (pk || pm)) { /* the two sums the packed form implies must be what the caller says they are */
-        uint64_t tot[3] = {0, 0, 0};
-        memcpy(tot, hs + 1, has_esc ? 24 : 16);
-        if (has_esc && tot[2]) return bail(fail(ctx, AVK_E_ARG, "packed batch: an escape list is not ascending, names an entry outside the batch, or lists an entry whose narrow field is not 0"));
-        if ((((pm ? pm->n_regions : n) && tot[0] != nv) || (nv && tot[1] != alen)))
-            return bail(fail(ctx, AVK_E_ARG, "packed batch: the call counts sum to %llu (n_variants %llu), the allele lengths to %llu (allele_bytes_len %llu)",
-                             (unsigned long long)tot[0], (unsigned long long)nv, (unsigned long long)tot[1], (unsigned long long)alen));
-    }
-    std::vector<uint64_t> pk_aoff; /* packed form: allele offsets on the host, made only when a call needs the host's edit distance */
-    std::vector<uint32_t> pk_w0, pk_w1; /* ... and the lengths, escapes honoured */
-    const uint8_t *pk_l0 = pk ? pk->a0_len : (pm ? pm->a0_len : nullptr), *pk_l1 = pk ? pk->a1_len : (pm ? pm->a1_len : nullptr);
-    if (e == hipSuccess && hs->n_pending && pk_l0 && has_esc) packed_host_alleles(pk_l0, pk_l1, nv, esc, pk_aoff, pk_w0, pk_w1);
-    else if (e == hipSuccess && hs->n_pending && pk_l0) {
-        pk_aoff.resize(nv + 1);
-        uint64_t run = 0;
-        for (uint64_t v = 0; v < nv; ++v) pk_aoff[v] = run, run += (uint64_t)pk_l0[v] + pk_l1[v];
-    }
-    if (e == hipSuccess && hs->n_pending) {
-        /* calls whose two alleles are both long after the common prefix and suffix are gone: their alt_ed comes from the host
-         * (avk_edit_distance, the routine the host-side packer uses for every call), and the region passes run again */
-        const uint32_t np = hs->n_pending;
-        std::vector<uint32_t> idx(np), ed(np);
-        e = hipMemcpy(idx.data(), a.pending, (size_t)np * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) {
-            avk_parallel_for(np, avk_host_threads(), [&](unsigned, uint64_t lo, uint64_t hi) {
-                for (uint64_t k = lo; k < hi; ++k) {
-                    const uint64_t v = idx[k];
-                    const uint64_t o0 = pk_l0 ? pk_aoff[v] : (b ? b->a0_off[v] : (cb ? cb->a_off[v] : mb->a0_off[v])), l0 = pk_l0 ? (has_esc ? pk_w0[v] : (uint32_t)pk_l0[v]) : (b ? b->a0_len[v] : (cb ? cb->a0_len[v] : mb->a0_len[v])),
-                                   o1 = pk_l0 ? o0 + l0 : (b ? b->a1_off[v] : (cb ? o0 + l0 : mb->a1_off[v])), l1 = pk_l0 ? (has_esc ? pk_w1[v] : (uint32_t)pk_l1[v]) : (b ? b->a1_len[v] : (cb ? cb->a1_len[v] : mb->a1_len[v]));
-                    ed[k] = (uint32_t)avk::host_edit_distance(host_alleles + o0, l0, host_alleles + o1, l1);
-                }
-            });
-            uint32_t *d_idx = (uint32_t *)tmp((size_t)np * 4), *d_ed = (uint32_t *)tmp((size_t)np * 4);
-            if (rc) return bail(rc);
-            e = hipMemcpy(d_idx, idx.data(), (size_t)np * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(d_ed, ed.data(), (size_t)np * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(avk_dp_patch_ed_kernel, dim3((np + 255) / 256), dim3(256), 0, s, a.vinfo, (const uint32_t *)d_idx, (const uint32_t *)d_ed, np);
-                e = hipMemsetAsync(a.st, 0, sizeof(dpk::DpState), s);
-            }
-            if (e == hipSuccess) e = region_passes();
-        }
-    }
-    if (e != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(e)));
-    const auto t_plan = now();
-    if (hs->err & dpk::DP_ERR_RANGE) return bail(fail(ctx, AVK_E_ARG, "variant range of a region exceeds n_variants"));
-    if (hs->err & dpk::DP_ERR_ALLELE) return bail(fail(ctx, AVK_E_ARG, "allele range exceeds allele_bytes_len"));
-    if (hs->err & dpk::DP_ERR_BLOB) return bail(fail(ctx, AVK_E_ARG, "region blob exceeds 2 GiB; split the region's alleles"));
-    if (hs->total_v > 0x7FFFFFFFull) return bail(fail(ctx, AVK_E_ARG, "more than 2^31 variant records; split the batch"));
-    db->v_lo = a.in.v_lo, db->v_hi = a.in.v_hi;
-    if (hs->err & dpk::DP_NOTE_OUTSIDE) db->v_lo = 0, db->v_hi = nv;
-    /* every call of the range is owned, and once: nothing to preserve.  The packed forms' offsets are the running sums of the counts — dense when the sums are right;
-     * forms with explicit offsets are dense when as many calls are marked as the range has and the counts add up to the same number */
-    db->var_dense = !(hs->err & dpk::DP_NOTE_OUTSIDE) && hs->total_v == db->v_hi - db->v_lo && (!a.in.owned || hs->n_owned == db->v_hi - db->v_lo);
-    if (hs->total_blob_words / 2 > 0xFFFFFFFFull) return bail(fail(ctx, AVK_E_ARG, "region blob arena exceeds its limits; split the batch"));
-    db->n_variants_dev = hs->total_v;
-    db->seq_total = hs->total_seq;
-    db->n_bp_groups = hs->total_groups;
-    { /* per-wave HBM slices of this batch's launches: large enough for 98 % of the regions predicted to need the tier (64 MB at most) */
-        uint64_t n_c = 0, run = 0;
-        for (int k = 0; k < dpk::DP_NEED_BUCKETS; ++k) n_c += hs->need_hist[k];
-        int pick = 0;
-        for (int k = 0; k < dpk::DP_NEED_BUCKETS && n_c >= 64; ++k) {
-            run += hs->need_hist[k];
-            pick = k;
-            if (run * 100 >= n_c * 98) break;
-        }
-        if (pick > 6) pick = 6;
-        const int64_t want = 1ll << (20 + pick);
-        db->ws_bytes_eff = want > ctx->ws_bytes_per_wave && ctx->ws_bytes_per_wave > 0 && ctx->adaptive_ws ? want : 0;
-        /* regions predicted beyond the last bucket (windows of tens of kilobases with dozens of calls): the shared slices start at the size of the library's first
-         * capacity retry, so that these regions are solved in the step and not again, one sub-batch at a time, by avk_results_download */
-        db->big_bytes_eff = hs->need_hist[dpk::DP_NEED_BUCKETS - 1] > 0 && ctx->adaptive_ws ? (1ll << 30) : 0;
-    }
-    db->plan.n_hbm = hs->n_hbm, db->plan.n_hard = hs->n_hard, db->plan.n_fast_total = hs->n_fast_total, db->plan.n_hbm_notwide = hs->n_hbm_notwide;
-    uint32_t tiles_total = 0;
-    for (int fc = 0; fc < AVK_FAST_CLASSES; ++fc) {
-        db->plan.n_fast[fc] = hs->n_fast[fc], db->plan.n_fast_heavy[fc] = hs->n_fast_heavy[fc], db->plan.fast_base[fc] = hs->fast_base[fc];
-        db->fast_word_base[fc] = hs->fast_word_base[fc], db->fast_tiles[fc] = hs->fast_tiles[fc];
-        tiles_total += hs->fast_tiles[fc];
-    }
-    /* the batch's own buffers */
-    const uint64_t nvd = hs->total_v;
-    db->d_regions = (AvkDevRegion *)kept((n + 1) * sizeof(AvkDevRegion));
-    db->d_blob = (uint32_t *)kept(((size_t)hs->total_blob_words + 4) * 4);
-    db->d_region_out = (uint32_t *)kept((n * 4 + 4) * 4);
-    db->d_var_out = (uint32_t *)kept((nvd + 1) * 4);
-    db->d_seqlen = (uint32_t *)kept((n * 5 + 1) * 4);
-    db->d_tally = (uint64_t *)kept((size_t)AVK_TALLY_STRIDE * 8);
-    db->d_partials = (uint64_t *)kept((size_t)AVK_TALLY_STRIDE * AVK_TALLY_COPIES * 8);
-    db->d_counters = (uint32_t *)kept((size_t)AVK_N_COUNTERS * 4);
-    db->d_overflow = (uint32_t *)kept((n + 1024) * 4);
-    db->d_overflow2 = (uint32_t *)kept((n + 1) * 4);
-    db->d_overflow3 = (uint32_t *)kept((3 * (n + 1) + 1024) * 4);
-    db->d_overflow4 = (uint32_t *)kept((n + 1) * 4);
-    db->d_overflow5 = (uint32_t *)kept((n + 1) * 4);
-    db->d_overflow6 = (uint32_t *)kept((n + 1) * 4);
-    db->d_overflow7 = (uint32_t *)kept((n + 1) * 4);
-    db->d_overflow8 = (uint32_t *)kept((n + 1) * 4);
-    db->d_notwide = (uint32_t *)kept((n + 2) * 4);
-    if (hs->n_fast_total) db->d_fast = (uint32_t *)kept(((size_t)hs->fast_words + 64) * 4);
-    /* the packer's arguments in device memory: the waves that solve handed-back regions write their records themselves */
-    if (hs->n_fast_total) db->d_dp_args = (dpk::DpArgs *)kept(sizeof(dpk::DpArgs));
-    if (rc) return bail(rc);
-    a.regions = db->d_regions, a.blob = db->d_blob, a.fast = db->d_fast;
-    db->dp_args = a;
-    const bool clear_beside = n >= 262144; /* (a small batch: the two events between the streams cost more than the fills, 1.16 instead of 0.98 ms per 46,000-region call) */
-    if (clear_beside) { /* the batch's partial tallies and counters are cleared beside the writers, on a side stream (in front of the solver launches the two fills took 55 us) */
-        hipStream_t side = (spec.up_side ? spec.up_side : ctx->lane_stream4);
-        hipError_t ez = hipEventRecord(ctx->ev_copy_fork, s); /* the buffers may have been another batch's until here */
-        if (ez == hipSuccess) ez = hipStreamWaitEvent(side, ctx->ev_copy_fork, 0);
-        if (ez == hipSuccess && db->d_dp_args) ez = hipMemcpyAsync(db->d_dp_args, &db->dp_args, sizeof(dpk::DpArgs), hipMemcpyHostToDevice, side); /* (behind the writers it was
-                                                                                                     most of a 130 us gap in front of the solver launches) */
-        if (ez == hipSuccess) ez = hipMemsetAsync(db->d_partials, 0, (size_t)AVK_TALLY_STRIDE * AVK_TALLY_COPIES * sizeof(uint64_t), side);
-        if (ez == hipSuccess) ez = hipMemsetAsync(db->d_counters, 0, AVK_N_COUNTERS * sizeof(uint32_t), side);
-        if (ez == hipSuccess) ez = hipEventRecord(ctx->ev_copy_join, side);
-        if (ez != hipSuccess) {
-            (void)hipStreamSynchronize(side);
-            return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(ez)));
-        }
-        db->scratch_clean = true;
-    }
-    if (tiles_total) hipLaunchKernelGGL(avk_dp_fast_records_kernel, dim3((tiles_total + 3) / 4), dim3(256), 0, s, a, tiles_total);
-    /* records and blobs: now for the regions the wave-per-region launches start with; for the lanes' regions when (and if) a launch asks for them */
-    const uint32_t n_eager = (uint32_t)n - hs->n_fast_total;
-    if (n_eager) {
-        hipLaunchKernelGGL(avk_dp_region_records_kernel, dim3((n_eager + 255) / 256), dim3(256), 0, s, a, n_eager);
-        hipLaunchKernelGGL(avk_dp_region_records_wave_kernel, dim3(256), dim3(256), 0, s, a);
-    }
-    db->records_full = hs->n_fast_total == 0;
-    db->lazy_from = n_eager;
-    if (db->d_dp_args && !clear_beside) {
-        hipError_t ec = hipMemcpyAsync(db->d_dp_args, &db->dp_args, sizeof(dpk::DpArgs), hipMemcpyHostToDevice, s);
-        if (ec != hipSuccess) return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(ec)));
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess && clear_beside) e = hipStreamWaitEvent(s, ctx->ev_copy_join, 0); /* the cleared scratch, before anything that follows on this stream */
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize((spec.up_side ? spec.up_side : ctx->lane_stream4));
-        return bail(fail(ctx, AVK_E_HIP, "device packing failed: %s", hipGetErrorString(e)));
-    }
-    mark(3);
-    for (void *p : temps) pool_release(ctx, p); /* in stream order: the writers above run before anything that is handed these buffers next */
-    if (!spec.up_stream && ctx->ev_pool_fence) { /* ... which an upload on the packing stream of the asynchronous boundary is not, by itself: it waits for this point once */
-        if (hipEventRecord(ctx->ev_pool_fence, s) == hipSuccess) ctx->pool_fence_pending = true;
-        else (void)hipGetLastError();
-    }
-    if (timing)
-        fprintf(stderr, "avk upload (device-packed): %llu regions, %llu calls: buffers %.3f ms, copies queued %.3f ms, packing kernels + plan %.3f ms, writers queued %.3f ms; lanes %u regions in %u tiles, class C %u, class B %u\n",
-                (unsigned long long)n, (unsigned long long)nv, ms(t_start, t_alloc), ms(t_alloc, t_copy), ms(t_copy, t_plan), ms(t_plan, now()), hs->n_fast_total, tiles_total,
-                hs->n_hbm, hs->n_hard);
-    *out = db;
-    return 0;
 }
 
 /* ---- download of a device-packed batch: dp_unpack on the device, then plain copies into the caller's arrays ------------------------- */

@@ -34,6 +34,7 @@
 #include "avk_counters.h"
 #include "avk_step_plan.h"
 #include "avk_step_geometry.h"
+#include "avk_upload_forms.h"
 #include "avk_solver.inl"
 #include "avk_lane.inl"
 #include "avk_quad.inl"
@@ -344,7 +345,7 @@ struct avk_ctx {
     int64_t use_packed_reference = 1;
     std::vector<uint64_t> contig_base, contig_len;
     uint64_t *d_contig_tab = nullptr; /* contig_base[n_contigs] then contig_len[n_contigs], for the device-side packer */
-    /* device-side packing (avk_devpack_host.inl) */
+    /* device-side packing (avk_devpack_host.inl, avk_upload.inl) */
     int64_t adaptive_ws = 1;               /* device-packed batches size their per-wave HBM slices by the predicted need of their class C regions (option ws_bytes_per_wave is the minimum) */
     int64_t ws_budget_bytes = 96ll << 30;  /* at most this much HBM for those slices: fewer waves per launch when the slices are large */
     int64_t device_pack = 1;               /* batches are validated, classified, ordered and written ON THE DEVICE from the caller's arrays (0: avk_pack.h on the host threads) */
@@ -652,6 +653,7 @@ static CallSpec call_spec(const avk_ctx *ctx, const avk_result_batch *out, bool 
 }
 
 #include "avk_devpack_host.inl"
+#include "avk_upload.inl"
 
 extern "C" {
 
@@ -1210,7 +1212,7 @@ static int upload_internal(avk_ctx *ctx, const CallSpec &spec, const avk_region_
     *out = nullptr;
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->device_pack) return upload_device_packed(ctx, spec, batch, nullptr, pairs_mode, out);
+    if (ctx->device_pack) return upload_device_packed(ctx, spec, UploadSource::of(batch, pairs_mode), nullptr, out);
     const bool timing = getenv("AVK_TIMING") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -2205,7 +2207,7 @@ static int submit_impl(avk_ctx *ctx, const avk_packed_batch *batch, const avk_co
             ctx->pool_fence_pending = false;
         }
     }
-    rc = upload_device_packed(ctx, spec, nullptr, nullptr, false, &t->db, nullptr, batch, nullptr, &pre, esc);
+    rc = upload_device_packed(ctx, spec, UploadSource::of(batch, esc), &pre, &t->db);
     if (!rc && spec.up_stream) {
         hipError_t e = hipEventRecord(ctx->ev_packed, spec.up_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ev_packed, 0);
@@ -2491,7 +2493,7 @@ static int upload_compact(avk_ctx *ctx, const CallSpec &spec, const avk_compact_
     *out = nullptr;
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    return upload_device_packed(ctx, spec, nullptr, batch, false, out);
+    return upload_device_packed(ctx, spec, UploadSource::of(batch), nullptr, out);
 }
 int avk_batch_upload_compact(avk_ctx *ctx, const avk_compact_batch *batch, avk_dev_batch **out) { return ctx ? upload_compact(ctx, call_spec(ctx), batch, out) : AVK_E_ARG; }
 
@@ -2500,7 +2502,7 @@ static int upload_packed(avk_ctx *ctx, const CallSpec &spec, const avk_packed_ba
     *out = nullptr;
     if (!ctx->d_ref) return fail(ctx, AVK_E_STATE, "avk_ref_upload has not been called");
     AVK_HIP(ctx, hipSetDevice(ctx->device));
-    return upload_device_packed(ctx, spec, nullptr, nullptr, false, out, nullptr, batch, nullptr, nullptr, esc);
+    return upload_device_packed(ctx, spec, UploadSource::of(batch, esc), nullptr, out);
 }
 int avk_batch_upload_packed_esc(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, avk_dev_batch **out) {
     return ctx ? upload_packed(ctx, call_spec(ctx), batch, esc, out) : AVK_E_ARG;
@@ -3339,7 +3341,7 @@ static int merge_batch_internal(avk_ctx *ctx, const avk_multi_batch *mb, const a
         avk_dev_batch *db = nullptr;
         CallSpec spec = call_spec(ctx);
         spec.emit_gm = false; /* the pair solve writes no metric blocks */
-        int rc = upload_device_packed(ctx, spec, nullptr, nullptr, true, &db, mb, nullptr, pm, nullptr, esc);
+        int rc = upload_device_packed(ctx, spec, pm ? UploadSource::of(pm, *mb, esc) : UploadSource::of(mb), nullptr, &db);
         if (rc) return rc;
         avk_compare_config pcfg;
         pcfg.max_branch_factor = cfg->max_branch_factor, pcfg.enable_sequences = 0, pcfg.enable_exact_shortcut = 0;

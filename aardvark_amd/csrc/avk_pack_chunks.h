@@ -1,5 +1,6 @@
 /*
- * avk_pack_chunks.h — the chunk plan of a packed compare call whose region pass runs under its copies (context option pack_chunks; avk_devpack_host.inl).
+ * avk_pack_chunks.h — the chunk plan of a packed compare call whose region pass runs under its copies (context option pack_chunks; Upload::copy_packed_chunked
+ * of avk_upload.inl queues it, avk_dp_region_chunk_kernel of avk_devpack_host.inl runs it).
  *
  * Plain C++, no HIP: the host cuts the batch, the region pass's workgroups evaluate the ownership rule, and tests/native/pack_chunks_check.cpp sweeps both on the CPU.
  *

@@ -303,7 +303,7 @@ void lane_main(void *p, int /*lane*/) {
     } else avk::region_worker<false, true>(*t->args, t->wave_id, nullptr);
 }
 
-/* ---- the device-side packer (aardvark_amd/csrc/avk_devpack.inl) run the way upload_device_packed of avk_devpack_host.inl queues it: the same
+/* ---- the device-side packer (aardvark_amd/csrc/avk_devpack.inl) run the way upload_device_packed of avk_upload.inl queues it: the same
  * device functions, the workgroup-level plumbing (histogram, scans, scatter) as plain loops */
 uint64_t g_last_pair_regions = 0; /* emu_last_pair_regions: regions of the last emulated call that went through the lookup of avk_pairs.inl */
 uint32_t g_hbm_ed_cap = 1024; /* emu_set_hbm_ed_cap: context option hbm_ed_cap */
