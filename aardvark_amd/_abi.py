@@ -191,6 +191,37 @@ def declare_submit_strata(lib):
     lib.avk_compare_packed_submit_strata.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkResultBatch), _p(C.c_uint64), _p(vp)]
 
 
+BOOT_MAX_REPLICATES, BOOT_MAX_BLOCKS = 4096, 16384
+
+
+class AvkBootSpec(C.Structure):
+    """avk_boot_spec: the bootstrap replicates of a call (aardvark_amd/csrc/avk_boot.h has the rule)"""
+    _fields_ = [("replicates", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class BootSpec:
+    """`replicates` Poisson-bootstrap replicates of the tallies (1 .. 4096; with a strata handle of L labels (1 + L) * replicates <= 16384), drawn with `seed`"""
+
+    def __init__(self, replicates, seed=1):
+        self.replicates, self.seed = int(replicates), int(seed)
+
+    def c_struct(self):
+        return AvkBootSpec(self.replicates, self.seed & 0xFFFFFFFFFFFFFFFF)
+
+
+def declare_boot(lib):
+    """avk_boot_block, avk_boot_tallies, avk_compare_packed_boot, avk_boot_tallies_host (include/aardvark_amd.h)"""
+    vp, u64p = C.c_void_p, _p(C.c_uint64)
+    lib.avk_boot_block.restype = C.c_uint32
+    lib.avk_boot_block.argtypes = [vp]
+    lib.avk_boot_tallies.restype = C.c_int
+    lib.avk_boot_tallies.argtypes = [vp, vp, _p(AvkBootSpec), vp, u64p]
+    lib.avk_compare_packed_boot.restype = C.c_int
+    lib.avk_compare_packed_boot.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkResultBatch), u64p, _p(AvkBootSpec), u64p]
+    lib.avk_boot_tallies_host.restype = C.c_int
+    lib.avk_boot_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkBootSpec), _p(AvkRegionLabels), C.c_uint32, u64p]
+
+
 CONTEXT_PAD_MAX, CONTEXT_GC_EDGES_MAX, CONTEXT_HP_EDGES_MAX = 1024, 17, 16
 
 

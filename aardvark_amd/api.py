@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
-                   PackedBatch, RegionBatch, ResultBatch, ContextSpec, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
+                   PackedBatch, RegionBatch, ResultBatch, BootSpec, ContextSpec, declare_boot, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
                    region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -90,6 +90,8 @@ def load_library():
         declare_submit_strata(lib)
     if hasattr(lib, "avk_strata_upload_context"):  # sequence-context labels behind the sets' (avk_context.inl); (AVK_LIB may name an older in-tree build: A/B runs)
         declare_context_strata(lib)
+    if hasattr(lib, "avk_boot_tallies"):  # bootstrap replicates of the tallies (avk_boot.inl); (AVK_LIB may name an older in-tree build: A/B runs)
+        declare_boot(lib)
     if hasattr(lib, "avk_debug_ref_packed"):  # (AVK_LIB may name an older in-tree build: A/B runs)
         declare_debug_ref_packed(lib)
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
@@ -304,14 +306,29 @@ class Context:
         esc = None if pbatch.escapes is None else pbatch.escapes.pinned(self.host_array)
         return PackedBatch(escapes=esc, **{f: pin(getattr(pbatch, f)) for f in PackedBatch.FIELDS})
 
-    def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None, strata=None):
+    def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None, strata=None, boot=None, boot_tallies=None):
         """avk_compare_packed: solve_compare_region for every region of a batch in the packed form -> ResultBatch (indexed like the packed arrays).
         labels=(n_labels, label_off, label_idx): avk_compare_packed_labels — the per-label sums come back as res.label_tallies, a [n_labels, TALLY_LEN] uint64
         array (label_tallies: an array of that shape the sums are added to instead).
-        strata=a Strata handle (upload_strata): avk_compare_packed_strata — the same sums, the lists made on the device"""
+        strata=a Strata handle (upload_strata): avk_compare_packed_strata — the same sums, the lists made on the device.
+        boot=a BootSpec: avk_compare_packed_boot — the bootstrap replicates come back as res.boot_tallies, a [1 + n_labels, replicates, TALLY_LEN] uint64 array
+        (scope 0: every region; scope 1 + l: label l of `strata`; boot_tallies: an array of that shape the sums are added to instead)"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
         pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
+        if boot is not None and boot.replicates:
+            if labels is not None:
+                raise ValueError("boot takes strata, not label lists")
+            n_labels = 0 if strata is None else strata.n_labels
+            sums = np.zeros((n_labels, TALLY_LEN), np.uint64) if label_tallies is None else label_tallies
+            reps = np.zeros((1 + n_labels, boot.replicates, TALLY_LEN), np.uint64) if boot_tallies is None else boot_tallies
+            bs = boot.c_struct()
+            self._check(self.lib.avk_compare_packed_boot(self.handle, C.byref(pb), None if esc is None else C.byref(esc), None if strata is None else strata.handle, C.byref(cfg),
+                                                         C.byref(ro), sums.ctypes.data_as(u64p), C.byref(bs), reps.ctypes.data_as(u64p)))
+            if strata is not None:
+                res.label_tallies = sums
+            res.boot_tallies = reps
+            return res
         if strata is not None:
             if labels is not None:
                 raise ValueError("labels and strata exclude each other")
@@ -483,6 +500,19 @@ class Context:
         """avk_label_tallies_strata: label_tallies_compact with the lists made on the device from the resident sets; returns / adds to [n_labels, TALLY_LEN]"""
         out = np.zeros((strata.n_labels, TALLY_LEN), np.uint64) if out is None else out
         self._check(self.lib.avk_label_tallies_strata(self.handle, rb.handle, strata.handle, out.ctypes.data_as(u64p)))
+        return out
+
+    def boot_block(self):
+        """avk_boot_block: how many replicates of one scope a launch of the bootstrap kernel holds (more replicates or scopes: more launches)"""
+        return int(self.lib.avk_boot_block(self.handle))
+
+    def boot_tallies(self, rb, spec, strata=None, out=None):
+        """avk_boot_tallies: the bootstrap replicates of a solved resident batch (needs emit_bp_groups during compare_resident); returns / adds to a
+        [1 + n_labels, replicates, TALLY_LEN] uint64 array — scope 0: every region; scope 1 + l: label l of `strata`"""
+        n_labels = 0 if strata is None else strata.n_labels
+        out = np.zeros((1 + n_labels, max(spec.replicates, 0), TALLY_LEN), np.uint64) if out is None else out
+        bs = spec.c_struct()
+        self._check(self.lib.avk_boot_tallies(self.handle, rb.handle, C.byref(bs), None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
         return out
 
     def synchronize(self):

@@ -44,6 +44,7 @@
 #include "avk_labels.inl"
 #include "avk_strata.inl"
 #include "avk_context.inl"
+#include "avk_boot.inl"
 #include "avk_mergecount.inl"
 #include "avk_mergesweep.inl"
 static_assert((int)avk::ms::MS_KMAX == (int)avk::dp::DP_MERGE_KMAX, "the sweep kernel decides what the classification kernel decides");
@@ -3016,10 +3017,17 @@ struct LabelStage {
     const avk_strata *st;
     uint64_t *sums; /* the caller's [n_labels * AVK_TALLY_LEN]: gains the sums */
 };
+/* ... and the bootstrap replicates behind the download (avk_compare_packed_boot): the capacity retry has patched the device view by then, so the regions it
+ * repaired are counted by the same kernel; the scopes' masks are those of the upload's count pass */
+struct BootStage {
+    const avk_boot_spec *spec;
+    uint64_t *sums; /* the caller's [(1 + n_labels) * replicates * AVK_TALLY_LEN]: gains the sums */
+};
+static int boot_sums_run(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *bs, uint32_t n_labels, const uint32_t *d_mask, uint64_t *out);
 static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_result_batch *out, uint64_t n, const char *timed_as,
-                            const std::function<int(const CallSpec &, avk_dev_batch **)> &upload, const LabelStage *ls = nullptr) {
+                            const std::function<int(const CallSpec &, avk_dev_batch **)> &upload, const LabelStage *ls = nullptr, const BootStage *boot = nullptr) {
     ctx->last_one_shot = 0;
-    CallSpec spec = call_spec(ctx, out, ls != nullptr); /* (the groups are what the label kernel reads, whether the caller asked for them or not) */
+    CallSpec spec = call_spec(ctx, out, ls != nullptr || boot != nullptr); /* (the groups are what the label kernel reads, whether the caller asked for them or not) */
     const uint32_t n_labels = !ls ? 0 : ls->st ? ls->st->n_labels : ls->lab->n_labels;
     std::vector<uint64_t> host((size_t)n_labels * AVK_TALLY_LEN, 0);
     avk_dev_batch *db = nullptr;
@@ -3060,6 +3068,7 @@ static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_res
     const auto t3 = std::chrono::steady_clock::now();
     const uint64_t n_strata_idx = L.total;
     if (ls) (void)hipStreamSynchronize(ctx->stream);
+    if (!rc && boot) rc = boot_sums_run(ctx, db, boot->spec, job.st ? job.st->n_labels : 0, (const uint32_t *)L.d_mask, boot->sums);
     strata_lists_release(ctx, L);
     pool_release(ctx, d_out);
     if (db) {
@@ -3126,6 +3135,164 @@ int avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, const
     if (!esc_present(esc)) esc = nullptr;
     const LabelStage ls{nullptr, st, label_tallies};
     return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, &ls);
+}
+
+/* ---- bootstrap replicates of the tallies (avk_boot.h, avk_boot.inl) ----------------------------------------------------------------------------------- */
+static_assert(AVK_BT_REPS * AVK_BT_SLOT <= AVK_BT_THREADS && AVK_BT_SLOT >= AVK_N_FIELDS + 1 && AVK_N_GROUPS <= 32, "a workgroup of avk_boot_tally_kernel holds its lanes and a slot its words");
+/* the refusals of every entry point with a spec, before anything is queued (no device involved) */
+static int boot_spec_check(avk_ctx *ctx, const avk_boot_spec *bs, uint32_t n_labels, const uint64_t *out) {
+    if (bs->replicates < 1 || bs->replicates > AVK_BOOT_MAX_REPLICATES) return fail(ctx, AVK_E_ARG, "bootstrap: %u replicates, 1 to %u are possible", bs->replicates, AVK_BOOT_MAX_REPLICATES);
+    if (((uint64_t)n_labels + 1) * bs->replicates > AVK_BOOT_MAX_BLOCKS)
+        return fail(ctx, AVK_E_ARG, "bootstrap: %u replicates of 1 + %u scopes are more than %u blocks", bs->replicates, n_labels, AVK_BOOT_MAX_BLOCKS);
+    if (!out) return fail(ctx, AVK_E_ARG, "boot_tallies missing");
+    return 0;
+}
+/* the kernel over the scopes and the blocks of replicates, on stream s behind whatever wrote the batch's results: d_out[(1 + n_labels) * B * AVK_TALLY_LEN] gains the sums */
+static int boot_launch(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *bs, uint32_t n_labels, const uint32_t *d_mask, uint64_t *d_out, hipStream_t s) {
+    const uint64_t n = db->n_regions;
+    if (!n) return 0;
+    avk::lb::LbView v;
+    memset(&v, 0, sizeof(v));
+    v.in = db->dp_args.in, v.vinfo = db->dp_args.vinfo, v.region_out = db->d_region_out, v.var_out = db->d_var_out, v.v_off = db->d_voff, v.bp_off = db->d_bp_off, v.bp = db->d_bp;
+    /* as many workgroups as a CU keeps resident (avk_boot.inl: one, at 131 registers a lane); more would only add flushes */
+    uint64_t blocks = (n + AVK_BT_TILE - 1) / AVK_BT_TILE;
+    if (blocks > (uint64_t)ctx->n_cus * AVK_BT_WG_PER_CU) blocks = (uint64_t)ctx->n_cus * AVK_BT_WG_PER_CU;
+    const unsigned long long seed_mix = avk_boot_mix(bs->seed);
+    const uint32_t B = bs->replicates;
+    for (uint32_t scope = 0; scope <= (d_mask ? n_labels : 0u); ++scope)
+        for (uint32_t lo = 0; lo < B; lo += AVK_BT_REPS) {
+            const uint32_t hi = B - lo > AVK_BT_REPS ? lo + AVK_BT_REPS : B;
+            hipLaunchKernelGGL(avk_boot_tally_kernel, dim3((unsigned)blocks), dim3(AVK_BT_THREADS), 0, s, v, d_mask, (uint32_t)n, scope, seed_mix, B, lo, hi, (unsigned long long *)d_out);
+            AVK_HIP(ctx, hipGetLastError());
+        }
+    return 0;
+}
+/* sums cleared, kernels, copy back, wait, added to the caller's: on the context's stream */
+static int boot_sums_run(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *bs, uint32_t n_labels, const uint32_t *d_mask, uint64_t *out) {
+    if (!d_mask) n_labels = 0;
+    const size_t words = ((size_t)n_labels + 1) * bs->replicates * AVK_TALLY_LEN;
+    std::vector<uint64_t> host(words, 0);
+    void *d_out = nullptr;
+    int rc = pool_alloc(ctx, &d_out, words * 8);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
+    if (!rc && e == hipSuccess) rc = boot_launch(ctx, db, bs, n_labels, d_mask, (uint64_t *)d_out, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    pool_release(ctx, d_out);
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(ctx, AVK_E_HIP, "bootstrap tallies failed: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    for (size_t k = 0; k < words; ++k) out[k] += host[k];
+    return 0;
+}
+
+uint32_t avk_boot_block(const avk_ctx *ctx) { return ctx ? AVK_BT_REPS : 0; }
+
+int avk_boot_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *bs, const avk_strata *st, uint64_t *out) {
+    if (!ctx || !db || !bs) return AVK_E_ARG;
+    {
+        const int rb = boot_spec_check(ctx, bs, st ? st->n_labels : 0, out);
+        if (rb) return rb;
+    }
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    if (!db->dev_packed) return fail(ctx, AVK_E_STATE, "bootstrap tallies on the device need a device-packed batch: the option device_pack was 0 at its upload (host route: avk_boot_tallies_host)");
+    if (!db->has_run || db->last_mode != 0) return fail(ctx, AVK_E_STATE, "bootstrap tallies need a batch that avk_compare_resident has solved");
+    if (!db->bp_valid) return fail(ctx, AVK_E_STATE, "the batch has no BASEPAIR groups on the device: set emit_bp_groups before avk_compare_resident");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = db->n_regions;
+    StrataLists L;
+    int rc = 0;
+    if (st && st->n_labels && n) { /* the scopes' membership: the strata pass's masks, nothing else of the lists */
+        rc = strata_lists_alloc(ctx, st, n, L);
+        if (!rc) {
+            const hipError_t e = strata_mask_launch(st, db->dp_args.in, n, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums, ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata masks failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (!rc) rc = boot_sums_run(ctx, db, bs, L.d_mask ? st->n_labels : 0, (const uint32_t *)L.d_mask, out);
+    else (void)hipStreamSynchronize(ctx->stream);
+    strata_lists_release(ctx, L);
+    return rc;
+}
+
+int avk_compare_packed_boot(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg, avk_result_batch *out,
+                            uint64_t *label_tallies, const avk_boot_spec *bs, uint64_t *boot_tallies) {
+    if (!bs || bs->replicates == 0) return avk_compare_packed_strata(ctx, batch, esc, st, cfg, out, label_tallies); /* the call without a spec, launch for launch */
+    if (!batch) return AVK_E_ARG;
+    if (st && st->n_labels == 0) st = nullptr;
+    {
+        const int rb = boot_spec_check(ctx, bs, st ? st->n_labels : 0, boot_tallies);
+        if (rb) return rb;
+    }
+    if (st && !label_tallies) return fail(ctx, AVK_E_ARG, "label_tallies missing");
+    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->device_pack) return fail(ctx, AVK_E_STATE, "bootstrap tallies on the device need the option device_pack (host route: avk_boot_tallies_host)");
+    if (!esc_present(esc)) esc = nullptr;
+    const LabelStage ls{nullptr, st, label_tallies};
+    const BootStage boot{bs, boot_tallies};
+    return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, st ? &ls : nullptr,
+                            &boot);
+}
+
+int avk_boot_tallies_host(const avk_region_batch *b, const avk_result_batch *res, const avk_boot_spec *bs, const avk_region_labels *lab, uint32_t threads, uint64_t *out) {
+    if (!b || !res || !bs) return fail(nullptr, AVK_E_ARG, "bootstrap: batch, results or spec missing");
+    const uint32_t n_labels = lab ? lab->n_labels : 0;
+    {
+        const int rb = boot_spec_check(nullptr, bs, n_labels, out);
+        if (rb) return rb;
+        if (lab && n_labels) {
+            const int rl = labels_check(nullptr, b->n_regions, lab, out);
+            if (rl) return rl;
+        }
+    }
+    if (!(res->status || res->region_packed)) return fail(nullptr, AVK_E_ARG, "bootstrap: the results have neither status nor region_packed");
+    if (b->n_regions && !b->start) return fail(nullptr, AVK_E_ARG, "bootstrap: the batch has no start array");
+    const uint64_t n = b->n_regions;
+    const uint32_t B = bs->replicates;
+    const size_t words = ((size_t)n_labels + 1) * B * AVK_TALLY_LEN;
+    /* every thread sums into a block of its own: at most 64 of them, and no more than keep those blocks within 1 GiB */
+    uint32_t T = threads < 1 ? 1u : (threads > 64u ? 64u : threads);
+    while (T > 1 && (uint64_t)T * words * 8 > (1ull << 30)) --T;
+    std::vector<std::vector<uint64_t>> part(T);
+    std::vector<int> bad(T, 0);
+    auto work = [&](uint32_t t) {
+        std::vector<uint64_t> &acc = part[t];
+        acc.assign(words, 0);
+        uint32_t blk[AVK_N_GROUPS * AVK_N_FIELDS];
+        std::vector<uint8_t> w(B);
+        for (uint64_t r = n * t / T; r < n * (t + 1) / T; ++r) {
+            const uint32_t status = res->status ? (uint32_t)res->status[r] : avk_rp_status(res->region_packed[r]);
+            if (status != 0) continue;
+            if (avk_group_metrics_from_compact(b, r, res, blk)) {
+                bad[t] = 1;
+                return;
+            }
+            const uint64_t h = avk_boot_region_hash(bs->seed, avk_boot_key(b->contig_idx ? b->contig_idx[r] : 0u, (uint32_t)b->start[r]));
+            for (uint32_t k = 0; k < B; ++k) w[k] = (uint8_t)avk_boot_weight_of_hash(h, k);
+            auto add = [&](uint32_t scope) {
+                for (uint32_t k = 0; k < B; ++k) {
+                    if (!w[k]) continue;
+                    uint64_t *dst = acc.data() + ((size_t)scope * B + k) * AVK_TALLY_LEN;
+                    for (int i = 0; i < AVK_N_GROUPS * AVK_N_FIELDS; ++i) dst[i] += (uint64_t)w[k] * blk[i];
+                    dst[AVK_TALLY_SOLVED] += w[k];
+                }
+            };
+            add(0);
+            if (n_labels)
+                for (uint64_t q = lab->label_off[r]; q < lab->label_off[r + 1]; ++q) add(1u + lab->label_idx[q]);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < T; ++t) pool.emplace_back(work, t);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    for (uint32_t t = 0; t < T; ++t)
+        if (bad[t]) return fail(nullptr, AVK_E_ARG, "bootstrap: avk_group_metrics_from_compact refused a region (per-call outputs and BASEPAIR groups are needed)");
+    for (uint32_t t = 0; t < T; ++t)
+        for (size_t k = 0; k < words; ++k) out[k] += part[t][k];
+    return 0;
 }
 
 int avk_compare_packed_submit_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg,

@@ -40,7 +40,9 @@ void usage() {
             "  [--max-branch-factor 50] [--enable-exact-shortcut] [--enable-haplotype-metrics] [--enable-weighted-haplotype-metrics]\n"
             "  [--enable-record-basepair-metrics] [-s STRAT.tsv] [--output-debug DIR] [--skip N] [--take N] [--device 0 | --devices 0,1,..] [--batch-regions 4000000] [--batch-form packed|wide]\n"
             "  [--context-strata gc|hp|gc,hp]  (GC-content bins and homopolymer classes as further region labels, made on the GPU from the reference alone; with or without -s;\n"
-            "   packed feed and --strat-lists device only)  [--context-gc-edges 0,15,..,101] [--context-gc-pad 50] [--context-hp-edges 4,7,12,21] [--context-hp-pad 5]\n");
+            "   packed feed and --strat-lists device only)  [--context-gc-edges 0,15,..,101] [--context-gc-pad 50] [--context-hp-edges 4,7,12,21] [--context-hp-pad 5]\n"
+            "  [--bootstrap B]  (B Poisson-bootstrap replicates of the tallies, 1..4096, summed on the GPU; writes summary_ci.tsv: summary.tsv's rows with percentile intervals of\n"
+            "   recall, precision and F1; default 0: off, no file)  [--bootstrap-seed 1] [--bootstrap-level 90|95|99 (default 95)]\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -89,6 +91,10 @@ int main(int argc, char **argv) {
     bool cx_gc = false, cx_hp = false, cx_given = false, cx_override = false;
     std::vector<uint32_t> cx_gc_edges = {0, 15, 20, 25, 30, 55, 60, 65, 70, 75, 80, 85, 101}, cx_hp_edges = {4, 7, 12, 21};
     uint32_t cx_gc_pad = 50, cx_hp_pad = 5;
+    /* --bootstrap: replicates of the tallies (avk_boot_spec) and the level of summary_ci.tsv's intervals */
+    avk_boot_spec boot_spec = {0, 1};
+    uint32_t boot_level = 95;
+    bool boot_override = false;
     auto number_list = [](const std::string &opt, const std::string &list) {
         std::vector<uint32_t> out;
         for (size_t b = 0; b <= list.size();) {
@@ -169,6 +175,20 @@ int main(int argc, char **argv) {
         else if (a == "--context-hp-edges") cx_hp_edges = number_list(a, val()), cx_override = true;
         else if (a == "--context-gc-pad") cx_gc_pad = number_list(a, val())[0], cx_override = true;
         else if (a == "--context-hp-pad") cx_hp_pad = number_list(a, val())[0], cx_override = true;
+        else if (a == "--bootstrap") {
+            const std::vector<uint32_t> v = number_list(a, val());
+            if (v.size() != 1 || v[0] > AVK_BOOT_MAX_REPLICATES) die(64, "--bootstrap takes a number of replicates from 0 (off) to 4096", "");
+            boot_spec.replicates = v[0];
+        } else if (a == "--bootstrap-seed") {
+            const char *v = val();
+            char *end = nullptr;
+            boot_spec.seed = strtoull(v, &end, 10), boot_override = true;
+            if (!*v || *end) die(64, "invalid value for --bootstrap-seed", v);
+        } else if (a == "--bootstrap-level") {
+            const std::vector<uint32_t> v = number_list(a, val());
+            if (v.size() != 1 || (v[0] != 90 && v[0] != 95 && v[0] != 99)) die(64, "--bootstrap-level takes 90, 95 or 99", "");
+            boot_level = v[0], boot_override = true;
+        }
         else if (a == "-h" || a == "--help") {
             usage();
             return 0;
@@ -204,6 +224,13 @@ int main(int argc, char **argv) {
         if (avk_context_label_name(&cx_spec, 0, name, sizeof(name))) die(64, "--context-strata", avk_last_error(nullptr)); /* (the library's own check of the spec) */
         n_ctx_labels = (cx_spec.n_gc_edges ? cx_spec.n_gc_edges - 1 : 0) + cx_spec.n_hp_edges;
     }
+    /* The replicates are summed where the blocks are: by kernel behind the packed call (avk_compare_packed_boot; labels from the sets resident on the GPU), or on the
+     * host from the wide feed's results (avk_boot_tallies_host).  What neither route carries is refused here, by name. */
+    const bool boot = boot_spec.replicates != 0;
+    if (boot_override && !boot) die(64, "--bootstrap-seed and --bootstrap-level need --bootstrap", "");
+    if (boot && !debug_dir.empty()) die(64, "--bootstrap cannot be combined with --output-debug (the debug run writes per-region tables, not replicates)", "");
+    if (boot && !strat_tsv.empty() && strat_lists == "host" && want_packed)
+        die(64, "--bootstrap on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
     if (!devices.empty()) device = devices[0];
     if (mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create output folder", out_dir.c_str());
     if (!debug_dir.empty() && mkdir(debug_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create debug folder", debug_dir.c_str());
@@ -290,6 +317,8 @@ int main(int argc, char **argv) {
     avf_strat *strat = nullptr;
     if (!strat_tsv.empty() && avf_strat_load(strat_tsv.c_str(), &strat)) die(74, "Error while loading stratifications", avf_last_error());
     const uint32_t n_bed_labels = avf_strat_n_labels(strat), n_labels = n_bed_labels + n_ctx_labels; /* the sets' labels, then the context labels */
+    if (boot && ((uint64_t)n_labels + 1) * boot_spec.replicates > AVK_BOOT_MAX_BLOCKS)
+        die(64, "--bootstrap: replicates x (1 + region labels) may not exceed 16384 blocks", "");
 
     /* the reference goes to the GPU (upload + 2-bit packing) while the regions are walked */
     t0 = std::chrono::steady_clock::now();
@@ -377,6 +406,29 @@ int main(int argc, char **argv) {
         avk_result_batch shifted = out_for(out, v_first);
         return avk_compare_packed_strata(c, &part, &part_esc, sets, &cfg, &shifted, sums);
     };
+    /* --bootstrap on the packed feed: compare_part / compare_part_strata that also add the part's replicates to `reps` (avk_compare_packed_boot; sets may be NULL) */
+    auto compare_part_boot = [&](avk_ctx *c, uint64_t at_abs, uint64_t n, const avk_compare_config &cfg, const avk_result_batch &out, const avk_strata *sets, uint64_t *sums,
+                                 uint64_t *reps) -> int {
+        avk_packed_batch part;
+        avk_packed_escapes part_esc;
+        uint64_t v_first = 0;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, &v_first)) return AVK_E_ARG;
+        avk_result_batch shifted = out_for(out, v_first);
+        return avk_compare_packed_boot(c, &part, &part_esc, sets, &cfg, &shifted, sums, &boot_spec, reps);
+    };
+    /* --bootstrap on the wide feed: the part's replicates from its results on the host (avk_boot_tallies_host: `out` carries the compact BASEPAIR groups) */
+    struct HostGroups {
+        std::vector<uint32_t> off, groups;
+    };
+    auto host_groups = [&](uint64_t n, avk_result_batch &out, HostGroups &g) {
+        g.off.assign(n + 1, 0), g.groups.assign(4 * (size_t)(n + all->n_variants + 1), 0);
+        out.bp_off = g.off.data(), out.bp_groups = g.groups.data();
+    };
+    auto boot_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *reps) -> int {
+        avk_region_labels lab;
+        lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
+        return avk_boot_tallies_host(&b, &out, &boot_spec, n_labels ? &lab : nullptr, 16, reps);
+    };
     auto upload_part = [&](avk_ctx *c, const avk_region_batch &b, uint64_t at_abs, uint64_t n, avk_dev_batch **db, uint64_t *v_first) -> int {
         *v_first = 0;
         if (!packed) return avk_batch_upload(c, &b, db);
@@ -434,7 +486,15 @@ int main(int argc, char **argv) {
             strata_route = false;
         }
     }
+    if (boot && packed && n_labels && !strata_route) die(70, "--bootstrap on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
+    const bool boot_host = boot && !packed; /* the wide feed: avk_boot_tallies_host on each part's results */
     (void)avk_ctx_set_option(ctx, "emit_group_metrics", (n_labels && !compact_labels) || debug ? 1 : 0);
+    if (boot_host) (void)avk_ctx_set_option(ctx, "emit_bp_groups", 1);
+    std::vector<uint64_t> boot_total(boot ? ((size_t)n_labels + 1) * boot_spec.replicates * AVK_TALLY_LEN : 0, 0);
+    if (verbosity && boot)
+        fprintf(stderr, "Bootstrap: %u replicates, seed %llu, %u %% intervals in summary_ci.tsv; the replicates are summed %s.\n", boot_spec.replicates,
+                (unsigned long long)boot_spec.seed, boot_level,
+                boot_host ? "on the host from each batch's results (avk_boot_tallies_host, the wide feed)" : "on the GPU behind each batch's solve (avk_compare_packed_boot)");
     if (verbosity && compact_labels) {
         if (strata_route)
             fprintf(stderr, "Region labels: listed on the GPU (--strat-lists device, avk_compare_packed_strata): %llu intervals of %u labels uploaded once per context.\n",
@@ -477,7 +537,9 @@ int main(int argc, char **argv) {
                 !packed ? "wide" : escaped ? "packed with escapes" : "packed", (unsigned long long)esc_all.n_esc_regions, (unsigned long long)esc_all.n_esc_slots,
                 (unsigned long long)esc_all.n_esc_calls, n_workers, n_workers == 1 ? " solves" : "s solve");
     bool sharded = false;
-    if (n_workers > 1 && packed && !n_labels) {
+    if (verbosity && boot && n_workers > 1 && packed && !n_labels)
+        fprintf(stderr, "Bootstrap: the hash-sharded route does not carry the replicates; --bootstrap selects the route on which the contexts share the region batches.\n");
+    if (n_workers > 1 && packed && !n_labels && !boot) {
         sharded = true;
         avk_packed_batch sel;
         avk_packed_escapes sel_esc;
@@ -600,7 +662,7 @@ int main(int argc, char **argv) {
         std::atomic<uint64_t> next_batch{0};
         std::vector<std::string> worker_err(n_workers);
         std::vector<std::vector<uint64_t>> w_total(n_workers, std::vector<uint64_t>(AVK_TALLY_LEN, 0)),
-            w_strat(n_workers, std::vector<uint64_t>((size_t)n_labels * AVK_TALLY_LEN, 0));
+            w_strat(n_workers, std::vector<uint64_t>((size_t)n_labels * AVK_TALLY_LEN, 0)), w_boot(n_workers, std::vector<uint64_t>(boot_total.size(), 0));
         std::mutex log_mutex;
         auto worker = [&](size_t w) {
             avk_ctx *my = ctx;
@@ -623,6 +685,7 @@ int main(int argc, char **argv) {
                     return;
                 }
                 (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels && !compact_labels ? 1 : 0);
+                if (boot_host) (void)avk_ctx_set_option(my, "emit_bp_groups", 1);
             }
             avk_strata *my_sets = w > 0 ? nullptr : strata;
             if (w > 0 && strata_route && cx_given && strata_upload(my, &my_sets)) { /* (context labels: no host route) */
@@ -634,6 +697,11 @@ int main(int argc, char **argv) {
                 std::lock_guard<std::mutex> lock(log_mutex);
                 fprintf(stderr, "Warning: cannot upload the stratification sets to context %zu: %s; its region labels are listed on the host.\n", w, avk_last_error(my));
                 my_sets = nullptr;
+                if (boot) { /* (the replicates' scopes are read from the sets on the GPU) */
+                    worker_err[w] = "--bootstrap: cannot upload the stratification sets to every context";
+                    avk_ctx_destroy(my);
+                    return;
+                }
             }
             std::vector<uint64_t> w_tally(AVK_TALLY_LEN);
             for (uint64_t bi = next_batch.fetch_add(1); bi < n_batches; bi = next_batch.fetch_add(1)) {
@@ -657,7 +725,10 @@ int main(int argc, char **argv) {
                 out.var_observed = var_observed.data();
                 out.var_class = var_class.data();
                 int rc = 0;
-                if (strata_route && my_sets) rc = compare_part_strata(my, first + at, n, cfg, out, my_sets, w_strat[w].data());
+                HostGroups hg;
+                if (boot_host) host_groups(n, out, hg);
+                if (boot && packed) rc = compare_part_boot(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data());
+                else if (strata_route && my_sets) rc = compare_part_strata(my, first + at, n, cfg, out, my_sets, w_strat[w].data());
                 else if (n_labels) {
                     std::vector<uint64_t> label_off(n + 1, 0);
                     std::vector<uint32_t> label_idx;
@@ -680,8 +751,18 @@ int main(int argc, char **argv) {
                         if (!rc) rc = avk_results_download(my, db, &shifted);
                         if (!rc) rc = avk_label_tallies(my, db, n_labels, label_off.data(), label_idx.data(), w_strat[w].data());
                         if (db) avk_batch_free(my, db);
+                        if (!rc && boot_host && boot_part_host(b, out, label_off.data(), label_idx.data(), w_boot[w].data())) {
+                            worker_err[w] = std::string("bootstrap tallies failed: ") + avk_last_error(nullptr);
+                            break;
+                        }
                     }
-                } else rc = compare_part(my, b, first + at, n, cfg, out);
+                } else {
+                    rc = compare_part(my, b, first + at, n, cfg, out);
+                    if (!rc && boot_host && boot_part_host(b, out, nullptr, nullptr, w_boot[w].data())) {
+                        worker_err[w] = std::string("bootstrap tallies failed: ") + avk_last_error(nullptr);
+                        break;
+                    }
+                }
                 if (rc) {
                     worker_err[w] = std::string("compare failed: ") + avk_last_error(my);
                     break;
@@ -707,6 +788,7 @@ int main(int argc, char **argv) {
         for (size_t w = 0; w < n_workers; ++w) {
             for (size_t k = 0; k < (size_t)AVK_TALLY_LEN; ++k) total[k] += w_total[w][k];
             for (size_t k = 0; k < strat_total.size(); ++k) strat_total[k] += w_strat[w][k];
+            for (size_t k = 0; k < boot_total.size(); ++k) boot_total[k] += w_boot[w][k]; /* the contexts' blocks, added on the host */
         }
     }
     for (uint64_t at = 0; n_workers == 1 && at < count; at += batch_regions) {
@@ -748,7 +830,11 @@ int main(int argc, char **argv) {
             out.seq_stride = seq_stride.data();
             out.seq_len = seq_len.data();
         }
-        if (strata_route) { /* one call: the batch goes in, the sums come back with the results; the lists never exist on the host */
+        HostGroups hg;
+        if (boot_host) host_groups(n, out, hg);
+        if (boot && packed) { /* the one call that also returns the replicates (with the sets' handle: the labels' sums and scopes) */
+            if (compare_part_boot(ctx, first + at, n, cfg, out, strata_route ? strata : nullptr, strat_total.data(), boot_total.data())) die(70, "compare failed", avk_last_error(ctx));
+        } else if (strata_route) { /* one call: the batch goes in, the sums come back with the results; the lists never exist on the host */
             if (compare_part_strata(ctx, first + at, n, cfg, out, strata, strat_total.data())) die(70, "compare failed", avk_last_error(ctx));
         } else if (compact_labels) { /* one call: the lists go in with the batch, the sums come back with the results */
             std::vector<uint64_t> label_off(n + 1, 0);
@@ -782,7 +868,11 @@ int main(int argc, char **argv) {
             if (rc_labels) die(70, "cannot list the region labels", avf_last_error());
             if (avk_label_tallies(ctx, db, n_labels, label_off.data(), label_idx.data(), strat_total.data())) die(70, "stratified tallies failed", avk_last_error(ctx));
             avk_batch_free(ctx, db);
-        } else if (compare_part(ctx, b, first + at, n, cfg, out)) die(70, "compare failed", avk_last_error(ctx));
+            if (boot_host && boot_part_host(b, out, label_off.data(), label_idx.data(), boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
+        } else {
+            if (compare_part(ctx, b, first + at, n, cfg, out)) die(70, "compare failed", avk_last_error(ctx));
+            if (boot_host && boot_part_host(b, out, nullptr, nullptr, boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
+        }
         for (size_t k = 0; k < (size_t)AVK_TALLY_LEN; ++k) total[k] += tally[k];
         if (debug && (avf_region_summary_rows(region_table, genome, all, first + at, n, out.status, gm.data()) ||
                       avf_region_sequences_rows(sequence_table, genome, all, first + at, n, out.status, seq_bytes.data(), seq_len.data(), seq_off.data(),
@@ -819,6 +909,20 @@ int main(int argc, char **argv) {
             die(74, "Error while saving summary file", avf_last_error());
     } else if (avf_write_summary_stratified(summary.c_str(), label.c_str(), total.data(), strat, strat_total.data(), mask))
         die(74, "Error while saving summary file", avf_last_error());
+    if (boot) { /* summary_ci.tsv: summary.tsv's rows with the replicates' percentile intervals */
+        std::vector<std::string> ci_names;
+        for (uint32_t l = 0; l < n_bed_labels; ++l) ci_names.push_back(avf_strat_label(strat, l));
+        for (uint32_t j = 0; j < n_ctx_labels; ++j) {
+            char name[64];
+            if (avk_context_label_name(&cx_spec, j, name, sizeof(name))) die(70, "context label name", avk_last_error(nullptr));
+            ci_names.push_back(name);
+        }
+        std::vector<const char *> ci_ptrs;
+        for (const std::string &n : ci_names) ci_ptrs.push_back(n.c_str());
+        if (avf_write_summary_ci((out_dir + "/summary_ci.tsv").c_str(), label.c_str(), total.data(), n_labels, ci_ptrs.data(), strat_total.data(), mask, boot_spec.replicates,
+                                 boot_total.data(), boot_level))
+            die(74, "Error while saving summary_ci.tsv", avf_last_error());
+    }
     /* the annotated VCFs (VariantCategorizer): truth.vcf.gz and query.vcf.gz with their .tbi */
     std::string command;
     for (int i = 0; i < argc; ++i) command += (i ? " " : "") + std::string(argv[i]);

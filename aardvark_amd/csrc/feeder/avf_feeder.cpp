@@ -2000,4 +2000,104 @@ int avf_write_summary(const char *path, const char *compare_label, const uint64_
     return avf_write_summary_stratified(path, compare_label, tally, nullptr, nullptr, metrics_mask);
 }
 
+/* summary_ci.tsv: the rows of avf_write_summary_named — same order, same key columns, rows it leaves out left out — with percentile intervals of recall, precision
+ * and F1 over bootstrap replicates (avk_boot_tallies: boot_blocks[(scope * replicates + b) * AVK_TALLY_LEN + word], scope 0 the ALL group, scope 1 + l label l).
+ * A metric's interval is taken over the m replicates in which it is defined (its denominator is not 0), sorted ascending: with a = 100 - level_percent,
+ * lo = x[floor(a m / 200)], hi = x[ceil((200 - a) m / 200) - 1], both in integer arithmetic and clamped to [0, m - 1]; m = 0: empty cells.  The column
+ * `replicates` is the m of F1 (recall and precision both defined and not both 0), the smallest of the three.  Joint rows are summed per replicate before the ratio is taken. */
+int avf_write_summary_ci(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names, const uint64_t *strat_tallies,
+                         uint32_t metrics_mask, uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent) {
+    if (!path || !tally || (n_labels && (!strat_tallies || !label_names)) || !replicates || !boot_blocks) return fail(AVK_E_ARG, "null argument, or no replicates");
+    if (level_percent != 90 && level_percent != 95 && level_percent != 99) return fail(AVK_E_ARG, "the interval's level is 90, 95 or 99, not %u", level_percent);
+    for (uint32_t l = 0; l < n_labels; ++l)
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+    const std::string p(path);
+    const char delim = p.size() >= 4 && p.compare(p.size() - 4, 4, ".csv") == 0 ? ',' : '\t';
+    FILE *fp = fopen(path, "w");
+    if (!fp) return fail(AVK_E_ARG, "cannot create %s", path);
+    const std::string label = csv_field(compare_label ? compare_label : "", delim);
+    static const char *const header[15] = {"compare_label", "comparison", "region_label", "filter", "variant_type", "metric_recall", "recall_lo", "recall_hi",
+                                           "metric_precision", "precision_lo", "precision_hi", "metric_f1", "f1_lo", "f1_hi", "replicates"};
+    for (int k = 0; k < 15; ++k) fprintf(fp, "%s%c", header[k], k == 14 ? '\n' : delim);
+    static const char *const type_name[12] = {"Snv", "Insertion", "Deletion", "Indel", "SvInsertion", "SvDeletion", "SvDuplication", "SvInversion",
+                                              "SvBreakend", "TrContraction", "TrExpansion", "Unknown"};
+    const std::vector<int> joint_types[3] = {{AVK_VT_INSERTION, AVK_VT_DELETION, AVK_VT_INDEL},
+                                             {AVK_VT_SV_INSERTION, AVK_VT_SV_DELETION, AVK_VT_SV_DUPLICATION, AVK_VT_SV_INVERSION, AVK_VT_SV_BREAKEND},
+                                             {AVK_VT_TR_EXPANSION, AVK_VT_TR_CONTRACTION}};
+    static const char *const joint_name[3] = {"JointIndel", "JointStructuralVariant", "JointTandemRepeat"};
+    const struct {
+        uint32_t bit;
+        const char *name;
+        int base;
+    } kinds[5] = {{AVF_METRIC_GT, "GT", AVK_F_GT_TRUTH_TP}, {AVF_METRIC_BASEPAIR, "BASEPAIR", AVK_F_BP_TRUTH_TP}, {AVF_METRIC_HAP, "HAP", AVK_F_HAP_TRUTH_TP},
+                  {AVF_METRIC_WEIGHTED_HAP, "WEIGHTED_HAP", AVK_F_WHAP_TRUTH_TP}, {AVF_METRIC_RECORD_BP, "RECORD_BP", AVK_F_RBP_TRUTH_TP}};
+    /* recall, precision, F1 of four sums; false where undefined */
+    auto ratios = [](const uint64_t m[4], double v[3], bool ok[3]) {
+        const uint64_t ttot = m[0] + m[1], qtot = m[2] + m[3];
+        ok[0] = ttot > 0, ok[1] = qtot > 0, ok[2] = ttot > 0 && qtot > 0;
+        v[0] = ok[0] ? (double)m[0] / (double)ttot : 0.0;
+        v[1] = ok[1] ? (double)m[2] / (double)qtot : 0.0;
+        v[2] = ok[2] ? 2.0 * v[0] * v[1] / (v[0] + v[1]) : 0.0;
+    };
+    const uint64_t a = 100 - level_percent;
+    std::vector<double> xs[3];
+    auto write_group = [&](const uint64_t *point, const uint64_t *reps, const std::string &region_label) {
+        for (const auto &kd : kinds) {
+            if (!(metrics_mask & kd.bit)) continue;
+            /* the four sums of the groups `groups` of a block, added */
+            auto sums = [&](const uint64_t *block, const std::vector<int> &groups, uint64_t m[4]) {
+                m[0] = m[1] = m[2] = m[3] = 0;
+                for (int g : groups)
+                    for (int k = 0; k < 4; ++k) m[k] += block[(size_t)g * AVK_N_FIELDS + kd.base + k];
+            };
+            auto row = [&](const char *vtype, const std::vector<int> &groups, bool always) {
+                uint64_t m[4];
+                sums(point, groups, m);
+                if (!always && m[0] + m[1] + m[2] + m[3] == 0) return; /* is_empty: no row in summary.tsv, none here */
+                double v[3];
+                bool ok[3];
+                ratios(m, v, ok);
+                for (auto &x : xs) x.clear();
+                for (uint32_t b = 0; b < replicates; ++b) {
+                    uint64_t mb[4];
+                    double vb[3];
+                    bool okb[3];
+                    sums(reps + (size_t)b * AVK_TALLY_LEN, groups, mb);
+                    ratios(mb, vb, okb);
+                    for (int q = 0; q < 3; ++q)
+                        if (okb[q] && vb[q] == vb[q]) xs[q].push_back(vb[q]); /* (F1 of recall = precision = 0 is 0 / 0: not defined in that replicate) */
+                }
+                fprintf(fp, "%s%c%s%c%s%cALL%c%s", label.c_str(), delim, kd.name, delim, region_label.c_str(), delim, delim, vtype);
+                for (int q = 0; q < 3; ++q) {
+                    std::sort(xs[q].begin(), xs[q].end());
+                    const uint64_t mq = xs[q].size();
+                    std::string lo, hi;
+                    if (mq) {
+                        uint64_t il = a * mq / 200, ih = ((200 - a) * mq + 199) / 200;
+                        ih = ih ? ih - 1 : 0;
+                        if (il > mq - 1) il = mq - 1;
+                        if (ih > mq - 1) ih = mq - 1;
+                        lo = fmt_f64(xs[q][il]), hi = fmt_f64(xs[q][ih]);
+                    }
+                    fprintf(fp, "%c%s%c%s%c%s", delim, ok[q] ? fmt_f64(v[q]).c_str() : "", delim, lo.c_str(), delim, hi.c_str());
+                }
+                fprintf(fp, "%c%llu\n", delim, (unsigned long long)xs[2].size());
+            };
+            row("ALL", {0}, true);
+            for (int t = 0; t < AVK_N_VARIANT_TYPES; ++t) row(type_name[t], {1 + t}, false);
+            for (int j = 0; j < 3; ++j) {
+                std::vector<int> groups;
+                for (int t : joint_types[j]) groups.push_back(1 + t);
+                row(joint_name[j], groups, false);
+            }
+        }
+    };
+    write_group(tally, boot_blocks, "ALL");
+    for (uint32_t l = 0; l < n_labels; ++l)
+        write_group(strat_tallies + (size_t)l * AVK_TALLY_LEN, boot_blocks + (size_t)(1 + l) * replicates * AVK_TALLY_LEN, csv_field(label_names[l], delim));
+    const bool bad = ferror(fp) != 0;
+    if (fclose(fp) != 0 || bad) return fail(AVK_E_ARG, "write error on %s", path);
+    return 0;
+}
+
 } /* extern "C" */

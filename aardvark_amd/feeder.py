@@ -410,6 +410,22 @@ def write_summary_named(path, tally, names, strat_tallies, compare_label="compar
     _check(lib, lib.avf_write_summary_named(os.fsencode(path), compare_label.encode(), t.ctypes.data_as(u64p), len(names), arr, st.ctypes.data_as(u64p), metrics))
 
 
+def write_summary_ci(path, tally, names, strat_tallies, boot_blocks, level=95, compare_label="compare", metrics=METRIC_GT | METRIC_BASEPAIR):
+    """avf_write_summary_ci: the rows of write_summary_named with percentile intervals of recall, precision and F1 over the bootstrap replicates `boot_blocks`
+    ([1 + len(names), replicates, TALLY_LEN], Context.boot_tallies' layout); level: 90, 95 or 99"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    t = np.ascontiguousarray(tally, dtype=np.uint64)
+    st = np.ascontiguousarray(strat_tallies if len(names) else np.zeros(1), dtype=np.uint64).reshape(-1)
+    bb = np.ascontiguousarray(boot_blocks, dtype=np.uint64)
+    if bb.ndim != 3 or bb.shape[0] != 1 + len(names):
+        raise ValueError("boot_blocks is [1 + labels, replicates, TALLY_LEN]")
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names]) if names else None
+    lib.avf_write_summary_ci.argtypes = [C.c_char_p, C.c_char_p, u64p, C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32, C.c_uint32, u64p, C.c_uint32]
+    _check(lib, lib.avf_write_summary_ci(os.fsencode(path), compare_label.encode(), t.ctypes.data_as(u64p), len(names), arr, st.ctypes.data_as(u64p), metrics, bb.shape[1],
+                                         bb.reshape(-1).ctypes.data_as(u64p), int(level)))
+
+
 def write_debug_tables(summary_path, sequences_path, genome, batch, result, metrics=METRIC_GT | METRIC_BASEPAIR):
     """region_summary.tsv.gz and region_sequences.tsv.gz of --output-debug for one batch and its ResultBatch (with sequences)."""
     lib = load_library()

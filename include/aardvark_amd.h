@@ -600,6 +600,39 @@ int  avk_compare_packed_strata(avk_ctx *ctx, const avk_packed_batch *batch, cons
 int  avk_compare_packed_submit_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata,
                                       const avk_compare_config *cfg, avk_result_batch *out, uint64_t *label_tallies, avk_ticket **ticket);
 
+/* BOOTSTRAP REPLICATES of the tallies (avk_boot.inl; the rule is this project's own, stated in aardvark_amd/csrc/avk_boot.h and DESIGN.md section 5): the region
+ * is the resampling unit, region r enters replicate b with the integer weight w(r, b) ~ Poisson(1) that avk_boot_weight gives — a function of the seed, the
+ * region's contig and window start and b alone, so a job's replicates do not depend on how it is cut into batches, shards or slices.
+ *   block    a replicate's block has AVK_TALLY_LEN words: words 0 .. 285 the sum over the solved regions (status 0) of w(r, b) x the region's block (what
+ *            avk_group_metrics_from_compact gives, 32-bit truncations included), word AVK_TALLY_SOLVED the sum of w over them, word AVK_TALLY_ERRORS not touched
+ *   scopes   scope 0 is every region; with a strata handle of L labels scope 1 + l is the regions of label l (context labels included)
+ *   out      out[(scope * replicates + b) * AVK_TALLY_LEN + word]; sums are ADDED: a job sums over its batches and ranks (avk_counts_allreduce, or on the host)
+ *   limits   1 <= replicates <= AVK_BOOT_MAX_REPLICATES and (1 + L) * replicates <= AVK_BOOT_MAX_BLOCKS, otherwise AVK_E_ARG before anything is queued, out untouched
+ * A launch holds avk_boot_block(ctx) replicates of one scope; more replicates or scopes are more launches over the regions.  The submit / wait forms and the
+ * merge take no spec. */
+#include "../aardvark_amd/csrc/avk_boot.h"
+typedef struct avk_boot_spec {
+    uint32_t replicates;
+    uint64_t seed;
+} avk_boot_spec;
+/* (the shared header defines the rule, host side: static inline uint32_t avk_boot_weight(uint64_t seed, uint32_t contig_idx, uint32_t start, uint32_t b)) */
+uint32_t avk_boot_block(const avk_ctx *ctx);
+/* resident form; preconditions and refusals are those of avk_label_tallies_strata: a device-packed batch (wide, compact or packed upload, with or without escapes)
+ * after avk_compare_resident with the option emit_bp_groups set, otherwise AVK_E_STATE; a handle of another context is AVK_E_ARG.  strata == NULL: scope 0 only.
+ * Called after avk_results_download it also counts the regions the capacity retry repaired. */
+int  avk_boot_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *spec, const avk_strata *strata, uint64_t *out);
+/* avk_compare_packed_strata that also returns the replicates (ADDED to boot_tallies).  Results, tally and label sums are bit for bit those of the call without a
+ * spec; spec == NULL or replicates == 0 is exactly that call, launch for launch (boot_tallies is not read).  The library switches the BASEPAIR groups on itself;
+ * regions the capacity retry repairs are counted.  strata == NULL or zero labels: scope 0 only, label_tallies is not read. */
+int  avk_compare_packed_boot(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata, const avk_compare_config *cfg,
+                             avk_result_batch *out, uint64_t *label_tallies, const avk_boot_spec *spec, uint64_t *boot_tallies);
+/* host only (no GPU involved): the same sums from a result batch — the route for batches that were not packed on the device (option device_pack 0).  Region r's
+ * block comes from avk_group_metrics_from_compact(batch, r, res) — res needs what that function needs, and status or region_packed —, its key from
+ * batch->contig_idx and batch->start, its scopes from labels (NULL: scope 0 only; a label named twice in a region's list counts twice).  threads: host threads
+ * (0: one); the regions are cut among them, the sums do not depend on the cut. */
+int  avk_boot_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_boot_spec *spec, const avk_region_labels *labels, uint32_t threads,
+                           uint64_t *out);
+
 /* SEQUENCE-CONTEXT labels (avk_context.inl): labels that are functions of the reference sequence alone, made by kernel from the reference avk_ref_upload left in
  * HBM — a stratified job needs no BED set for them.  The rule is this project's own (the reference has no such labels):
  *   window   a region's query is the one the interval sets get, [first, last] on its contig; a family's window is [first - pad, last + 1 + pad), clamped to the

@@ -156,6 +156,14 @@ int avf_write_summary_stratified(const char *path, const char *compare_label, co
  * avf_write_summary_stratified is this function with the names of the sets. */
 int avf_write_summary_named(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names,
                             const uint64_t *strat_tallies, uint32_t metrics_mask);
+/* summary_ci.tsv: the rows of avf_write_summary_named for the same tallies — same order, same key columns (compare_label comparison region_label filter variant_type),
+ * rows it leaves out left out, point values formatted alike — followed by metric_recall recall_lo recall_hi metric_precision precision_lo precision_hi metric_f1 f1_lo
+ * f1_hi replicates: percentile intervals over bootstrap replicates (avk_boot_tallies' layout: boot_blocks[(scope * replicates + b) * AVK_TALLY_LEN + word], scope 0
+ * the ALL group, scope 1 + l label l).  A metric's interval is taken over the m replicates in which it is defined, sorted ascending, with a = 100 - level_percent:
+ * lo = x[floor(a m / 200)], hi = x[ceil((200 - a) m / 200) - 1], indices clamped to [0, m - 1], empty cells when m = 0.  The column `replicates` is the m of F1 (both
+ * denominators non-zero and recall + precision > 0), the smallest of the three.  Joint rows are summed per replicate before the ratio is taken.  level_percent: 90, 95 or 99. */
+int avf_write_summary_ci(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names, const uint64_t *strat_tallies,
+                         uint32_t metrics_mask, uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent);
 
 /* One of the two annotated VCFs of `compare` (VariantCategorizer, src/writers/variant_categorizer.rs:41-230; source 0 =
  * truth.vcf.gz, 1 = query.vcf.gz): the meta lines of input_vcf, the aardvark_version / aardvark_command lines and the
