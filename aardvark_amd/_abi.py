@@ -222,6 +222,61 @@ def declare_boot(lib):
     lib.avk_boot_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkBootSpec), _p(AvkRegionLabels), C.c_uint32, u64p]
 
 
+SIZE_EDGES_MAX, SIZE_FIELDS = 15, 14
+
+
+class AvkSizeSpec(C.Structure):
+    """avk_size_spec: the edges of the size bins (aardvark_amd/csrc/avk_sizebin.h has the rule)"""
+    _fields_ = [("n_edges", C.c_uint32), ("edges", C.c_uint32 * SIZE_EDGES_MAX)]
+
+
+class SizeSpec:
+    """Size bins of the per-call tallies: size = |a1_len - a0_len|; 1 to 15 ascending edges, the first at least 1; bin 0 is size < edges[0], the last bin
+    size >= edges[-1].  The library checks the spec; an invalid one is refused there."""
+
+    def __init__(self, edges=(1, 6, 16, 50)):
+        self.edges = tuple(int(e) for e in edges)
+
+    @property
+    def n_bins(self):
+        return len(self.edges) + 1
+
+    def c_struct(self):
+        s = AvkSizeSpec()
+        s.n_edges = len(self.edges)
+        for k, e in enumerate(self.edges[:SIZE_EDGES_MAX]):
+            s.edges[k] = e & 0xFFFFFFFF
+        return s
+
+    def names(self):
+        """avk_size_bin_name for every bin: len_<lo>_<hi> (inclusive), len_<lo> for one size, len_ge<lo> for the last"""
+        from .api import load_library
+        lib, cs, out = load_library(), self.c_struct(), []
+        for j in range(self.n_bins):
+            buf = C.create_string_buffer(64)
+            if lib.avk_size_bin_name(C.byref(cs), j, buf, 64):
+                raise ValueError(lib.avk_last_error(None).decode())
+            out.append(buf.value.decode())
+        return out
+
+
+def declare_size(lib):
+    """avk_size_n_bins, avk_size_bin_name, avk_size_block, avk_size_tallies, avk_compare_packed_size, avk_size_tallies_host (include/aardvark_amd.h)"""
+    vp, u64p = C.c_void_p, _p(C.c_uint64)
+    lib.avk_size_n_bins.restype = C.c_uint32
+    lib.avk_size_n_bins.argtypes = [_p(AvkSizeSpec)]
+    lib.avk_size_bin_name.restype = C.c_int
+    lib.avk_size_bin_name.argtypes = [_p(AvkSizeSpec), C.c_uint32, C.c_char_p, C.c_size_t]
+    lib.avk_size_block.restype = C.c_uint32
+    lib.avk_size_block.argtypes = [vp]
+    lib.avk_size_tallies.restype = C.c_int
+    lib.avk_size_tallies.argtypes = [vp, vp, _p(AvkSizeSpec), vp, u64p]
+    lib.avk_compare_packed_size.restype = C.c_int
+    lib.avk_compare_packed_size.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkSizeSpec), _p(AvkResultBatch), u64p]
+    lib.avk_size_tallies_host.restype = C.c_int
+    lib.avk_size_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkSizeSpec), _p(AvkRegionLabels), C.c_uint32, u64p]
+
+
 CONTEXT_PAD_MAX, CONTEXT_GC_EDGES_MAX, CONTEXT_HP_EDGES_MAX = 1024, 17, 16
 
 

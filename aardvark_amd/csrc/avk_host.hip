@@ -3024,8 +3024,17 @@ struct BootStage {
     uint64_t *sums; /* the caller's [(1 + n_labels) * replicates * AVK_TALLY_LEN]: gains the sums */
 };
 static int boot_sums_run(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *bs, uint32_t n_labels, const uint32_t *d_mask, uint64_t *out);
+/* ... and the size-bin tallies, behind the download for the same reason (avk_compare_packed_size); they read no BASEPAIR groups, and the scopes' masks are made
+ * from the resident batch when a handle is given */
+struct SizeStage {
+    const avk_size_spec *spec;
+    const avk_strata *st;
+    uint64_t *sums; /* the caller's [(1 + n_labels) * n_bins * AVK_N_GROUPS * AVK_SIZE_FIELDS]: gains the sums */
+};
+static int size_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *sp, const avk_strata *st, uint64_t *out);
 static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_result_batch *out, uint64_t n, const char *timed_as,
-                            const std::function<int(const CallSpec &, avk_dev_batch **)> &upload, const LabelStage *ls = nullptr, const BootStage *boot = nullptr) {
+                            const std::function<int(const CallSpec &, avk_dev_batch **)> &upload, const LabelStage *ls = nullptr, const BootStage *boot = nullptr,
+                            const SizeStage *size = nullptr) {
     ctx->last_one_shot = 0;
     CallSpec spec = call_spec(ctx, out, ls != nullptr || boot != nullptr); /* (the groups are what the label kernel reads, whether the caller asked for them or not) */
     const uint32_t n_labels = !ls ? 0 : ls->st ? ls->st->n_labels : ls->lab->n_labels;
@@ -3069,6 +3078,7 @@ static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_res
     const uint64_t n_strata_idx = L.total;
     if (ls) (void)hipStreamSynchronize(ctx->stream);
     if (!rc && boot) rc = boot_sums_run(ctx, db, boot->spec, job.st ? job.st->n_labels : 0, (const uint32_t *)L.d_mask, boot->sums);
+    if (!rc && size) rc = size_resident_run(ctx, db, size->spec, size->st, size->sums);
     strata_lists_release(ctx, L);
     pool_release(ctx, d_out);
     if (db) {
@@ -3290,6 +3300,186 @@ int avk_boot_tallies_host(const avk_region_batch *b, const avk_result_batch *res
     for (std::thread &th : pool) th.join();
     for (uint32_t t = 0; t < T; ++t)
         if (bad[t]) return fail(nullptr, AVK_E_ARG, "bootstrap: avk_group_metrics_from_compact refused a region (per-call outputs and BASEPAIR groups are needed)");
+    for (uint32_t t = 0; t < T; ++t)
+        for (size_t k = 0; k < words; ++k) out[k] += part[t][k];
+    return 0;
+}
+
+/* ---- per-call tallies by size bin (avk_sizebin.h, avk_sizebin.inl) ------------------------------------------------------------------------------------ */
+/* (included here, behind the kernels of the solver step and the packer: the code of the headline call lies where it lay) */
+} /* extern "C" */
+#include "avk_sizebin.inl"
+extern "C" {
+static_assert(AVK_SIZE_FIELDS == AVK_F_WHAP_QUERY_FP + 1 && AVK_F_GT_TRUTH_TP == 0, "the size block's fields are the first fourteen of a group");
+static_assert(AVK_SZ_BLOCK_WORDS(AVK_SIZE_EDGES_MAX + 1) * 8 <= AVK_SZ_LDS_BYTES && AVK_SZ_THREADS % 64 == 0 && AVK_N_VARIANT_TYPES < 15,
+              "a workgroup of avk_size_tally_kernel holds one scope's block of the widest spec, whole waves, and a key its type");
+/* the refusals of every entry point with a spec, before anything is queued (no device involved) */
+static int size_spec_check(avk_ctx *ctx, const avk_size_spec *sp, const uint64_t *out) {
+    if (!sp) return fail(ctx, AVK_E_ARG, "size bins: spec missing");
+    if (!avk_size_spec_ok(sp)) return fail(ctx, AVK_E_ARG, "size bins: 1 to %d edges, the first at least 1, strictly ascending", AVK_SIZE_EDGES_MAX);
+    if (!out) return fail(ctx, AVK_E_ARG, "size_tallies missing");
+    return 0;
+}
+uint32_t avk_size_n_bins(const avk_size_spec *sp) { return avk_size_spec_ok(sp) ? sp->n_edges + 1u : 0u; }
+uint32_t avk_size_block(const avk_ctx *ctx) { return ctx ? AVK_SZ_THREADS : 0; }
+int avk_size_bin_name(const avk_size_spec *sp, uint32_t j, char *buf, size_t cap) {
+    if (!avk_size_spec_ok(sp) || j > sp->n_edges || !buf || !cap) return fail(nullptr, AVK_E_ARG, "size bins: invalid spec, bin or buffer");
+    uint32_t lo, hi;
+    avk_size_bin_bounds(sp, j, &lo, &hi);
+    const int k = j == sp->n_edges ? snprintf(buf, cap, "len_ge%u", lo) : lo == hi ? snprintf(buf, cap, "len_%u", lo) : snprintf(buf, cap, "len_%u_%u", lo, hi);
+    return k > 0 && (size_t)k < cap ? 0 : fail(nullptr, AVK_E_ARG, "size bins: the name buffer is too small");
+}
+/* the kernel over blocks of scopes, on stream s behind whatever wrote the batch's results: d_out[(1 + n_labels) * AVK_SZ_BLOCK_WORDS(n_bins)] gains the sums */
+static int size_launch(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *sp, uint32_t n_labels, const uint32_t *d_mask, uint64_t *d_out, hipStream_t s) {
+    const uint64_t n = db->n_regions;
+    if (!n) return 0;
+    avk::lb::LbView v;
+    memset(&v, 0, sizeof(v));
+    v.in = db->dp_args.in, v.vinfo = db->dp_args.vinfo, v.region_out = db->d_region_out, v.var_out = db->d_var_out, v.v_off = db->d_voff;
+    const uint32_t block_bytes = AVK_SZ_BLOCK_WORDS(sp->n_edges + 1u) * 8u, n_scopes = 1u + (d_mask ? n_labels : 0u);
+    uint32_t per_launch = AVK_SZ_LDS_BYTES / block_bytes;
+    if (per_launch > AVK_SZ_SCOPES_MAX) per_launch = AVK_SZ_SCOPES_MAX;
+    /* four workgroups a CU (their LDS), and no more workgroups than tiles: each flushes its block once */
+    uint64_t blocks = (n + AVK_SZ_THREADS - 1) / AVK_SZ_THREADS;
+    if (blocks > (uint64_t)ctx->n_cus * 4u) blocks = (uint64_t)ctx->n_cus * 4u;
+    for (uint32_t lo = 0; lo < n_scopes; lo += per_launch) {
+        const uint32_t hi = n_scopes - lo > per_launch ? lo + per_launch : n_scopes;
+        hipLaunchKernelGGL(avk_size_tally_kernel, dim3((unsigned)blocks), dim3(AVK_SZ_THREADS), (size_t)(hi - lo) * block_bytes, s, v, d_mask, (uint32_t)n, *sp, lo, hi,
+                           (unsigned long long *)d_out);
+        AVK_HIP(ctx, hipGetLastError());
+    }
+    return 0;
+}
+/* sums cleared, kernels, copy back, wait, added to the caller's: on the context's stream */
+static int size_sums_run(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *sp, uint32_t n_labels, const uint32_t *d_mask, uint64_t *out) {
+    if (!d_mask) n_labels = 0;
+    const size_t words = ((size_t)n_labels + 1) * AVK_SZ_BLOCK_WORDS(sp->n_edges + 1u);
+    std::vector<uint64_t> host(words, 0);
+    void *d_out = nullptr;
+    int rc = pool_alloc(ctx, &d_out, words * 8);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
+    if (!rc && e == hipSuccess) rc = size_launch(ctx, db, sp, n_labels, d_mask, (uint64_t *)d_out, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    pool_release(ctx, d_out);
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(ctx, AVK_E_HIP, "size-bin tallies failed: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    for (size_t k = 0; k < words; ++k) out[k] += host[k];
+    return 0;
+}
+/* a solved resident batch: the scopes' membership (the strata pass's masks, nothing else of the lists), then the sums */
+static int size_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *sp, const avk_strata *st, uint64_t *out) {
+    const uint64_t n = db->n_regions;
+    StrataLists L;
+    int rc = 0;
+    if (st && st->n_labels && n) {
+        rc = strata_lists_alloc(ctx, st, n, L);
+        if (!rc) {
+            const hipError_t e = strata_mask_launch(st, db->dp_args.in, n, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums, ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata masks failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (!rc) rc = size_sums_run(ctx, db, sp, L.d_mask ? st->n_labels : 0, (const uint32_t *)L.d_mask, out);
+    else (void)hipStreamSynchronize(ctx->stream);
+    strata_lists_release(ctx, L);
+    return rc;
+}
+
+int avk_size_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *sp, const avk_strata *st, uint64_t *out) {
+    if (!ctx || !db) return AVK_E_ARG;
+    {
+        const int rs = size_spec_check(ctx, sp, out);
+        if (rs) return rs;
+    }
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    if (!db->dev_packed) return fail(ctx, AVK_E_STATE, "size-bin tallies on the device need a device-packed batch: the option device_pack was 0 at its upload (host route: avk_size_tallies_host)");
+    if (!db->has_run || db->last_mode != 0) return fail(ctx, AVK_E_STATE, "size-bin tallies need a batch that avk_compare_resident has solved");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    return size_resident_run(ctx, db, sp, st, out);
+}
+
+int avk_compare_packed_size(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg,
+                            const avk_size_spec *sp, avk_result_batch *out, uint64_t *size_out) {
+    if (!batch) return AVK_E_ARG;
+    if (st && st->n_labels == 0) st = nullptr;
+    {
+        const int rs = size_spec_check(ctx, sp, size_out);
+        if (rs) return rs;
+    }
+    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->device_pack) return fail(ctx, AVK_E_STATE, "size-bin tallies on the device need the option device_pack (host route: avk_size_tallies_host)");
+    if (!esc_present(esc)) esc = nullptr;
+    const SizeStage size{sp, st, size_out};
+    return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, nullptr, nullptr,
+                            &size);
+}
+
+int avk_size_tallies_host(const avk_region_batch *b, const avk_result_batch *res, const avk_size_spec *sp, const avk_region_labels *lab, uint32_t threads, uint64_t *out) {
+    if (!b || !res) return fail(nullptr, AVK_E_ARG, "size bins: batch or results missing");
+    const uint32_t n_labels = lab ? lab->n_labels : 0;
+    {
+        const int rs = size_spec_check(nullptr, sp, out);
+        if (rs) return rs;
+        if (lab && n_labels) {
+            const int rl = labels_check(nullptr, b->n_regions, lab, out);
+            if (rl) return rl;
+        }
+    }
+    if (!(res->status || res->region_packed)) return fail(nullptr, AVK_E_ARG, "size bins: the results have neither status nor region_packed");
+    const bool wide_calls = res->var_expected && res->var_observed;
+    if (!wide_calls && !res->var_packed) return fail(nullptr, AVK_E_ARG, "size bins: the results have no per-call outputs");
+    const uint64_t n = b->n_regions;
+    const uint32_t n_bins = sp->n_edges + 1u;
+    const size_t block = AVK_SZ_BLOCK_WORDS(n_bins), words = ((size_t)n_labels + 1) * block;
+    const uint32_t T = threads < 1 ? 1u : (threads > 64u ? 64u : threads); /* every thread sums into a block of its own */
+    std::vector<std::vector<uint64_t>> part(T);
+    std::vector<int> bad(T, 0);
+    auto work = [&](uint32_t t) {
+        std::vector<uint64_t> &acc = part[t];
+        acc.assign(words, 0);
+        for (uint64_t r = n * t / T; r < n * (t + 1) / T; ++r) {
+            const uint32_t status = res->status ? (uint32_t)res->status[r] : avk_rp_status(res->region_packed[r]);
+            if (status != 0) continue;
+            for (int side = 0; side < 2; ++side) {
+                const uint64_t off = side == 0 ? b->t_off[r] : b->q_off[r];
+                const uint32_t cnt = side == 0 ? b->t_cnt[r] : b->q_cnt[r];
+                if (off > b->n_variants || cnt > b->n_variants - off) {
+                    bad[t] = 1;
+                    return;
+                }
+                for (uint32_t i = 0; i < cnt; ++i) {
+                    const uint64_t v = off + i;
+                    const uint32_t vt = b->var_type[v];
+                    const uint64_t w = avk::host_edit_distance(b->allele_bytes + b->a0_off[v], b->a0_len[v], b->allele_bytes + b->a1_off[v], b->a1_len[v]); /* Variant::alt_ed */
+                    const uint32_t ea = wide_calls ? res->var_expected[v] : avk_vp_expected(res->var_packed[v]), oa = wide_calls ? res->var_observed[v] : avk_vp_observed(res->var_packed[v]);
+                    /* one iteration of lb_side (avk_labels.inl): the query entries are stored toggled */
+                    const uint32_t exp = side == 0 ? ea : oa, obs = side == 0 ? oa : ea;
+                    const uint32_t val[AVK_SIZE_VALUES] = {exp == obs ? 1u : 0u, exp == obs ? 0u : 1u, (exp != obs && obs > 0) ? 1u : 0u, obs, exp - obs, (uint32_t)((uint64_t)obs * w),
+                                                           (uint32_t)((uint64_t)(uint32_t)(exp - obs) * w)};
+                    const uint32_t bin = avk_size_bin_of(sp, avk_size_of(b->a0_len[v], b->a1_len[v]));
+                    auto add = [&](uint32_t scope) {
+                        for (uint32_t g : {0u, 1u + vt}) {
+                            if (g >= AVK_N_GROUPS) continue;
+                            uint64_t *dst = acc.data() + (size_t)scope * block + ((size_t)bin * AVK_N_GROUPS + g) * AVK_SIZE_FIELDS;
+                            for (uint32_t k = 0; k < AVK_SIZE_VALUES; ++k) dst[avk_size_field_of(k, side)] += val[k];
+                        }
+                    };
+                    add(0);
+                    if (n_labels)
+                        for (uint64_t q = lab->label_off[r]; q < lab->label_off[r + 1]; ++q) add(1u + lab->label_idx[q]);
+                }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < T; ++t) pool.emplace_back(work, t);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    for (uint32_t t = 0; t < T; ++t)
+        if (bad[t]) return fail(nullptr, AVK_E_ARG, "size bins: a region's calls lie outside the batch");
     for (uint32_t t = 0; t < T; ++t)
         for (size_t k = 0; k < words; ++k) out[k] += part[t][k];
     return 0;

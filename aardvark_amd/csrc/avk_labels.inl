@@ -48,6 +48,25 @@ struct LbSide {
     u32 gt_tp, gt_fn, gt_fn_gt, hap_tp, hap_fn, w_tp, w_fn;
     u64 tot;
 };
+/* one call's contribution to them: its per-call word x (truth or query entry) and its alt_ed w.  One iteration of lb_side; avk_sizebin.inl keys the same seven
+ * values by the call's size */
+struct LbCall {
+    u32 gt_tp, gt_fn, gt_fn_gt, hap_tp, hap_fn, w_tp, w_fn;
+};
+AVK_DEV LbCall lb_call(u32 x, bool query, u64 w) {
+    const u32 ea = x & 0xFFu, oa = (x >> 8) & 0xFFu;
+    /* the query entries are stored toggled (compare_benchmark.rs:109-123): scored as truth they expected var_observed and observed var_expected */
+    const u32 exp = query ? oa : ea, obs = query ? ea : oa;
+    LbCall k;
+    k.hap_tp = obs;
+    k.hap_fn = exp - obs;
+    k.w_tp = (u32)((u64)obs * w);
+    k.w_fn = (u32)((u64)(u32)(exp - obs) * w);
+    k.gt_tp = exp == obs ? 1u : 0u;
+    k.gt_fn = exp == obs ? 0u : 1u;
+    k.gt_fn_gt = (exp != obs && obs > 0) ? 1u : 0u;
+    return k;
+}
 AVK_DEV LbSide lb_side(const LbView &v, u64 off, u32 cnt, const u32 *vw, bool query, u32 g) {
     LbSide s;
     s.gt_tp = s.gt_fn = s.gt_fn_gt = s.hap_tp = s.hap_fn = s.w_tp = s.w_fn = 0;
@@ -56,19 +75,14 @@ AVK_DEV LbSide lb_side(const LbView &v, u64 off, u32 cnt, const u32 *vw, bool qu
         const u64 c = off + i;
         const u32 vt = v.in.type_of(c);
         if (g != 0 && g != 1u + vt) continue;
-        const u32 x = vw[i], ea = x & 0xFFu, oa = (x >> 8) & 0xFFu;
-        /* the query entries are stored toggled (compare_benchmark.rs:109-123): scored as truth they expected var_observed and observed var_expected */
-        const u32 exp = query ? oa : ea, obs = query ? ea : oa;
-        const u64 w = v.vinfo[c].alt_ed;
-        s.hap_tp += obs;
-        s.hap_fn += exp - obs;
-        s.w_tp += (u32)((u64)obs * w);
-        s.w_fn += (u32)((u64)(u32)(exp - obs) * w);
-        if (exp == obs) s.gt_tp += 1;
-        else {
-            s.gt_fn += 1;
-            if (obs > 0) s.gt_fn_gt += 1;
-        }
+        const LbCall k = lb_call(vw[i], query, v.vinfo[c].alt_ed);
+        s.hap_tp += k.hap_tp;
+        s.hap_fn += k.hap_fn;
+        s.w_tp += k.w_tp;
+        s.w_fn += k.w_fn;
+        s.gt_tp += k.gt_tp;
+        s.gt_fn += k.gt_fn;
+        s.gt_fn_gt += k.gt_fn_gt;
         const u32 z = v.in.zyg_of(c);
         const u64 cz = z == AVK_ZYG_HOM_ALT ? 2u : ((z >= AVK_ZYG_UNPHASED_HET && z <= AVK_ZYG_PHASED_HET10) ? 1u : 0u);
         s.tot += cz * (u64)v.in.raw_of(c, v.in.a0_len_of(c), v.in.a1_len_of(c));

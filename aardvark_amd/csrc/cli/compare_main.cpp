@@ -42,7 +42,10 @@ void usage() {
             "  [--context-strata gc|hp|gc,hp]  (GC-content bins and homopolymer classes as further region labels, made on the GPU from the reference alone; with or without -s;\n"
             "   packed feed and --strat-lists device only)  [--context-gc-edges 0,15,..,101] [--context-gc-pad 50] [--context-hp-edges 4,7,12,21] [--context-hp-pad 5]\n"
             "  [--bootstrap B]  (B Poisson-bootstrap replicates of the tallies, 1..4096, summed on the GPU; writes summary_ci.tsv: summary.tsv's rows with percentile intervals of\n"
-            "   recall, precision and F1; default 0: off, no file)  [--bootstrap-seed 1] [--bootstrap-level 90|95|99 (default 95)]\n");
+            "   recall, precision and F1; default 0: off, no file)  [--bootstrap-seed 1] [--bootstrap-level 90|95|99 (default 95)]\n"
+            "  [--size-strata]  (writes summary_size.tsv: summary.tsv's GT, HAP and WEIGHTED_HAP rows per size bin of the calls, size = |alt length - ref length|, the bin's\n"
+            "   name in the filter column, summed on the GPU; BASEPAIR and RECORD_BP rows are not part of this file: they belong to a region's haplotypes, not to a call)\n"
+            "  [--size-edges 1,6,16,50]  (1 to 15 ascending sizes, the first at least 1; default bins len_0 len_1_5 len_6_15 len_16_49 len_ge50)\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -95,6 +98,9 @@ int main(int argc, char **argv) {
     avk_boot_spec boot_spec = {0, 1};
     uint32_t boot_level = 95;
     bool boot_override = false;
+    /* --size-strata: per-call tallies by size bin (avk_size_spec) for summary_size.tsv */
+    bool size = false, size_override = false;
+    std::vector<uint32_t> size_edges = {1, 6, 16, 50};
     auto number_list = [](const std::string &opt, const std::string &list) {
         std::vector<uint32_t> out;
         for (size_t b = 0; b <= list.size();) {
@@ -189,6 +195,8 @@ int main(int argc, char **argv) {
             if (v.size() != 1 || (v[0] != 90 && v[0] != 95 && v[0] != 99)) die(64, "--bootstrap-level takes 90, 95 or 99", "");
             boot_level = v[0], boot_override = true;
         }
+        else if (a == "--size-strata") size = true;
+        else if (a == "--size-edges") size_edges = number_list(a, val()), size_override = true;
         else if (a == "-h" || a == "--help") {
             usage();
             return 0;
@@ -231,6 +239,21 @@ int main(int argc, char **argv) {
     if (boot && !debug_dir.empty()) die(64, "--bootstrap cannot be combined with --output-debug (the debug run writes per-region tables, not replicates)", "");
     if (boot && !strat_tsv.empty() && strat_lists == "host" && want_packed)
         die(64, "--bootstrap on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
+    /* The size bins are summed where the per-call outputs are: by kernel on the packed feed (avk_compare_packed_size, or avk_size_tallies on the resident batch when
+     * label sums or replicates are wanted of the same batch; scopes from the sets resident on the GPU), or on the host from the wide feed's results
+     * (avk_size_tallies_host).  What neither route carries is refused here, by name. */
+    avk_size_spec size_spec;
+    memset(&size_spec, 0, sizeof(size_spec));
+    if (size_override && !size) die(64, "--size-edges needs --size-strata", "");
+    if (size) {
+        if (size_edges.empty() || size_edges.size() > AVK_SIZE_EDGES_MAX) die(64, "--size-edges takes 1 to 15 strictly ascending sizes, the first at least 1", "");
+        size_spec.n_edges = (uint32_t)size_edges.size();
+        for (size_t k = 0; k < size_edges.size(); ++k) size_spec.edges[k] = size_edges[k];
+        if (!avk_size_n_bins(&size_spec)) die(64, "--size-edges takes 1 to 15 strictly ascending sizes, the first at least 1", ""); /* (the library's own check of the spec) */
+        if (!debug_dir.empty()) die(64, "--size-strata cannot be combined with --output-debug (the debug run writes per-region tables, not size bins)", "");
+        if (!strat_tsv.empty() && strat_lists == "host" && want_packed)
+            die(64, "--size-strata on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
+    }
     if (!devices.empty()) device = devices[0];
     if (mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create output folder", out_dir.c_str());
     if (!debug_dir.empty() && mkdir(debug_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create debug folder", debug_dir.c_str());
@@ -429,6 +452,33 @@ int main(int argc, char **argv) {
         lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
         return avk_boot_tallies_host(&b, &out, &boot_spec, n_labels ? &lab : nullptr, 16, reps);
     };
+    /* --size-strata on the packed feed: the part's results and its size blocks.  Alone it is one call (avk_compare_packed_size); when the labels' sums or the
+     * replicates are wanted of the same batch the batch stays resident: solve, download (the capacity retry patches the device view), then the label, bootstrap and
+     * size kernels on it — the sums the one-call forms return */
+    auto compare_part_size = [&](avk_ctx *c, uint64_t at_abs, uint64_t n, const avk_compare_config &cfg, const avk_result_batch &out, const avk_strata *sets, uint64_t *sums,
+                                 uint64_t *reps, uint64_t *blocks) -> int {
+        avk_packed_batch part;
+        avk_packed_escapes part_esc;
+        uint64_t v_first = 0;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, &v_first)) return AVK_E_ARG;
+        avk_result_batch shifted = out_for(out, v_first);
+        if (!sets && !boot) return avk_compare_packed_size(c, &part, &part_esc, nullptr, &cfg, &size_spec, &shifted, blocks);
+        avk_dev_batch *db = nullptr;
+        int rc = avk_batch_upload_packed_esc(c, &part, &part_esc, &db);
+        if (!rc) rc = avk_compare_resident(c, db, &cfg, nullptr);
+        if (!rc) rc = avk_results_download(c, db, &shifted);
+        if (!rc && sets) rc = avk_label_tallies_strata(c, db, sets, sums);
+        if (!rc && boot) rc = avk_boot_tallies(c, db, &boot_spec, sets, reps);
+        if (!rc) rc = avk_size_tallies(c, db, &size_spec, sets, blocks);
+        if (db) avk_batch_free(c, db);
+        return rc;
+    };
+    /* --size-strata on the wide feed: the part's blocks from its results on the host */
+    auto size_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *blocks) -> int {
+        avk_region_labels lab;
+        lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
+        return avk_size_tallies_host(&b, &out, &size_spec, n_labels ? &lab : nullptr, 16, blocks);
+    };
     auto upload_part = [&](avk_ctx *c, const avk_region_batch &b, uint64_t at_abs, uint64_t n, avk_dev_batch **db, uint64_t *v_first) -> int {
         *v_first = 0;
         if (!packed) return avk_batch_upload(c, &b, db);
@@ -488,8 +538,18 @@ int main(int argc, char **argv) {
     }
     if (boot && packed && n_labels && !strata_route) die(70, "--bootstrap on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
     const bool boot_host = boot && !packed; /* the wide feed: avk_boot_tallies_host on each part's results */
+    if (size && packed && n_labels && !strata_route) die(70, "--size-strata on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
+    const bool size_host = size && !packed;                            /* the wide feed: avk_size_tallies_host on each part's results */
+    const bool size_resident = size && packed && (strata_route || boot); /* label sums or replicates of the same batch: the kernels run on the resident batch */
     (void)avk_ctx_set_option(ctx, "emit_group_metrics", (n_labels && !compact_labels) || debug ? 1 : 0);
-    if (boot_host) (void)avk_ctx_set_option(ctx, "emit_bp_groups", 1);
+    if (boot_host || size_resident) (void)avk_ctx_set_option(ctx, "emit_bp_groups", 1);
+    const uint32_t size_bins = size ? size_spec.n_edges + 1 : 0;
+    std::vector<uint64_t> size_total(size ? ((size_t)n_labels + 1) * size_bins * AVK_N_GROUPS * AVK_SIZE_FIELDS : 0, 0);
+    if (verbosity && size)
+        fprintf(stderr, "Size bins: %u bins in summary_size.tsv (GT, HAP, WEIGHTED_HAP; no BASEPAIR rows); the bins are summed %s.\n", size_bins,
+                size_host       ? "on the host from each batch's results (avk_size_tallies_host, the wide feed)"
+                : size_resident ? "on the GPU on each resident batch behind its solve and download (avk_size_tallies)"
+                                : "on the GPU behind each batch's solve (avk_compare_packed_size)");
     std::vector<uint64_t> boot_total(boot ? ((size_t)n_labels + 1) * boot_spec.replicates * AVK_TALLY_LEN : 0, 0);
     if (verbosity && boot)
         fprintf(stderr, "Bootstrap: %u replicates, seed %llu, %u %% intervals in summary_ci.tsv; the replicates are summed %s.\n", boot_spec.replicates,
@@ -539,7 +599,9 @@ int main(int argc, char **argv) {
     bool sharded = false;
     if (verbosity && boot && n_workers > 1 && packed && !n_labels)
         fprintf(stderr, "Bootstrap: the hash-sharded route does not carry the replicates; --bootstrap selects the route on which the contexts share the region batches.\n");
-    if (n_workers > 1 && packed && !n_labels && !boot) {
+    if (verbosity && size && n_workers > 1 && packed && !n_labels)
+        fprintf(stderr, "Size bins: the hash-sharded route does not carry the blocks; --size-strata selects the route on which the contexts share the region batches.\n");
+    if (n_workers > 1 && packed && !n_labels && !boot && !size) {
         sharded = true;
         avk_packed_batch sel;
         avk_packed_escapes sel_esc;
@@ -662,7 +724,8 @@ int main(int argc, char **argv) {
         std::atomic<uint64_t> next_batch{0};
         std::vector<std::string> worker_err(n_workers);
         std::vector<std::vector<uint64_t>> w_total(n_workers, std::vector<uint64_t>(AVK_TALLY_LEN, 0)),
-            w_strat(n_workers, std::vector<uint64_t>((size_t)n_labels * AVK_TALLY_LEN, 0)), w_boot(n_workers, std::vector<uint64_t>(boot_total.size(), 0));
+            w_strat(n_workers, std::vector<uint64_t>((size_t)n_labels * AVK_TALLY_LEN, 0)), w_boot(n_workers, std::vector<uint64_t>(boot_total.size(), 0)),
+            w_size(n_workers, std::vector<uint64_t>(size_total.size(), 0));
         std::mutex log_mutex;
         auto worker = [&](size_t w) {
             avk_ctx *my = ctx;
@@ -685,7 +748,7 @@ int main(int argc, char **argv) {
                     return;
                 }
                 (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels && !compact_labels ? 1 : 0);
-                if (boot_host) (void)avk_ctx_set_option(my, "emit_bp_groups", 1);
+                if (boot_host || size_resident) (void)avk_ctx_set_option(my, "emit_bp_groups", 1);
             }
             avk_strata *my_sets = w > 0 ? nullptr : strata;
             if (w > 0 && strata_route && cx_given && strata_upload(my, &my_sets)) { /* (context labels: no host route) */
@@ -697,8 +760,8 @@ int main(int argc, char **argv) {
                 std::lock_guard<std::mutex> lock(log_mutex);
                 fprintf(stderr, "Warning: cannot upload the stratification sets to context %zu: %s; its region labels are listed on the host.\n", w, avk_last_error(my));
                 my_sets = nullptr;
-                if (boot) { /* (the replicates' scopes are read from the sets on the GPU) */
-                    worker_err[w] = "--bootstrap: cannot upload the stratification sets to every context";
+                if (boot || size) { /* (the replicates' and the size bins' scopes are read from the sets on the GPU) */
+                    worker_err[w] = boot ? "--bootstrap: cannot upload the stratification sets to every context" : "--size-strata: cannot upload the stratification sets to every context";
                     avk_ctx_destroy(my);
                     return;
                 }
@@ -727,7 +790,8 @@ int main(int argc, char **argv) {
                 int rc = 0;
                 HostGroups hg;
                 if (boot_host) host_groups(n, out, hg);
-                if (boot && packed) rc = compare_part_boot(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data());
+                if (size && packed) rc = compare_part_size(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data(), w_size[w].data());
+                else if (boot && packed) rc = compare_part_boot(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data());
                 else if (strata_route && my_sets) rc = compare_part_strata(my, first + at, n, cfg, out, my_sets, w_strat[w].data());
                 else if (n_labels) {
                     std::vector<uint64_t> label_off(n + 1, 0);
@@ -755,11 +819,19 @@ int main(int argc, char **argv) {
                             worker_err[w] = std::string("bootstrap tallies failed: ") + avk_last_error(nullptr);
                             break;
                         }
+                        if (!rc && size_host && size_part_host(b, out, label_off.data(), label_idx.data(), w_size[w].data())) {
+                            worker_err[w] = std::string("size-bin tallies failed: ") + avk_last_error(nullptr);
+                            break;
+                        }
                     }
                 } else {
                     rc = compare_part(my, b, first + at, n, cfg, out);
                     if (!rc && boot_host && boot_part_host(b, out, nullptr, nullptr, w_boot[w].data())) {
                         worker_err[w] = std::string("bootstrap tallies failed: ") + avk_last_error(nullptr);
+                        break;
+                    }
+                    if (!rc && size_host && size_part_host(b, out, nullptr, nullptr, w_size[w].data())) {
+                        worker_err[w] = std::string("size-bin tallies failed: ") + avk_last_error(nullptr);
                         break;
                     }
                 }
@@ -789,6 +861,7 @@ int main(int argc, char **argv) {
             for (size_t k = 0; k < (size_t)AVK_TALLY_LEN; ++k) total[k] += w_total[w][k];
             for (size_t k = 0; k < strat_total.size(); ++k) strat_total[k] += w_strat[w][k];
             for (size_t k = 0; k < boot_total.size(); ++k) boot_total[k] += w_boot[w][k]; /* the contexts' blocks, added on the host */
+            for (size_t k = 0; k < size_total.size(); ++k) size_total[k] += w_size[w][k];
         }
     }
     for (uint64_t at = 0; n_workers == 1 && at < count; at += batch_regions) {
@@ -832,7 +905,10 @@ int main(int argc, char **argv) {
         }
         HostGroups hg;
         if (boot_host) host_groups(n, out, hg);
-        if (boot && packed) { /* the one call that also returns the replicates (with the sets' handle: the labels' sums and scopes) */
+        if (size && packed) { /* the size blocks with the results (and, on the resident batch, the labels' sums and the replicates) */
+            if (compare_part_size(ctx, first + at, n, cfg, out, strata_route ? strata : nullptr, strat_total.data(), boot_total.data(), size_total.data()))
+                die(70, "compare failed", avk_last_error(ctx));
+        } else if (boot && packed) { /* the one call that also returns the replicates (with the sets' handle: the labels' sums and scopes) */
             if (compare_part_boot(ctx, first + at, n, cfg, out, strata_route ? strata : nullptr, strat_total.data(), boot_total.data())) die(70, "compare failed", avk_last_error(ctx));
         } else if (strata_route) { /* one call: the batch goes in, the sums come back with the results; the lists never exist on the host */
             if (compare_part_strata(ctx, first + at, n, cfg, out, strata, strat_total.data())) die(70, "compare failed", avk_last_error(ctx));
@@ -869,9 +945,11 @@ int main(int argc, char **argv) {
             if (avk_label_tallies(ctx, db, n_labels, label_off.data(), label_idx.data(), strat_total.data())) die(70, "stratified tallies failed", avk_last_error(ctx));
             avk_batch_free(ctx, db);
             if (boot_host && boot_part_host(b, out, label_off.data(), label_idx.data(), boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
+            if (size_host && size_part_host(b, out, label_off.data(), label_idx.data(), size_total.data())) die(70, "size-bin tallies failed", avk_last_error(nullptr));
         } else {
             if (compare_part(ctx, b, first + at, n, cfg, out)) die(70, "compare failed", avk_last_error(ctx));
             if (boot_host && boot_part_host(b, out, nullptr, nullptr, boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
+            if (size_host && size_part_host(b, out, nullptr, nullptr, size_total.data())) die(70, "size-bin tallies failed", avk_last_error(nullptr));
         }
         for (size_t k = 0; k < (size_t)AVK_TALLY_LEN; ++k) total[k] += tally[k];
         if (debug && (avf_region_summary_rows(region_table, genome, all, first + at, n, out.status, gm.data()) ||
@@ -922,6 +1000,25 @@ int main(int argc, char **argv) {
         if (avf_write_summary_ci((out_dir + "/summary_ci.tsv").c_str(), label.c_str(), total.data(), n_labels, ci_ptrs.data(), strat_total.data(), mask, boot_spec.replicates,
                                  boot_total.data(), boot_level))
             die(74, "Error while saving summary_ci.tsv", avf_last_error());
+    }
+    if (size) { /* summary_size.tsv: summary.tsv's GT / HAP / WEIGHTED_HAP rows per scope and size bin */
+        std::vector<std::string> sz_names, bin_names;
+        for (uint32_t l = 0; l < n_bed_labels; ++l) sz_names.push_back(avf_strat_label(strat, l));
+        for (uint32_t j = 0; j < n_ctx_labels; ++j) {
+            char name[64];
+            if (avk_context_label_name(&cx_spec, j, name, sizeof(name))) die(70, "context label name", avk_last_error(nullptr));
+            sz_names.push_back(name);
+        }
+        for (uint32_t j = 0; j < size_bins; ++j) {
+            char name[64];
+            if (avk_size_bin_name(&size_spec, j, name, sizeof(name))) die(70, "size bin name", avk_last_error(nullptr));
+            bin_names.push_back(name);
+        }
+        std::vector<const char *> sz_ptrs, bin_ptrs;
+        for (const std::string &n : sz_names) sz_ptrs.push_back(n.c_str());
+        for (const std::string &n : bin_names) bin_ptrs.push_back(n.c_str());
+        if (avf_write_summary_size((out_dir + "/summary_size.tsv").c_str(), label.c_str(), size_bins, bin_ptrs.data(), n_labels, sz_ptrs.data(), size_total.data(), mask))
+            die(74, "Error while saving summary_size.tsv", avf_last_error());
     }
     /* the annotated VCFs (VariantCategorizer): truth.vcf.gz and query.vcf.gz with their .tbi */
     std::string command;

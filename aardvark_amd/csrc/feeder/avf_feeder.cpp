@@ -1904,11 +1904,10 @@ int avf_write_summary_stratified(const char *path, const char *compare_label, co
     return avf_write_summary_named(path, compare_label, tally, (uint32_t)names.size(), names.data(), strat_tallies, metrics_mask);
 }
 
-int avf_write_summary_named(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names,
-                            const uint64_t *strat_tallies, uint32_t metrics_mask) {
-    if (!path || !tally || (n_labels && (!strat_tallies || !label_names))) return fail(AVK_E_ARG, "null argument");
-    for (uint32_t l = 0; l < n_labels; ++l)
-        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+/* The rows of a summary file, ONE statement for summary.tsv and summary_size.tsv: for each scope (region_label) and each filter the rows of the tally block
+ * tallies[scope * n_filters + filter] — per metric kind of the mask the ALL row, a row per call type that occurs, the joint rows that occur. */
+static int write_summary_rows(const char *path, const char *compare_label, uint32_t n_scopes, const char *const *scope_names, uint32_t n_filters, const char *const *filter_names,
+                              const uint64_t *const *tallies, uint32_t metrics_mask) {
     const std::string p(path);
     const char delim = p.size() >= 4 && p.compare(p.size() - 4, 4, ".csv") == 0 ? ',' : '\t';
     FILE *fp = fopen(path, "w");
@@ -1939,7 +1938,7 @@ int avf_write_summary_named(const char *path, const char *compare_label, const u
                            {AVF_METRIC_HAP, "HAP", AVK_F_HAP_TRUTH_TP, false},
                            {AVF_METRIC_WEIGHTED_HAP, "WEIGHTED_HAP", AVK_F_WHAP_TRUTH_TP, false},
                            {AVF_METRIC_RECORD_BP, "RECORD_BP", AVK_F_RBP_TRUTH_TP, false}};
-    std::string region_label = "ALL";
+    std::string region_label = "ALL", filter = "ALL";
     auto row = [&](const Kind &kd, const char *vtype, const uint64_t m[4], const uint64_t gt_extra[2]) {
         const uint64_t ttot = m[0] + m[1], qtot = m[2] + m[3];
         std::string recall, precision, f1;
@@ -1949,7 +1948,7 @@ int avf_write_summary_named(const char *path, const char *compare_label, const u
             const double r = (double)m[0] / (double)ttot, pr = (double)m[2] / (double)qtot;
             f1 = fmt_f64(2.0 * r * pr / (r + pr));
         }
-        fprintf(fp, "%s%c%s%c%s%cALL%c%s%c%llu%c%llu%c%llu%c%llu%c%llu%c%llu%c%s%c%s%c%s%c", label.c_str(), delim, kd.name, delim, region_label.c_str(), delim, delim, vtype, delim,
+        fprintf(fp, "%s%c%s%c%s%c%s%c%s%c%llu%c%llu%c%llu%c%llu%c%llu%c%llu%c%s%c%s%c%s%c", label.c_str(), delim, kd.name, delim, region_label.c_str(), delim, filter.c_str(), delim, vtype, delim,
                 (unsigned long long)ttot, delim, (unsigned long long)m[0], delim, (unsigned long long)m[1], delim, (unsigned long long)qtot, delim,
                 (unsigned long long)m[2], delim, (unsigned long long)m[3], delim, recall.c_str(), delim, precision.c_str(), delim, f1.c_str(), delim);
         if (kd.gt) fprintf(fp, "%llu%c%llu\n", (unsigned long long)gt_extra[0], delim, (unsigned long long)gt_extra[1]);
@@ -1985,14 +1984,53 @@ int avf_write_summary_named(const char *path, const char *compare_label, const u
             }
         }
     };
-    write_group(tally); /* the ALL group first (summary.rs:196-201) */
-    for (uint32_t l = 0; l < n_labels; ++l) {
-        region_label = csv_field(label_names[l], delim);
-        write_group(strat_tallies + (size_t)l * AVK_TALLY_LEN);
+    for (uint32_t sc = 0; sc < n_scopes; ++sc) { /* the ALL group first (summary.rs:196-201) */
+        region_label = csv_field(scope_names[sc], delim);
+        for (uint32_t fl = 0; fl < n_filters; ++fl) {
+            filter = csv_field(filter_names[fl], delim);
+            write_group(tallies[(size_t)sc * n_filters + fl]);
+        }
     }
     const bool bad = ferror(fp) != 0;
     if (fclose(fp) != 0 || bad) return fail(AVK_E_ARG, "write error on %s", path);
     return 0;
+}
+
+int avf_write_summary_named(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names,
+                            const uint64_t *strat_tallies, uint32_t metrics_mask) {
+    if (!path || !tally || (n_labels && (!strat_tallies || !label_names))) return fail(AVK_E_ARG, "null argument");
+    for (uint32_t l = 0; l < n_labels; ++l)
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+    std::vector<const char *> scopes = {"ALL"};
+    std::vector<const uint64_t *> blocks = {tally};
+    for (uint32_t l = 0; l < n_labels; ++l) scopes.push_back(label_names[l]), blocks.push_back(strat_tallies + (size_t)l * AVK_TALLY_LEN);
+    static const char *const all = "ALL";
+    return write_summary_rows(path, compare_label, 1 + n_labels, scopes.data(), 1, &all, blocks.data(), metrics_mask);
+}
+
+/* summary_size.tsv: the columns of summary.tsv with the size bin's name in `filter`.  For each scope (ALL, then the labels in order) and each bin the rows are those
+ * of avf_write_summary_named for a tally block whose fourteen GT / HAP / WEIGHTED_HAP words per group are the bin's (avk_size_tallies' layout:
+ * size_blocks[((scope * n_bins + bin) * AVK_N_GROUPS + g) * 14 + f]) and whose other words are zero.  BASEPAIR and RECORD_BP are properties of a region's
+ * haplotypes, not of a call: their mask bits are ignored. */
+int avf_write_summary_size(const char *path, const char *compare_label, uint32_t n_bins, const char *const *bin_names, uint32_t n_labels, const char *const *label_names,
+                           const uint64_t *size_blocks, uint32_t metrics_mask) {
+    if (!path || !n_bins || !bin_names || !size_blocks || (n_labels && !label_names)) return fail(AVK_E_ARG, "null argument, or no bins");
+    for (uint32_t b = 0; b < n_bins; ++b)
+        if (!bin_names[b]) return fail(AVK_E_ARG, "null argument");
+    for (uint32_t l = 0; l < n_labels; ++l)
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+    const int size_fields = AVK_F_WHAP_QUERY_FP + 1;
+    const size_t n_blocks = ((size_t)n_labels + 1) * n_bins;
+    std::vector<uint64_t> padded(n_blocks * AVK_TALLY_LEN, 0);
+    std::vector<const uint64_t *> blocks(n_blocks);
+    for (size_t k = 0; k < n_blocks; ++k) {
+        for (int g = 0; g < AVK_N_GROUPS; ++g)
+            for (int f = 0; f < size_fields; ++f) padded[k * AVK_TALLY_LEN + (size_t)g * AVK_N_FIELDS + f] = size_blocks[(k * AVK_N_GROUPS + g) * size_fields + f];
+        blocks[k] = padded.data() + k * AVK_TALLY_LEN;
+    }
+    std::vector<const char *> scopes = {"ALL"};
+    for (uint32_t l = 0; l < n_labels; ++l) scopes.push_back(label_names[l]);
+    return write_summary_rows(path, compare_label, 1 + n_labels, scopes.data(), n_bins, bin_names, blocks.data(), metrics_mask & ~(uint32_t)(AVF_METRIC_BASEPAIR | AVF_METRIC_RECORD_BP));
 }
 
 

@@ -410,6 +410,20 @@ def write_summary_named(path, tally, names, strat_tallies, compare_label="compar
     _check(lib, lib.avf_write_summary_named(os.fsencode(path), compare_label.encode(), t.ctypes.data_as(u64p), len(names), arr, st.ctypes.data_as(u64p), metrics))
 
 
+def write_summary_size(path, bin_names, names, size_blocks, compare_label="compare", metrics=METRIC_GT | METRIC_HAP | METRIC_WEIGHTED_HAP):
+    """avf_write_summary_size: summary_size.tsv — the rows of write_summary_named per scope (ALL, then `names`) and size bin, the bin's name in the `filter` column;
+    size_blocks is [1 + len(names), len(bin_names), N_GROUPS, 14] (Context.size_tallies' layout).  BASEPAIR and RECORD_BP bits of `metrics` are ignored"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    sb = np.ascontiguousarray(size_blocks, dtype=np.uint64)
+    if sb.ndim != 4 or sb.shape[0] != 1 + len(names) or sb.shape[1] != len(bin_names) or sb.shape[3] != 14:
+        raise ValueError("size_blocks is [1 + labels, bins, N_GROUPS, 14]")
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names]) if names else None
+    bins = (C.c_char_p * len(bin_names))(*[b.encode() for b in bin_names])
+    lib.avf_write_summary_size.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32]
+    _check(lib, lib.avf_write_summary_size(os.fsencode(path), compare_label.encode(), len(bin_names), bins, len(names), arr, sb.reshape(-1).ctypes.data_as(u64p), metrics))
+
+
 def write_summary_ci(path, tally, names, strat_tallies, boot_blocks, level=95, compare_label="compare", metrics=METRIC_GT | METRIC_BASEPAIR):
     """avf_write_summary_ci: the rows of write_summary_named with percentile intervals of recall, precision and F1 over the bootstrap replicates `boot_blocks`
     ([1 + len(names), replicates, TALLY_LEN], Context.boot_tallies' layout); level: 90, 95 or 99"""

@@ -633,6 +633,40 @@ int  avk_compare_packed_boot(avk_ctx *ctx, const avk_packed_batch *batch, const 
 int  avk_boot_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_boot_spec *spec, const avk_region_labels *labels, uint32_t threads,
                            uint64_t *out);
 
+/* PER-CALL TALLIES BY SIZE BIN (avk_sizebin.inl; the rule is this project's own, stated in aardvark_amd/csrc/avk_sizebin.h and DESIGN.md section 5): how the
+ * errors depend on the size of the variant — 1-5 bp indels against 6-15 bp against >= 50 bp — where every label above is a property of a region.
+ *   size     size(call) = |a1_len - a0_len| of the call as the batch holds it (after the feeder's trimming, escaped lengths resolved); SNVs are size 0
+ *   spec     avk_size_spec { n_edges, edges[AVK_SIZE_EDGES_MAX] }: 1 <= n_edges <= 15, edges[0] >= 1, strictly ascending — anything else is AVK_E_ARG, out
+ *            untouched; n_bins = n_edges + 1; bin 0: size < edges[0]; bin j: edges[j - 1] <= size < edges[j]; the last bin: size >= edges[n_edges - 1].
+ *            The default spec is {1, 6, 16, 50}: len_0, len_1_5, len_6_15, len_16_49, len_ge50
+ *   call     a call of a SOLVED region (status 0) contributes one iteration of GroupMetrics::add_truth_zygosity (grouped_metrics.rs:183-227) as
+ *            avk_group_metrics_from_compact states it per call — gt_tp, gt_fn, gt_fn_gt, hap_tp, hap_fn, w_tp, w_fn, the toggled reading of query entries and the
+ *            32-bit products included — to the truth fields of its side or to the query fields, of group 0 and group 1 + type, in bin(size), in scope 0 and in
+ *            scope 1 + l for every label l of the strata handle that holds the call's region
+ *   block    out[((scope * n_bins + bin) * AVK_N_GROUPS + g) * AVK_SIZE_FIELDS + f], f = AVK_F_GT_TRUTH_TP .. AVK_F_WHAP_QUERY_FP (14 fields): GT, HAP and
+ *            WEIGHTED_HAP only — BASEPAIR and RECORD_BP are properties of a region's haplotypes (waffle_solver.rs:335-522) and belong to no single call
+ *   out      sums are ADDED; the block is additive over batches, slices, shards and ranks (avk_counts_allreduce takes it as it is)
+ *   law      for every scope, group and f < 14 the sum over the bins equals word g * AVK_N_FIELDS + f of that scope's tally (avk_result_batch::tally for scope 0,
+ *            the label's block of avk_label_tallies_strata for scope 1 + l)
+ * The submit / wait forms and the merge take no spec. */
+#include "../aardvark_amd/csrc/avk_sizebin.h"
+uint32_t avk_size_n_bins(const avk_size_spec *spec);                                        /* n_edges + 1; 0 for a spec the rule refuses */
+int  avk_size_bin_name(const avk_size_spec *spec, uint32_t j, char *buf, size_t cap);       /* len_<lo>_<hi> (inclusive), len_<lo> for one size, len_ge<lo> for the last bin */
+uint32_t avk_size_block(const avk_ctx *ctx);                                                /* regions a workgroup of the kernel takes at a time */
+/* resident form: a device-packed batch (wide, compact or packed upload, with or without escapes) after avk_compare_resident, otherwise AVK_E_STATE; neither
+ * emit_bp_groups nor emit_group_metrics is needed; a handle of another context is AVK_E_ARG.  strata == NULL: scope 0 only.  Called after avk_results_download it
+ * also counts the regions the capacity retry repaired. */
+int  avk_size_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *spec, const avk_strata *strata, uint64_t *out);
+/* avk_compare_packed_esc that also returns the block (ADDED to size_out): results and tally are bit for bit those of the plain call; regions the capacity retry
+ * repairs are counted.  strata == NULL or zero labels: scope 0 only.  The option device_pack 0 is AVK_E_STATE (host route: avk_size_tallies_host). */
+int  avk_compare_packed_size(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata, const avk_compare_config *cfg,
+                             const avk_size_spec *spec, avk_result_batch *out, uint64_t *size_out);
+/* host only (no GPU involved): the same sums from the wide batch and its results (status or region_packed; var_expected and var_observed, or var_packed), alt_ed
+ * by avk_edit_distance's rule, scopes from labels (NULL: scope 0 only; a label named twice in a region's list counts twice).  threads: host threads (0: one); the
+ * sums do not depend on the cut. */
+int  avk_size_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_size_spec *spec, const avk_region_labels *labels, uint32_t threads,
+                           uint64_t *out);
+
 /* SEQUENCE-CONTEXT labels (avk_context.inl): labels that are functions of the reference sequence alone, made by kernel from the reference avk_ref_upload left in
  * HBM — a stratified job needs no BED set for them.  The rule is this project's own (the reference has no such labels):
  *   window   a region's query is the one the interval sets get, [first, last] on its contig; a family's window is [first - pad, last + 1 + pad), clamped to the

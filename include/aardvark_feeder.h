@@ -156,6 +156,13 @@ int avf_write_summary_stratified(const char *path, const char *compare_label, co
  * avf_write_summary_stratified is this function with the names of the sets. */
 int avf_write_summary_named(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names,
                             const uint64_t *strat_tallies, uint32_t metrics_mask);
+/* summary_size.tsv: the columns of summary.tsv, the `filter` column holding the size bin's name (avk_size_bin_name).  size_blocks is avk_size_tallies' block,
+ * [1 + n_labels][n_bins][AVK_N_GROUPS][14]; for each scope (ALL, then the labels in order) and each bin the rows — order, joint rows, rows left out, number
+ * formatting — are those avf_write_summary_named writes for a tally block whose fourteen GT / HAP / WEIGHTED_HAP words per group are the bin's and whose other
+ * words are zero.  Rows are GT, and HAP / WEIGHTED_HAP when their mask bits are set; AVF_METRIC_BASEPAIR and AVF_METRIC_RECORD_BP are ignored: those counts belong
+ * to a region's haplotypes, not to a call. */
+int avf_write_summary_size(const char *path, const char *compare_label, uint32_t n_bins, const char *const *bin_names, uint32_t n_labels, const char *const *label_names,
+                           const uint64_t *size_blocks, uint32_t metrics_mask);
 /* summary_ci.tsv: the rows of avf_write_summary_named for the same tallies — same order, same key columns (compare_label comparison region_label filter variant_type),
  * rows it leaves out left out, point values formatted alike — followed by metric_recall recall_lo recall_hi metric_precision precision_lo precision_hi metric_f1 f1_lo
  * f1_hi replicates: percentile intervals over bootstrap replicates (avk_boot_tallies' layout: boot_blocks[(scope * replicates + b) * AVK_TALLY_LEN + word], scope 0
