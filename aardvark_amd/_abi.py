@@ -277,6 +277,62 @@ def declare_size(lib):
     lib.avk_size_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkSizeSpec), _p(AvkRegionLabels), C.c_uint32, u64p]
 
 
+SCORE_THRESHOLDS_MAX, SCORE_FIELDS = 31, 14
+SCORE_DEFAULT = (5, 10, 15, 20, 25, 30, 35, 40, 50, 60)
+
+
+class AvkScoreSpec(C.Structure):
+    """avk_score_spec: the thresholds of the curve by query score (aardvark_amd/csrc/avk_score.h has the rule)"""
+    _fields_ = [("n_thresholds", C.c_uint32), ("t", C.c_float * SCORE_THRESHOLDS_MAX)]
+
+
+class ScoreSpec:
+    """Thresholds of the precision-recall curve by query score: 1 to 31 finite, strictly ascending float32 values; point 0 is "no filter", point k is
+    score >= thresholds[k - 1].  The library checks the spec; an invalid one is refused there."""
+
+    def __init__(self, thresholds=SCORE_DEFAULT):
+        self.thresholds = tuple(float(t) for t in thresholds)
+
+    @property
+    def n_points(self):
+        return len(self.thresholds) + 1
+
+    def c_struct(self):
+        s = AvkScoreSpec()
+        s.n_thresholds = len(self.thresholds)
+        for k, t in enumerate(self.thresholds[:SCORE_THRESHOLDS_MAX]):
+            s.t[k] = t
+        return s
+
+    def names(self):
+        """avk_score_point_name for every point: score_all, then score_ge_<t> (%g)"""
+        from .api import load_library
+        lib, cs, out = load_library(), self.c_struct(), []
+        for k in range(self.n_points):
+            buf = C.create_string_buffer(64)
+            if lib.avk_score_point_name(C.byref(cs), k, buf, 64):
+                raise ValueError(lib.avk_last_error(None).decode())
+            out.append(buf.value.decode())
+        return out
+
+
+def declare_score(lib):
+    """avk_score_n_points, avk_score_point_name, avk_score_block, avk_score_tallies, avk_compare_packed_score, avk_score_tallies_host (include/aardvark_amd.h)"""
+    vp, u64p, f32p = C.c_void_p, _p(C.c_uint64), _p(C.c_float)
+    lib.avk_score_n_points.restype = C.c_uint32
+    lib.avk_score_n_points.argtypes = [_p(AvkScoreSpec)]
+    lib.avk_score_point_name.restype = C.c_int
+    lib.avk_score_point_name.argtypes = [_p(AvkScoreSpec), C.c_uint32, C.c_char_p, C.c_size_t]
+    lib.avk_score_block.restype = C.c_uint32
+    lib.avk_score_block.argtypes = [vp]
+    lib.avk_score_tallies.restype = C.c_int
+    lib.avk_score_tallies.argtypes = [vp, vp, _p(AvkScoreSpec), f32p, vp, u64p]
+    lib.avk_compare_packed_score.restype = C.c_int
+    lib.avk_compare_packed_score.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkScoreSpec), f32p, _p(AvkResultBatch), u64p]
+    lib.avk_score_tallies_host.restype = C.c_int
+    lib.avk_score_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkScoreSpec), f32p, _p(AvkRegionLabels), C.c_uint32, u64p]
+
+
 CONTEXT_PAD_MAX, CONTEXT_GC_EDGES_MAX, CONTEXT_HP_EDGES_MAX = 1024, 17, 16
 
 

@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
-                   PackedBatch, RegionBatch, ResultBatch, BootSpec, ContextSpec, SizeSpec, SIZE_FIELDS, N_GROUPS, declare_boot, declare_size, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
+                   PackedBatch, RegionBatch, ResultBatch, BootSpec, ContextSpec, SizeSpec, SIZE_FIELDS, ScoreSpec, SCORE_FIELDS, N_GROUPS, declare_boot, declare_size, declare_score, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
                    region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -94,6 +94,8 @@ def load_library():
         declare_boot(lib)
     if hasattr(lib, "avk_size_tallies"):  # per-call tallies by size bin (avk_sizebin.inl); (AVK_LIB may name an older in-tree build: A/B runs)
         declare_size(lib)
+    if hasattr(lib, "avk_score_tallies"):  # the curve by query score (avk_score.inl); (AVK_LIB may name an older in-tree build: A/B runs)
+        declare_score(lib)
     if hasattr(lib, "avk_debug_ref_packed"):  # (AVK_LIB may name an older in-tree build: A/B runs)
         declare_debug_ref_packed(lib)
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
@@ -308,7 +310,8 @@ class Context:
         esc = None if pbatch.escapes is None else pbatch.escapes.pinned(self.host_array)
         return PackedBatch(escapes=esc, **{f: pin(getattr(pbatch, f)) for f in PackedBatch.FIELDS})
 
-    def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None, strata=None, boot=None, boot_tallies=None, size=None, size_tallies=None):
+    def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None, strata=None, boot=None, boot_tallies=None, size=None, size_tallies=None, score=None, scores=None,
+                     score_tallies=None):
         """avk_compare_packed: solve_compare_region for every region of a batch in the packed form -> ResultBatch (indexed like the packed arrays).
         labels=(n_labels, label_off, label_idx): avk_compare_packed_labels — the per-label sums come back as res.label_tallies, a [n_labels, TALLY_LEN] uint64
         array (label_tallies: an array of that shape the sums are added to instead).
@@ -316,10 +319,23 @@ class Context:
         boot=a BootSpec: avk_compare_packed_boot — the bootstrap replicates come back as res.boot_tallies, a [1 + n_labels, replicates, TALLY_LEN] uint64 array
         (scope 0: every region; scope 1 + l: label l of `strata`; boot_tallies: an array of that shape the sums are added to instead).
         size=a SizeSpec: avk_compare_packed_size — the per-call tallies by size bin come back as res.size_tallies, a [1 + n_labels, n_bins, N_GROUPS, 14] uint64
-        array (scopes as above; size_tallies: an array of that shape the sums are added to instead); it returns no label sums: labels, label_tallies and boot raise ValueError"""
+        array (scopes as above; size_tallies: an array of that shape the sums are added to instead); it returns no label sums: labels, label_tallies and boot raise ValueError.
+        score=a ScoreSpec, scores=a float32 array of n_variants (indexed like the packed call arrays; query entries are read, NaN: missing): avk_compare_packed_score —
+        the curve by query score comes back as res.score_tallies, a [1 + n_labels, n_points, N_GROUPS, 14] uint64 array (score_tallies: an array the sums are added
+        to instead); like size it excludes labels, label_tallies, boot and size"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
         pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
+        if score is not None:
+            if labels is not None or label_tallies is not None or (boot is not None and boot.replicates) or size is not None:
+                raise ValueError("score takes strata, not label lists, returns no label sums (label_tallies) and excludes boot and size")
+            n_labels = 0 if strata is None else strata.n_labels
+            blocks = np.zeros((1 + n_labels, score.n_points, N_GROUPS, SCORE_FIELDS), np.uint64) if score_tallies is None else score_tallies
+            ss, sc = score.c_struct(), _scores_array(scores, pbatch.n_variants)
+            self._check(self.lib.avk_compare_packed_score(self.handle, C.byref(pb), None if esc is None else C.byref(esc), None if strata is None else strata.handle, C.byref(cfg),
+                                                          C.byref(ss), None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_float)), C.byref(ro), blocks.ctypes.data_as(u64p)))
+            res.score_tallies = blocks
+            return res
         if size is not None:
             if labels is not None or label_tallies is not None or (boot is not None and boot.replicates):
                 raise ValueError("size takes strata, not label lists, returns no label sums (label_tallies) and excludes boot")
@@ -542,6 +558,21 @@ class Context:
         self._check(self.lib.avk_size_tallies(self.handle, rb.handle, C.byref(ss), None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
         return out
 
+    def score_block(self):
+        """avk_score_block: how many regions a workgroup of the score histogram kernel takes at a time (one lane each)"""
+        return int(self.lib.avk_score_block(self.handle))
+
+    def score_tallies(self, rb, spec, scores, strata=None, out=None):
+        """avk_score_tallies: the precision-recall curve by query score of a solved resident batch; scores: a float32 array of the batch's n_variants, indexed like
+        its call arrays (NaN: missing); returns / adds to a [1 + n_labels, n_points, N_GROUPS, 14] uint64 array — scope 0: every region; scope 1 + l: label l of
+        `strata`; point 0: no filter; point k: score >= thresholds[k - 1]"""
+        n_labels = 0 if strata is None else strata.n_labels
+        out = np.zeros((1 + n_labels, spec.n_points, N_GROUPS, SCORE_FIELDS), np.uint64) if out is None else out
+        ss, sc = spec.c_struct(), _scores_array(scores, rb.batch.n_variants)
+        self._check(self.lib.avk_score_tallies(self.handle, rb.handle, C.byref(ss), None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_float)),
+                                               None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
+        return out
+
     def synchronize(self):
         self._check(self.lib.avk_synchronize(self.handle))
 
@@ -647,6 +678,33 @@ def group_metrics_from_compact(batch, res):
         rc = lib.avk_group_metrics_from_compact(C.byref(cb), r, C.byref(ro), out[r].ctypes.data_as(C.POINTER(C.c_uint32)))
         if rc != 0:
             raise AardvarkAmdError("avk_group_metrics_from_compact failed for region %d" % r)
+    return out
+
+
+def _scores_array(scores, n_variants):
+    """a contiguous float32 array (None stays None: the library refuses it by name); n_variants: the length the batch asks for, when it is known here"""
+    if scores is None:
+        return None
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    if n_variants is not None and sc.size != int(n_variants):
+        raise ValueError("scores holds %d values, the batch %d calls" % (sc.size, int(n_variants)))
+    return sc
+
+
+def score_tallies_host(batch, res, spec, scores, labels=None, threads=1, out=None):
+    """avk_score_tallies_host: Context.score_tallies' curve on the host from a wide RegionBatch, its ResultBatch and the scores (no GPU involved);
+    labels=(n_labels, label_off, label_idx) or None -> [1 + n_labels, n_points, N_GROUPS, 14] uint64 (added to `out`)"""
+    lib = load_library()
+    n_labels = 0 if labels is None else int(labels[0])
+    out = np.zeros((1 + n_labels, spec.n_points, N_GROUPS, SCORE_FIELDS), np.uint64) if out is None else out
+    cb, ro, ss, sc = batch.c_struct(), res.c_struct(), spec.c_struct(), _scores_array(scores, batch.n_variants)
+    lab = None
+    if labels is not None:
+        lab, _keep = region_labels(*labels)
+    rc = lib.avk_score_tallies_host(C.byref(cb), C.byref(ro), C.byref(ss), None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_float)), None if lab is None else C.byref(lab),
+                                    int(threads), out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc:
+        raise AardvarkAmdError("avk_score_tallies_host: %d: %s" % (rc, lib.avk_last_error(None).decode()))
     return out
 
 

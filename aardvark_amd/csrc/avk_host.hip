@@ -3032,9 +3032,17 @@ struct SizeStage {
     uint64_t *sums; /* the caller's [(1 + n_labels) * n_bins * AVK_N_GROUPS * AVK_SIZE_FIELDS]: gains the sums */
 };
 static int size_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *sp, const avk_strata *st, uint64_t *out);
+/* ... and the curve by query score (avk_compare_packed_score), likewise */
+struct ScoreStage {
+    const avk_score_spec *spec;
+    const float *scores; /* the caller's [n_variants] */
+    const avk_strata *st;
+    uint64_t *sums; /* the caller's [(1 + n_labels) * n_points * AVK_N_GROUPS * AVK_SCORE_FIELDS]: gains the sums */
+};
+static int score_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_score_spec *sp, const float *scores, const avk_strata *st, uint64_t *out);
 static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_result_batch *out, uint64_t n, const char *timed_as,
                             const std::function<int(const CallSpec &, avk_dev_batch **)> &upload, const LabelStage *ls = nullptr, const BootStage *boot = nullptr,
-                            const SizeStage *size = nullptr) {
+                            const SizeStage *size = nullptr, const ScoreStage *score = nullptr) {
     ctx->last_one_shot = 0;
     CallSpec spec = call_spec(ctx, out, ls != nullptr || boot != nullptr); /* (the groups are what the label kernel reads, whether the caller asked for them or not) */
     const uint32_t n_labels = !ls ? 0 : ls->st ? ls->st->n_labels : ls->lab->n_labels;
@@ -3079,6 +3087,7 @@ static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_res
     if (ls) (void)hipStreamSynchronize(ctx->stream);
     if (!rc && boot) rc = boot_sums_run(ctx, db, boot->spec, job.st ? job.st->n_labels : 0, (const uint32_t *)L.d_mask, boot->sums);
     if (!rc && size) rc = size_resident_run(ctx, db, size->spec, size->st, size->sums);
+    if (!rc && score) rc = score_resident_run(ctx, db, score->spec, score->scores, score->st, score->sums);
     strata_lists_release(ctx, L);
     pool_release(ctx, d_out);
     if (db) {
@@ -3482,6 +3491,151 @@ int avk_size_tallies_host(const avk_region_batch *b, const avk_result_batch *res
         if (bad[t]) return fail(nullptr, AVK_E_ARG, "size bins: a region's calls lie outside the batch");
     for (uint32_t t = 0; t < T; ++t)
         for (size_t k = 0; k < words; ++k) out[k] += part[t][k];
+    return 0;
+}
+
+/* ---- precision-recall curve by query score (avk_score.h, avk_score.inl) -------------------------------------------------------------------------------- */
+} /* extern "C" */
+#include "avk_score.inl"
+#include "avk_score_host.h"
+extern "C" {
+static_assert(AVK_SCORE_FIELDS == AVK_SIZE_FIELDS && AVK_SCORE_FIELDS == AVK_F_WHAP_QUERY_FP + 1, "the score block's fields are the size block's");
+static_assert(AVK_SC_BLOCK_WORDS(AVK_SCORE_THRESHOLDS_MAX + 1) * 8 <= AVK_SC_LDS_BYTES && AVK_SC_THREADS % 64 == 0 && AVK_N_VARIANT_TYPES < 15 && AVK_SCORE_THRESHOLDS_MAX < 32,
+              "a workgroup of avk_score_hist_kernel holds one scope's block of the widest spec, whole waves, and a key its bin and type");
+/* the refusals of every entry point with a spec, before anything is queued (no device involved) */
+static int score_spec_check(avk_ctx *ctx, const avk_score_spec *sp, const float *scores, const uint64_t *out) {
+    if (!sp) return fail(ctx, AVK_E_ARG, "score curve: spec missing");
+    if (!avk_score_spec_ok(sp)) return fail(ctx, AVK_E_ARG, "score curve: 1 to %d thresholds, every one finite, strictly ascending", AVK_SCORE_THRESHOLDS_MAX);
+    if (!scores) return fail(ctx, AVK_E_ARG, "score curve: scores missing");
+    if (!out) return fail(ctx, AVK_E_ARG, "score_tallies missing");
+    return 0;
+}
+uint32_t avk_score_n_points(const avk_score_spec *sp) { return avk_score_spec_ok(sp) ? sp->n_thresholds + 1u : 0u; }
+uint32_t avk_score_block(const avk_ctx *ctx) { return ctx ? AVK_SC_THREADS : 0; }
+int avk_score_point_name(const avk_score_spec *sp, uint32_t k, char *buf, size_t cap) {
+    if (!avk_score_spec_ok(sp) || k > sp->n_thresholds || !buf || !cap) return fail(nullptr, AVK_E_ARG, "score curve: invalid spec, point or buffer");
+    const int w = k == 0 ? snprintf(buf, cap, "score_all") : snprintf(buf, cap, "score_ge_%g", (double)sp->t[k - 1]);
+    return w > 0 && (size_t)w < cap ? 0 : fail(nullptr, AVK_E_ARG, "score curve: the name buffer is too small");
+}
+/* scores in, histograms cleared, the histogram kernel over blocks of scopes, the curve kernel, copy back, wait, added to the caller's: on the context's stream */
+static int score_sums_run(avk_ctx *ctx, avk_dev_batch *db, const avk_score_spec *sp, const float *scores, uint32_t n_labels, const uint32_t *d_mask, uint64_t *out) {
+    if (!d_mask) n_labels = 0;
+    const uint64_t n = db->n_regions, nv = db->dp_args.in.n_variants;
+    const uint32_t n_points = sp->n_thresholds + 1u, n_scopes = 1u + n_labels;
+    const size_t hist_words = (size_t)n_scopes * AVK_SC_BLOCK_WORDS(n_points), curve_words = (size_t)n_scopes * AVK_SC_H_WORDS(n_points);
+    if (!n) return 0;
+    /* one pool block: the curve, the error word (in a 64-bit slot), the histograms; the scores in a second */
+    std::vector<uint64_t> host(curve_words + 1, 0);
+    void *d_blk = nullptr, *d_scores = nullptr;
+    int rc = pool_alloc(ctx, &d_blk, (curve_words + 1 + hist_words) * 8);
+    if (!rc) rc = pool_alloc(ctx, &d_scores, (size_t)nv * 4 + 16);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_blk, 0, (curve_words + 1 + hist_words) * 8, ctx->stream);
+    if (!rc && e == hipSuccess && nv) e = hipMemcpyAsync(d_scores, scores, (size_t)nv * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (!rc && e == hipSuccess) {
+        uint64_t *d_curve = (uint64_t *)d_blk, *d_hist = d_curve + curve_words + 1;
+        uint32_t *d_err = (uint32_t *)(d_curve + curve_words);
+        avk::lb::LbView v;
+        memset(&v, 0, sizeof(v));
+        v.in = db->dp_args.in, v.vinfo = db->dp_args.vinfo, v.region_out = db->d_region_out, v.var_out = db->d_var_out, v.v_off = db->d_voff;
+        const uint32_t block_bytes = AVK_SC_BLOCK_WORDS(n_points) * 8u;
+        uint32_t per_launch = AVK_SC_LDS_BYTES / block_bytes;
+        if (per_launch > AVK_SC_SCOPES_MAX) per_launch = AVK_SC_SCOPES_MAX;
+        const uint64_t tiles = (n + AVK_SC_THREADS - 1) / AVK_SC_THREADS;
+        for (uint32_t lo = 0; lo < n_scopes && e == hipSuccess; lo += per_launch) {
+            const uint32_t hi = n_scopes - lo > per_launch ? lo + per_launch : n_scopes;
+            const uint32_t lds_words = (hi - lo) * AVK_SC_BLOCK_WORDS(n_points);
+            /* as many workgroups a CU as this launch's blocks fit its 160 KB of LDS beside each other — two for a 32-point scope, eight (the CU's 2,048
+             * work-items) for one scope of a few thresholds —, and no more workgroups than tiles: each flushes its block once */
+            uint32_t per_cu = (uint32_t)(AVK_SC_CU_LDS_BYTES / ((size_t)lds_words * 8));
+            per_cu = per_cu < 1u ? 1u : per_cu > 2048u / AVK_SC_THREADS ? 2048u / AVK_SC_THREADS : per_cu;
+            const uint64_t blocks = tiles < (uint64_t)ctx->n_cus * per_cu ? tiles : (uint64_t)ctx->n_cus * per_cu;
+            hipLaunchKernelGGL(avk_score_hist_kernel, dim3((unsigned)blocks), dim3(AVK_SC_THREADS), (size_t)lds_words * 8, ctx->stream, v, d_mask, (uint32_t)n, *sp,
+                               (const float *)d_scores, lo, hi, lds_words, (unsigned long long *)d_hist, d_err);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(avk_score_curve_kernel, dim3(n_scopes * AVK_N_GROUPS), dim3(64), 0, ctx->stream, (const unsigned long long *)d_hist, n_points, n_scopes,
+                               (const uint32_t *)d_err, (unsigned long long *)d_curve);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d_curve, (curve_words + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    pool_release(ctx, d_blk), pool_release(ctx, d_scores);
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(ctx, AVK_E_HIP, "score curve failed: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    if (host[curve_words]) return fail(ctx, AVK_E_HIP, "score curve: the kernel refused its launch (error word %llu); nothing was added", (unsigned long long)host[curve_words]);
+    for (size_t k = 0; k < curve_words; ++k) out[k] += host[k];
+    return 0;
+}
+/* a solved resident batch: the scopes' membership (the strata pass's masks, nothing else of the lists), then the sums */
+static int score_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_score_spec *sp, const float *scores, const avk_strata *st, uint64_t *out) {
+    const uint64_t n = db->n_regions;
+    StrataLists L;
+    int rc = 0;
+    if (st && st->n_labels && n) {
+        rc = strata_lists_alloc(ctx, st, n, L);
+        if (!rc) {
+            const hipError_t e = strata_mask_launch(st, db->dp_args.in, n, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums, ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata masks failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (!rc) rc = score_sums_run(ctx, db, sp, scores, L.d_mask ? st->n_labels : 0, (const uint32_t *)L.d_mask, out);
+    else (void)hipStreamSynchronize(ctx->stream);
+    strata_lists_release(ctx, L);
+    return rc;
+}
+
+int avk_score_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_score_spec *sp, const float *scores, const avk_strata *st, uint64_t *out) {
+    if (!ctx || !db) return AVK_E_ARG;
+    {
+        const int rs = score_spec_check(ctx, sp, scores, out);
+        if (rs) return rs;
+    }
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    if (!db->dev_packed) return fail(ctx, AVK_E_STATE, "the score curve on the device needs a device-packed batch: the option device_pack was 0 at its upload (host route: avk_score_tallies_host)");
+    if (!db->has_run || db->last_mode != 0) return fail(ctx, AVK_E_STATE, "the score curve needs a batch that avk_compare_resident has solved");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    return score_resident_run(ctx, db, sp, scores, st, out);
+}
+
+int avk_compare_packed_score(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg,
+                             const avk_score_spec *sp, const float *scores, avk_result_batch *out, uint64_t *score_out) {
+    if (!batch) return AVK_E_ARG;
+    if (st && st->n_labels == 0) st = nullptr;
+    {
+        const int rs = score_spec_check(ctx, sp, scores, score_out);
+        if (rs) return rs;
+    }
+    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->device_pack) return fail(ctx, AVK_E_STATE, "the score curve on the device needs the option device_pack (host route: avk_score_tallies_host)");
+    if (!esc_present(esc)) esc = nullptr;
+    const ScoreStage score{sp, scores, st, score_out};
+    return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, nullptr, nullptr,
+                            nullptr, &score);
+}
+
+int avk_score_tallies_host(const avk_region_batch *b, const avk_result_batch *res, const avk_score_spec *sp, const float *scores, const avk_region_labels *lab, uint32_t threads,
+                           uint64_t *out) {
+    if (!b || !res) return fail(nullptr, AVK_E_ARG, "score curve: batch or results missing");
+    const uint32_t n_labels = lab ? lab->n_labels : 0;
+    {
+        const int rs = score_spec_check(nullptr, sp, scores, out);
+        if (rs) return rs;
+        if (lab && n_labels) {
+            const int rl = labels_check(nullptr, b->n_regions, lab, out);
+            if (rl) return rl;
+        }
+    }
+    if (!(res->status || res->region_packed)) return fail(nullptr, AVK_E_ARG, "score curve: the results have neither status nor region_packed");
+    const bool wide_calls = res->var_expected && res->var_observed;
+    if (!wide_calls && !res->var_packed) return fail(nullptr, AVK_E_ARG, "score curve: the results have no per-call outputs");
+    /* the sums themselves: plain C++ in a header of its own, which the sanitizer program of the tests includes as well */
+    if (avk_score_host_sum(b, res, sp, scores, lab && n_labels ? lab : nullptr, threads, avk::host_edit_distance, out))
+        return fail(nullptr, AVK_E_ARG, "score curve: a region's calls lie outside the batch, or a label is not one of the labels");
     return 0;
 }
 

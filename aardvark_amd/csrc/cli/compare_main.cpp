@@ -45,7 +45,10 @@ void usage() {
             "   recall, precision and F1; default 0: off, no file)  [--bootstrap-seed 1] [--bootstrap-level 90|95|99 (default 95)]\n"
             "  [--size-strata]  (writes summary_size.tsv: summary.tsv's GT, HAP and WEIGHTED_HAP rows per size bin of the calls, size = |alt length - ref length|, the bin's\n"
             "   name in the filter column, summed on the GPU; BASEPAIR and RECORD_BP rows are not part of this file: they belong to a region's haplotypes, not to a call)\n"
-            "  [--size-edges 1,6,16,50]  (1 to 15 ascending sizes, the first at least 1; default bins len_0 len_1_5 len_6_15 len_16_49 len_ge50)\n");
+            "  [--size-edges 1,6,16,50]  (1 to 15 ascending sizes, the first at least 1; default bins len_0 len_1_5 len_6_15 len_16_49 len_ge50)\n"
+            "  [--roc QUAL|GQ]  (writes summary_roc.tsv: summary.tsv's GT, HAP and WEIGHTED_HAP rows once per threshold on the query calls' QUAL or FORMAT/GQ, the point's name\n"
+            "   in the filter column, summed on the GPU from the ONE comparison of the job: an approximation of a filtered re-run per threshold, which could draw other regions)\n"
+            "  [--roc-thresholds 5,10,15,20,25,30,35,40,50,60]  (1 to 31 finite, strictly ascending numbers; points score_all, score_ge_5, ..)\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -101,6 +104,9 @@ int main(int argc, char **argv) {
     /* --size-strata: per-call tallies by size bin (avk_size_spec) for summary_size.tsv */
     bool size = false, size_override = false;
     std::vector<uint32_t> size_edges = {1, 6, 16, 50};
+    /* --roc: the precision-recall curve by the query calls' QUAL or GQ (avk_score_spec) for summary_roc.tsv */
+    bool roc = false, roc_override = false;
+    std::string roc_field, roc_list = "5,10,15,20,25,30,35,40,50,60";
     auto number_list = [](const std::string &opt, const std::string &list) {
         std::vector<uint32_t> out;
         for (size_t b = 0; b <= list.size();) {
@@ -197,6 +203,8 @@ int main(int argc, char **argv) {
         }
         else if (a == "--size-strata") size = true;
         else if (a == "--size-edges") size_edges = number_list(a, val()), size_override = true;
+        else if (a == "--roc") roc_field = val(), roc = true;
+        else if (a == "--roc-thresholds") roc_list = val(), roc_override = true;
         else if (a == "-h" || a == "--help") {
             usage();
             return 0;
@@ -253,6 +261,29 @@ int main(int argc, char **argv) {
         if (!debug_dir.empty()) die(64, "--size-strata cannot be combined with --output-debug (the debug run writes per-region tables, not size bins)", "");
         if (!strat_tsv.empty() && strat_lists == "host" && want_packed)
             die(64, "--size-strata on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
+    }
+    /* The curve by query score is summed where the size bins are, on the same routes (avk_compare_packed_score, avk_score_tallies on the resident batch,
+     * avk_score_tallies_host on the wide feed); the same combinations are refused, by name. */
+    avk_score_spec roc_spec;
+    memset(&roc_spec, 0, sizeof(roc_spec));
+    if (roc_override && !roc) die(64, "--roc-thresholds needs --roc", "");
+    if (roc) {
+        if (roc_field != "QUAL" && roc_field != "GQ") die(64, "--roc takes QUAL or GQ: unknown field", roc_field.c_str());
+        const char *bad_list = "--roc-thresholds takes 1 to 31 finite, strictly ascending numbers";
+        for (size_t b = 0; b <= roc_list.size();) {
+            const size_t e = roc_list.find(',', b);
+            const std::string item = roc_list.substr(b, e == std::string::npos ? std::string::npos : e - b);
+            char *end = nullptr;
+            const float x = strtof(item.c_str(), &end);
+            if (item.empty() || *end || roc_spec.n_thresholds >= AVK_SCORE_THRESHOLDS_MAX) die(64, bad_list, roc_list.c_str());
+            roc_spec.t[roc_spec.n_thresholds++] = x;
+            if (e == std::string::npos) break;
+            b = e + 1;
+        }
+        if (!avk_score_n_points(&roc_spec)) die(64, bad_list, roc_list.c_str()); /* (the library's own check of the spec) */
+        if (!debug_dir.empty()) die(64, "--roc cannot be combined with --output-debug (the debug run writes per-region tables, not a curve)", "");
+        if (!strat_tsv.empty() && strat_lists == "host" && want_packed)
+            die(64, "--roc on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
     }
     if (!devices.empty()) device = devices[0];
     if (mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create output folder", out_dir.c_str());
@@ -372,6 +403,17 @@ int main(int argc, char **argv) {
         avf_calls_free(calls[1]);
     });
     const avk_region_batch *all = avf_feed_batch(feed);
+    /* --roc: the query VCF's scores, one pass over its data lines, gathered into the feed's call order (the packed form's order too); truth entries are NaN */
+    std::vector<float> roc_scores(roc ? all->n_variants + 1 : 0);
+    if (roc) {
+        const uint64_t *rec = avf_feed_var_record(feed);
+        uint64_t n_records = 0;
+        for (uint64_t v = 0; v < all->n_variants; ++v) n_records = rec[v] + 1 > n_records ? rec[v] + 1 : n_records;
+        std::vector<float> per_record(n_records + 1);
+        if (avf_vcf_scores(query.c_str(), query_sample.c_str(), roc_field.c_str(), n_records, per_record.data()) ||
+            avf_feed_scores(feed, per_record.data(), n_records, roc_scores.data()))
+            die(74, "Error while reading the query scores", avf_last_error());
+    }
     if (th_reserve.joinable()) th_reserve.join();
     const double s_feed = seconds_since(t0);
     fprintf(stderr, "Loaded %llu truth and %llu query variants; %llu regions.\n", (unsigned long long)avf_feed_loaded_variants(feed, 0),
@@ -473,6 +515,34 @@ int main(int argc, char **argv) {
         if (db) avk_batch_free(c, db);
         return rc;
     };
+    /* --roc on the packed feed, the same way: alone one call (avk_compare_packed_score); with label sums, replicates or size bins of the same batch on the resident
+     * batch.  A part's scores are the feed's from its first call on */
+    auto compare_part_roc = [&](avk_ctx *c, uint64_t at_abs, uint64_t n, const avk_compare_config &cfg, const avk_result_batch &out, const avk_strata *sets, uint64_t *sums,
+                                uint64_t *reps, uint64_t *blocks, uint64_t *curve) -> int {
+        avk_packed_batch part;
+        avk_packed_escapes part_esc;
+        uint64_t v_first = 0;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, &v_first)) return AVK_E_ARG;
+        avk_result_batch shifted = out_for(out, v_first);
+        const float *sc = roc_scores.data() + v_first;
+        if (!sets && !boot && !size) return avk_compare_packed_score(c, &part, &part_esc, nullptr, &cfg, &roc_spec, sc, &shifted, curve);
+        avk_dev_batch *db = nullptr;
+        int rc = avk_batch_upload_packed_esc(c, &part, &part_esc, &db);
+        if (!rc) rc = avk_compare_resident(c, db, &cfg, nullptr);
+        if (!rc) rc = avk_results_download(c, db, &shifted);
+        if (!rc && sets) rc = avk_label_tallies_strata(c, db, sets, sums);
+        if (!rc && boot) rc = avk_boot_tallies(c, db, &boot_spec, sets, reps);
+        if (!rc && size) rc = avk_size_tallies(c, db, &size_spec, sets, blocks);
+        if (!rc) rc = avk_score_tallies(c, db, &roc_spec, sc, sets, curve);
+        if (db) avk_batch_free(c, db);
+        return rc;
+    };
+    /* --roc on the wide feed: the part's curve from its results on the host (the part's call offsets are the feed's) */
+    auto roc_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *curve) -> int {
+        avk_region_labels lab;
+        lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
+        return avk_score_tallies_host(&b, &out, &roc_spec, roc_scores.data(), n_labels ? &lab : nullptr, 16, curve);
+    };
     /* --size-strata on the wide feed: the part's blocks from its results on the host */
     auto size_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *blocks) -> int {
         avk_region_labels lab;
@@ -540,9 +610,20 @@ int main(int argc, char **argv) {
     const bool boot_host = boot && !packed; /* the wide feed: avk_boot_tallies_host on each part's results */
     if (size && packed && n_labels && !strata_route) die(70, "--size-strata on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
     const bool size_host = size && !packed;                            /* the wide feed: avk_size_tallies_host on each part's results */
-    const bool size_resident = size && packed && (strata_route || boot); /* label sums or replicates of the same batch: the kernels run on the resident batch */
+    const bool size_resident = size && packed && (strata_route || boot || roc); /* label sums, replicates or the score curve of the same batch: the kernels run on the resident batch */
+    if (roc && packed && n_labels && !strata_route) die(70, "--roc on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
+    const bool roc_host = roc && !packed;                                   /* the wide feed: avk_score_tallies_host on each part's results */
+    const bool roc_resident = roc && packed && (strata_route || boot || size); /* other sums of the same batch: the kernels run on the resident batch */
     (void)avk_ctx_set_option(ctx, "emit_group_metrics", (n_labels && !compact_labels) || debug ? 1 : 0);
-    if (boot_host || size_resident) (void)avk_ctx_set_option(ctx, "emit_bp_groups", 1);
+    if (boot_host || size_resident || roc_resident) (void)avk_ctx_set_option(ctx, "emit_bp_groups", 1);
+    const uint32_t roc_points = roc ? roc_spec.n_thresholds + 1 : 0;
+    std::vector<uint64_t> roc_total(roc ? ((size_t)n_labels + 1) * roc_points * AVK_N_GROUPS * AVK_SCORE_FIELDS : 0, 0);
+    if (verbosity && roc)
+        fprintf(stderr, "Score curve: %u points by %s in summary_roc.tsv (GT, HAP, WEIGHTED_HAP; no BASEPAIR rows), from the one comparison of the job; the points are summed %s.\n",
+                roc_points, roc_field.c_str(),
+                roc_host       ? "on the host from each batch's results (avk_score_tallies_host, the wide feed)"
+                : roc_resident ? "on the GPU on each resident batch behind its solve and download (avk_score_tallies)"
+                               : "on the GPU behind each batch's solve (avk_compare_packed_score)");
     const uint32_t size_bins = size ? size_spec.n_edges + 1 : 0;
     std::vector<uint64_t> size_total(size ? ((size_t)n_labels + 1) * size_bins * AVK_N_GROUPS * AVK_SIZE_FIELDS : 0, 0);
     if (verbosity && size)
@@ -601,7 +682,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "Bootstrap: the hash-sharded route does not carry the replicates; --bootstrap selects the route on which the contexts share the region batches.\n");
     if (verbosity && size && n_workers > 1 && packed && !n_labels)
         fprintf(stderr, "Size bins: the hash-sharded route does not carry the blocks; --size-strata selects the route on which the contexts share the region batches.\n");
-    if (n_workers > 1 && packed && !n_labels && !boot && !size) {
+    if (verbosity && roc && n_workers > 1 && packed && !n_labels)
+        fprintf(stderr, "Score curve: the hash-sharded route does not carry the blocks; --roc selects the route on which the contexts share the region batches.\n");
+    if (n_workers > 1 && packed && !n_labels && !boot && !size && !roc) {
         sharded = true;
         avk_packed_batch sel;
         avk_packed_escapes sel_esc;
@@ -725,7 +808,7 @@ int main(int argc, char **argv) {
         std::vector<std::string> worker_err(n_workers);
         std::vector<std::vector<uint64_t>> w_total(n_workers, std::vector<uint64_t>(AVK_TALLY_LEN, 0)),
             w_strat(n_workers, std::vector<uint64_t>((size_t)n_labels * AVK_TALLY_LEN, 0)), w_boot(n_workers, std::vector<uint64_t>(boot_total.size(), 0)),
-            w_size(n_workers, std::vector<uint64_t>(size_total.size(), 0));
+            w_size(n_workers, std::vector<uint64_t>(size_total.size(), 0)), w_roc(n_workers, std::vector<uint64_t>(roc_total.size(), 0));
         std::mutex log_mutex;
         auto worker = [&](size_t w) {
             avk_ctx *my = ctx;
@@ -748,7 +831,7 @@ int main(int argc, char **argv) {
                     return;
                 }
                 (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels && !compact_labels ? 1 : 0);
-                if (boot_host || size_resident) (void)avk_ctx_set_option(my, "emit_bp_groups", 1);
+                if (boot_host || size_resident || roc_resident) (void)avk_ctx_set_option(my, "emit_bp_groups", 1);
             }
             avk_strata *my_sets = w > 0 ? nullptr : strata;
             if (w > 0 && strata_route && cx_given && strata_upload(my, &my_sets)) { /* (context labels: no host route) */
@@ -760,8 +843,10 @@ int main(int argc, char **argv) {
                 std::lock_guard<std::mutex> lock(log_mutex);
                 fprintf(stderr, "Warning: cannot upload the stratification sets to context %zu: %s; its region labels are listed on the host.\n", w, avk_last_error(my));
                 my_sets = nullptr;
-                if (boot || size) { /* (the replicates' and the size bins' scopes are read from the sets on the GPU) */
-                    worker_err[w] = boot ? "--bootstrap: cannot upload the stratification sets to every context" : "--size-strata: cannot upload the stratification sets to every context";
+                if (boot || size || roc) { /* (the replicates', the size bins' and the curve's scopes are read from the sets on the GPU) */
+                    worker_err[w] = boot   ? "--bootstrap: cannot upload the stratification sets to every context"
+                                    : size ? "--size-strata: cannot upload the stratification sets to every context"
+                                           : "--roc: cannot upload the stratification sets to every context";
                     avk_ctx_destroy(my);
                     return;
                 }
@@ -790,7 +875,9 @@ int main(int argc, char **argv) {
                 int rc = 0;
                 HostGroups hg;
                 if (boot_host) host_groups(n, out, hg);
-                if (size && packed) rc = compare_part_size(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data(), w_size[w].data());
+                if (roc && packed)
+                    rc = compare_part_roc(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data(), w_size[w].data(), w_roc[w].data());
+                else if (size && packed) rc = compare_part_size(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data(), w_size[w].data());
                 else if (boot && packed) rc = compare_part_boot(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data());
                 else if (strata_route && my_sets) rc = compare_part_strata(my, first + at, n, cfg, out, my_sets, w_strat[w].data());
                 else if (n_labels) {
@@ -823,6 +910,10 @@ int main(int argc, char **argv) {
                             worker_err[w] = std::string("size-bin tallies failed: ") + avk_last_error(nullptr);
                             break;
                         }
+                        if (!rc && roc_host && roc_part_host(b, out, label_off.data(), label_idx.data(), w_roc[w].data())) {
+                            worker_err[w] = std::string("score curve failed: ") + avk_last_error(nullptr);
+                            break;
+                        }
                     }
                 } else {
                     rc = compare_part(my, b, first + at, n, cfg, out);
@@ -832,6 +923,10 @@ int main(int argc, char **argv) {
                     }
                     if (!rc && size_host && size_part_host(b, out, nullptr, nullptr, w_size[w].data())) {
                         worker_err[w] = std::string("size-bin tallies failed: ") + avk_last_error(nullptr);
+                        break;
+                    }
+                    if (!rc && roc_host && roc_part_host(b, out, nullptr, nullptr, w_roc[w].data())) {
+                        worker_err[w] = std::string("score curve failed: ") + avk_last_error(nullptr);
                         break;
                     }
                 }
@@ -862,6 +957,7 @@ int main(int argc, char **argv) {
             for (size_t k = 0; k < strat_total.size(); ++k) strat_total[k] += w_strat[w][k];
             for (size_t k = 0; k < boot_total.size(); ++k) boot_total[k] += w_boot[w][k]; /* the contexts' blocks, added on the host */
             for (size_t k = 0; k < size_total.size(); ++k) size_total[k] += w_size[w][k];
+            for (size_t k = 0; k < roc_total.size(); ++k) roc_total[k] += w_roc[w][k];
         }
     }
     for (uint64_t at = 0; n_workers == 1 && at < count; at += batch_regions) {
@@ -905,7 +1001,10 @@ int main(int argc, char **argv) {
         }
         HostGroups hg;
         if (boot_host) host_groups(n, out, hg);
-        if (size && packed) { /* the size blocks with the results (and, on the resident batch, the labels' sums and the replicates) */
+        if (roc && packed) { /* the curve with the results (and, on the resident batch, the labels' sums, the replicates and the size blocks) */
+            if (compare_part_roc(ctx, first + at, n, cfg, out, strata_route ? strata : nullptr, strat_total.data(), boot_total.data(), size_total.data(), roc_total.data()))
+                die(70, "compare failed", avk_last_error(ctx));
+        } else if (size && packed) { /* the size blocks with the results (and, on the resident batch, the labels' sums and the replicates) */
             if (compare_part_size(ctx, first + at, n, cfg, out, strata_route ? strata : nullptr, strat_total.data(), boot_total.data(), size_total.data()))
                 die(70, "compare failed", avk_last_error(ctx));
         } else if (boot && packed) { /* the one call that also returns the replicates (with the sets' handle: the labels' sums and scopes) */
@@ -946,10 +1045,12 @@ int main(int argc, char **argv) {
             avk_batch_free(ctx, db);
             if (boot_host && boot_part_host(b, out, label_off.data(), label_idx.data(), boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
             if (size_host && size_part_host(b, out, label_off.data(), label_idx.data(), size_total.data())) die(70, "size-bin tallies failed", avk_last_error(nullptr));
+            if (roc_host && roc_part_host(b, out, label_off.data(), label_idx.data(), roc_total.data())) die(70, "score curve failed", avk_last_error(nullptr));
         } else {
             if (compare_part(ctx, b, first + at, n, cfg, out)) die(70, "compare failed", avk_last_error(ctx));
             if (boot_host && boot_part_host(b, out, nullptr, nullptr, boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
             if (size_host && size_part_host(b, out, nullptr, nullptr, size_total.data())) die(70, "size-bin tallies failed", avk_last_error(nullptr));
+            if (roc_host && roc_part_host(b, out, nullptr, nullptr, roc_total.data())) die(70, "score curve failed", avk_last_error(nullptr));
         }
         for (size_t k = 0; k < (size_t)AVK_TALLY_LEN; ++k) total[k] += tally[k];
         if (debug && (avf_region_summary_rows(region_table, genome, all, first + at, n, out.status, gm.data()) ||
@@ -1019,6 +1120,25 @@ int main(int argc, char **argv) {
         for (const std::string &n : bin_names) bin_ptrs.push_back(n.c_str());
         if (avf_write_summary_size((out_dir + "/summary_size.tsv").c_str(), label.c_str(), size_bins, bin_ptrs.data(), n_labels, sz_ptrs.data(), size_total.data(), mask))
             die(74, "Error while saving summary_size.tsv", avf_last_error());
+    }
+    if (roc) { /* summary_roc.tsv: summary.tsv's GT / HAP / WEIGHTED_HAP rows per scope and point of the curve */
+        std::vector<std::string> sc_names, point_names;
+        for (uint32_t l = 0; l < n_bed_labels; ++l) sc_names.push_back(avf_strat_label(strat, l));
+        for (uint32_t j = 0; j < n_ctx_labels; ++j) {
+            char name[64];
+            if (avk_context_label_name(&cx_spec, j, name, sizeof(name))) die(70, "context label name", avk_last_error(nullptr));
+            sc_names.push_back(name);
+        }
+        for (uint32_t k = 0; k < roc_points; ++k) {
+            char name[64];
+            if (avk_score_point_name(&roc_spec, k, name, sizeof(name))) die(70, "score point name", avk_last_error(nullptr));
+            point_names.push_back(name);
+        }
+        std::vector<const char *> sc_ptrs, point_ptrs;
+        for (const std::string &n : sc_names) sc_ptrs.push_back(n.c_str());
+        for (const std::string &n : point_names) point_ptrs.push_back(n.c_str());
+        if (avf_write_summary_roc((out_dir + "/summary_roc.tsv").c_str(), label.c_str(), roc_points, point_ptrs.data(), n_labels, sc_ptrs.data(), roc_total.data(), mask))
+            die(74, "Error while saving summary_roc.tsv", avf_last_error());
     }
     /* the annotated VCFs (VariantCategorizer): truth.vcf.gz and query.vcf.gz with their .tbi */
     std::string command;

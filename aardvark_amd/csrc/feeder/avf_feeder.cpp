@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -2031,6 +2032,85 @@ int avf_write_summary_size(const char *path, const char *compare_label, uint32_t
     std::vector<const char *> scopes = {"ALL"};
     for (uint32_t l = 0; l < n_labels; ++l) scopes.push_back(label_names[l]);
     return write_summary_rows(path, compare_label, 1 + n_labels, scopes.data(), n_bins, bin_names, blocks.data(), metrics_mask & ~(uint32_t)(AVF_METRIC_BASEPAIR | AVF_METRIC_RECORD_BP));
+}
+
+/* summary_roc.tsv: the same file keyed by the POINTS of the curve by query score (avk_score_tallies' layout, [1 + n_labels][n_points][AVK_N_GROUPS][14]): the
+ * point's name (avk_score_point_name) in `filter`.  One layout, one writer: the rows — a metric whose denominator is 0 at a point included — are written as
+ * summary.tsv writes them. */
+int avf_write_summary_roc(const char *path, const char *compare_label, uint32_t n_points, const char *const *point_names, uint32_t n_labels, const char *const *label_names,
+                          const uint64_t *score_blocks, uint32_t metrics_mask) {
+    if (!path || !n_points || !point_names || !score_blocks || (n_labels && !label_names)) return fail(AVK_E_ARG, "null argument, or no points");
+    return avf_write_summary_size(path, compare_label, n_points, point_names, n_labels, label_names, score_blocks, metrics_mask);
+}
+
+/* ---- scores of a VCF's records for the curve by query score ----------------------------------------------------------------------------------------- */
+namespace {
+/* a VCF number -> float; ".", an empty field and anything strtof does not take whole are missing (NaN) */
+float score_field(std::string_view s) {
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    if (s.empty() || s == ".") return nan;
+    const std::string z(s);
+    char *end = nullptr;
+    const float x = strtof(z.c_str(), &end);
+    return end == z.c_str() || *end ? nan : x;
+}
+} // namespace
+
+int avf_vcf_scores(const char *vcf, const char *sample, const char *field, uint64_t n_records, float *out) {
+    if (!vcf || !field || (n_records && !out)) return fail(AVK_E_ARG, "null argument");
+    const bool qual = strcmp(field, "QUAL") == 0;
+    if (!qual && strcmp(field, "GQ") != 0) return fail(AVK_E_ARG, "score field \"%s\": QUAL or GQ", field);
+    for (uint64_t k = 0; k < n_records; ++k) out[k] = std::numeric_limits<float>::quiet_NaN();
+    LineReader in(vcf);
+    if (!in.ok()) return fail(AVK_E_ARG, "Error while opening %s", vcf);
+    std::string line;
+    VcfScratch w;
+    long sample_col = -1;
+    uint64_t record = 0;
+    bool have_header = false;
+    while (in.next(line)) {
+        if (line.empty()) continue;
+        if (line[0] == '#') {
+            if (line.compare(0, 6, "#CHROM") == 0) {
+                const int rc = vcf_sample_column(vcf, line, sample, w, sample_col);
+                if (rc) return rc;
+                have_header = true;
+            }
+            continue;
+        }
+        if (!have_header) return fail(AVK_E_ARG, "%s: data line before the #CHROM header", vcf);
+        const uint64_t rec = record++; /* (the index vcf_parse_record gives the line: avf_feed_var_record) */
+        if (rec >= n_records) continue;
+        split_sv(line, '\t', w.v);
+        if (qual) {
+            if (w.v.size() > 5) out[rec] = score_field(w.v[5]);
+            continue;
+        }
+        if ((long)w.v.size() <= sample_col) continue;
+        split_sv(w.v[8], ':', w.fmt);
+        split_sv(w.v[(size_t)sample_col], ':', w.sv);
+        for (size_t k = 0; k < w.fmt.size(); ++k)
+            if (w.fmt[k] == "GQ") {
+                if (k < w.sv.size()) out[rec] = score_field(w.sv[k]);
+                break;
+            }
+    }
+    if (in.failed()) return fail(AVK_E_ARG, "read error in %s", vcf);
+    if (!have_header) return fail(AVK_E_ARG, "%s has no #CHROM header line", vcf);
+    return 0;
+}
+
+int avf_feed_scores(const avf_feed *f, const float *per_record, uint64_t n_records, float *out) {
+    const avk_region_batch *b = f ? avf_feed_batch(f) : nullptr;
+    const uint64_t *rec = f ? avf_feed_var_record(f) : nullptr;
+    if (!b || !rec || (n_records && !per_record) || (b->n_variants && !out)) return fail(AVK_E_ARG, "null argument, or not a compare feed");
+    for (uint64_t v = 0; v < b->n_variants; ++v) out[v] = std::numeric_limits<float>::quiet_NaN(); /* truth entries carry no score */
+    for (uint64_t r = 0; r < b->n_regions; ++r) {
+        if (b->q_off[r] > b->n_variants || b->q_cnt[r] > b->n_variants - b->q_off[r]) return fail(AVK_E_ARG, "a region's calls lie outside the batch");
+        for (uint64_t v = b->q_off[r]; v < b->q_off[r] + b->q_cnt[r]; ++v)
+            if (rec[v] < n_records) out[v] = per_record[rec[v]];
+    }
+    return 0;
 }
 
 

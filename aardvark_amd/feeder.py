@@ -297,7 +297,19 @@ def _take_feed(lib, h, k, merge):
         lib.avf_feed_free(h)
 
 
-def feed_compare(truth_vcf, query_vcf, regions_bed, genome, truth_sample="", query_sample="", min_variant_gap=50, enable_trimming=True):
+def vcf_scores(vcf, field, n_records, sample=""):
+    """avf_vcf_scores: the score of each of the first n_records data lines of a VCF -> float32 [n_records]; field: "QUAL" (column 6) or "GQ" (FORMAT/GQ of
+    `sample`; "": the first sample); ".", an absent key or a value that is no number gives NaN"""
+    lib = load_library()
+    out = np.zeros(int(n_records), np.float32)
+    lib.avf_vcf_scores.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_float)]
+    _check(lib, lib.avf_vcf_scores(os.fsencode(vcf), sample.encode(), field.encode(), int(n_records), out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def feed_compare(truth_vcf, query_vcf, regions_bed, genome, truth_sample="", query_sample="", min_variant_gap=50, enable_trimming=True, score_field=None):
+    """score_field="QUAL" or "GQ": the feed also carries .scores, a float32 per call in the batch's (and the packed form's) call order — the query VCF's field
+    gathered through var_record (avf_vcf_scores, avf_feed_scores); truth entries are NaN"""
     lib = load_library()
     h = C.c_void_p()
     _check(lib, lib.avf_feed_compare(os.fsencode(truth_vcf), truth_sample.encode(), os.fsencode(query_vcf), query_sample.encode(),
@@ -310,8 +322,17 @@ def feed_compare(truth_vcf, query_vcf, regions_bed, genome, truth_sample="", que
                             _arr(b.var_pos, nv, np.uint64), _arr(b.var_type, nv, np.uint8), _arr(b.var_zyg, nv, np.uint8), _arr(b.var_raw_space, nv, np.uint32),
                             _arr(b.a0_off, nv, np.uint64), _arr(b.a0_len, nv, np.uint32), _arr(b.a1_off, nv, np.uint64), _arr(b.a1_len, nv, np.uint32),
                             _arr(b.allele_bytes, int(b.allele_bytes_len), np.uint8))
-        return Feed(batch, _arr(lib.avf_feed_var_record(h), nv, np.uint64), _arr(lib.avf_feed_var_alt_index(h), nv, np.uint32),
+        feed = Feed(batch, _arr(lib.avf_feed_var_record(h), nv, np.uint64), _arr(lib.avf_feed_var_alt_index(h), nv, np.uint32),
                     (int(lib.avf_feed_loaded_variants(h, 0)), int(lib.avf_feed_loaded_variants(h, 1))), *_both_packed(lib, h, False))
+        feed.scores = None
+        if score_field is not None:
+            n_records = int(feed.var_record.max()) + 1 if nv else 0
+            per_record = vcf_scores(query_vcf, score_field, n_records, query_sample)
+            feed.scores = np.zeros(nv, np.float32)
+            f32p = C.POINTER(C.c_float)
+            lib.avf_feed_scores.argtypes = [C.c_void_p, f32p, C.c_uint64, f32p]
+            _check(lib, lib.avf_feed_scores(h, per_record.ctypes.data_as(f32p), n_records, feed.scores.ctypes.data_as(f32p)))
+        return feed
     finally:
         lib.avf_feed_free(h)
 
@@ -422,6 +443,21 @@ def write_summary_size(path, bin_names, names, size_blocks, compare_label="compa
     bins = (C.c_char_p * len(bin_names))(*[b.encode() for b in bin_names])
     lib.avf_write_summary_size.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32]
     _check(lib, lib.avf_write_summary_size(os.fsencode(path), compare_label.encode(), len(bin_names), bins, len(names), arr, sb.reshape(-1).ctypes.data_as(u64p), metrics))
+
+
+def write_summary_roc(path, point_names, names, score_blocks, compare_label="compare", metrics=METRIC_GT | METRIC_HAP | METRIC_WEIGHTED_HAP):
+    """avf_write_summary_roc: summary_roc.tsv — the rows of write_summary_named per scope (ALL, then `names`) and point of the curve by query score, the point's
+    name in the `filter` column; score_blocks is [1 + len(names), len(point_names), N_GROUPS, 14] (Context.score_tallies' layout).  BASEPAIR and RECORD_BP bits of
+    `metrics` are ignored"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    sb = np.ascontiguousarray(score_blocks, dtype=np.uint64)
+    if sb.ndim != 4 or sb.shape[0] != 1 + len(names) or sb.shape[1] != len(point_names) or sb.shape[3] != 14:
+        raise ValueError("score_blocks is [1 + labels, points, N_GROUPS, 14]")
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names]) if names else None
+    points = (C.c_char_p * len(point_names))(*[b.encode() for b in point_names])
+    lib.avf_write_summary_roc.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32]
+    _check(lib, lib.avf_write_summary_roc(os.fsencode(path), compare_label.encode(), len(point_names), points, len(names), arr, sb.reshape(-1).ctypes.data_as(u64p), metrics))
 
 
 def write_summary_ci(path, tally, names, strat_tallies, boot_blocks, level=95, compare_label="compare", metrics=METRIC_GT | METRIC_BASEPAIR):

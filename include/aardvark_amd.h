@@ -667,6 +667,36 @@ int  avk_compare_packed_size(avk_ctx *ctx, const avk_packed_batch *batch, const 
 int  avk_size_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_size_spec *spec, const avk_region_labels *labels, uint32_t threads,
                            uint64_t *out);
 
+/* PRECISION-RECALL CURVE BY QUERY SCORE (avk_score.inl; the rule is this project's own, stated in aardvark_amd/csrc/avk_score.h and DESIGN.md section 5): what
+ * recall and precision the caller keeps at QUAL >= 20, at every threshold of a list, from ONE solve.  The curve is derived from that one comparison — as hap.py's
+ * is — and so approximates K filtered re-runs: a filtered re-run could draw different regions.
+ *   score    scores[n_variants], a float per call, indexed like the batch's call arrays; only query entries are read; NaN: missing
+ *   spec     avk_score_spec { n_thresholds, t[AVK_SCORE_THRESHOLDS_MAX] }: 1 <= n_thresholds <= 31, every threshold finite, strictly ascending — anything else
+ *            is AVK_E_ARG, out untouched; n_points = n_thresholds + 1; point 0: no filter; point k >= 1: score >= t[k - 1]
+ *   bin      of a query call: the number of thresholds <= score in float32 (NaN: 0, +inf: n_thresholds, -inf: 0); kept at the points 0 .. bin.  Of a truth call:
+ *            n_thresholds when its observed count is 0; otherwise the minimum bin over the query calls of its region with hap_tp > 0 (n_thresholds if none)
+ *   point k  a query call with k <= bin adds the seven values of a call of the size rule to the query fields, otherwise nothing; a truth call with k <= bin adds
+ *            them to the truth fields, otherwise its LOST values (gt_fn = 1, hap_fn = expected, w_fn = (u32)(expected * alt_ed)) — to group 0 and group 1 + type,
+ *            in scope 0 and scope 1 + l for every label l of the strata handle that holds its region; unsolved regions add nothing
+ *   block    out[((scope * n_points + k) * AVK_N_GROUPS + g) * AVK_SCORE_FIELDS + f], f = AVK_F_GT_TRUTH_TP .. AVK_F_WHAP_QUERY_FP; sums are ADDED
+ *   law      point 0 is the size block summed over its bins, i.e. the first 14 fields of the tally; GT_TRUTH_TP + GT_TRUTH_FN and HAP_TRUTH_TP + HAP_TRUTH_FN
+ *            are the same at every point; every TP field and every query field is non-increasing in k
+ * The submit / wait forms, the hash-sharded route and the merge take no spec. */
+#include "../aardvark_amd/csrc/avk_score.h"
+uint32_t avk_score_n_points(const avk_score_spec *spec);                                    /* n_thresholds + 1; 0 for a spec the rule refuses */
+int  avk_score_point_name(const avk_score_spec *spec, uint32_t k, char *buf, size_t cap);   /* score_all for point 0, score_ge_<t> (%g) for the others */
+uint32_t avk_score_block(const avk_ctx *ctx);                                               /* regions a workgroup of the histogram kernel takes at a time */
+/* resident form: a device-packed batch after avk_compare_resident, otherwise AVK_E_STATE; scores (host, n_variants floats; NULL: AVK_E_ARG) are copied into a pool
+ * buffer on the call's stream.  strata == NULL: scope 0 only.  An error word from the kernel keeps the block from reaching out. */
+int  avk_score_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_score_spec *spec, const float *scores, const avk_strata *strata, uint64_t *out);
+/* avk_compare_packed_esc that also returns the block (ADDED to score_out): results and tally are bit for bit those of the plain call.  The option device_pack 0
+ * is AVK_E_STATE (host route: avk_score_tallies_host). */
+int  avk_compare_packed_score(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata, const avk_compare_config *cfg,
+                              const avk_score_spec *spec, const float *scores, avk_result_batch *out, uint64_t *score_out);
+/* host only (no GPU involved): the same rule from the wide batch and its results, scopes from labels (NULL: scope 0 only).  threads: host threads (0: one) */
+int  avk_score_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_score_spec *spec, const float *scores,
+                            const avk_region_labels *labels, uint32_t threads, uint64_t *out);
+
 /* SEQUENCE-CONTEXT labels (avk_context.inl): labels that are functions of the reference sequence alone, made by kernel from the reference avk_ref_upload left in
  * HBM — a stratified job needs no BED set for them.  The rule is this project's own (the reference has no such labels):
  *   window   a region's query is the one the interval sets get, [first, last] on its contig; a family's window is [first - pad, last + 1 + pad), clamped to the

@@ -163,6 +163,18 @@ int avf_write_summary_named(const char *path, const char *compare_label, const u
  * to a region's haplotypes, not to a call. */
 int avf_write_summary_size(const char *path, const char *compare_label, uint32_t n_bins, const char *const *bin_names, uint32_t n_labels, const char *const *label_names,
                            const uint64_t *size_blocks, uint32_t metrics_mask);
+/* summary_roc.tsv: the same for the curve by query score — score_blocks is avk_score_tallies' block, [1 + n_labels][n_points][AVK_N_GROUPS][14], and the `filter`
+ * column holds the point's name (avk_score_point_name: score_all, score_ge_<t>).  Rows are GT, and HAP / WEIGHTED_HAP when their mask bits are set, once per scope
+ * and point; a metric whose denominator is 0 at a point is written as summary.tsv writes such a metric. */
+int avf_write_summary_roc(const char *path, const char *compare_label, uint32_t n_points, const char *const *point_names, uint32_t n_labels, const char *const *label_names,
+                          const uint64_t *score_blocks, uint32_t metrics_mask);
+/* The scores of a VCF's records for that curve, in one pass over its data lines: out[rec] for the first n_records data lines (the index avf_feed_var_record
+ * speaks of), NaN where the file has fewer.  field: "QUAL" (column 6) or "GQ" (FORMAT/GQ of `sample`; NULL or "": the first sample); ".", an absent key or a value
+ * that is no number gives NaN.  The record parser is not involved. */
+int avf_vcf_scores(const char *vcf, const char *sample, const char *field, uint64_t n_records, float *out);
+/* ... gathered into the batch's call order: out[v] = per_record[avf_feed_var_record[v]] for the query entries of a compare feed (a multi-allelic record gives
+ * each of its calls its score; a record at or beyond n_records gives NaN), NaN for the truth entries.  out: n_variants floats. */
+int avf_feed_scores(const avf_feed *f, const float *per_record, uint64_t n_records, float *out);
 /* summary_ci.tsv: the rows of avf_write_summary_named for the same tallies — same order, same key columns (compare_label comparison region_label filter variant_type),
  * rows it leaves out left out, point values formatted alike — followed by metric_recall recall_lo recall_hi metric_precision precision_lo precision_hi metric_f1 f1_lo
  * f1_hi replicates: percentile intervals over bootstrap replicates (avk_boot_tallies' layout: boot_blocks[(scope * replicates + b) * AVK_TALLY_LEN + word], scope 0
