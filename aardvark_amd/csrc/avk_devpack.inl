@@ -1176,8 +1176,8 @@ AVK_DEV u32 dp_unpack_bp_need(const DpOut &o, u64 r, u32 &word) {
     }
     return hi - lo;
 }
-/* `need` / `word` from dp_unpack_bp_need; `at` = where the region's spilled groups go (the kernel hands the places out a workgroup at a time: one atomic per 256
- * regions instead of one per wave — 56,000 returning atomics on one word were 0.4 ms of a whole-genome call); at == 0xFFFFFFFF: taken here, with an atomic of its own */
+/* `need` / `word` from dp_unpack_bp_need; `at` = where the region's spilled groups go (the kernel hands the places out a workgroup at a time: one atomic per 2,048
+ * regions — 56,000 returning atomics on one word, one per wave, were 0.4 ms of a whole-genome call, 14,000 still 0.1 ms); at == 0xFFFFFFFF: taken here, with an atomic of its own */
 AVK_DEV void dp_unpack(const DpOut &o, u64 r, u32 need, u32 word, u32 at) {
     if (r >= o.n_regions) return;
     const avk_u4 w = *(const avk_u4 *)(o.region_out + 4 * r);
@@ -1213,6 +1213,38 @@ AVK_DEV void dp_unpack(const DpOut &o, u64 r, u32 need, u32 word, u32 at) {
         if (o.var_class) o.var_class[hv] = (u8)((x >> 16) & 0xFF);
         if (o.var_zyg) o.var_zyg[hv] = (u8)(x >> 24);
         if (o.var_packed) o.var_packed[hv] = (u8)((x & 3u) | ((x >> 8) & 3u) << 2 | ((x >> 24) & 7u) << 4);
+    }
+}
+
+/* ---- dp_unpack_calls: the per-call outputs of a dense batch read from its packed source, by element -------------------------------------
+ * dp_unpack above stores word v_off[r] + k of var_out at call (k < tc ? toff + k : qoff + k - tc) - v_lo.  For a batch read from its packed source toff = pk_voff[r]
+ * and qoff = toff + tc, so that is call pk_voff[r] + k - v_lo.  pk_voff is the exclusive running sum of pk_tc + pk_qc over the regions in the caller's order
+ * (queue_prefix_sum); v_off is the exclusive running sum of the same counts in the same order (avk_dp_scan_apply_kernel: t_cnt_of / q_cnt_of are pk_tc / pk_qc, and a
+ * region that fails the range check adds 0 there but also sets DP_ERR_RANGE, which check_state refuses).  The packed form owns its calls by construction
+ * (avk_owned_range: v_lo = 0, v_hi = n_variants) and first_passes has checked that the counts sum to n_variants.  Hence pk_voff[r] - v_lo == v_off[r] for every r:
+ * word j of var_out is call v_lo + j, byte j of every per-call output, and every j < n_calls is some region's (the batch is dense: total_v == v_hi - v_lo).
+ * Lane q takes the calls [4q, 4q + 4): one 16-byte load, one 32-bit store per output; the last lane a tail of 1 to 3 calls, byte by byte.  var_out and the outputs
+ * are pool buffers of their own and start at call v_lo, so word and byte 0 are aligned.  Nothing at or beyond n_calls is written. */
+AVK_DEV u32 dp_call_packed(u32 x) { return (x & 3u) | ((x >> 8) & 3u) << 2 | ((x >> 24) & 7u) << 4; } /* as dp_unpack's var_packed */
+AVK_DEV void dp_unpack_calls(const DpOut &o, u64 n_calls, u64 q) {
+    const u64 j = 4 * q;
+    if (j >= n_calls) return;
+    if (j + 4 <= n_calls) {
+        const avk_u4 x = *(const avk_u4 *)(o.var_out + j);
+        if (o.var_expected) *(u32 *)(o.var_expected + j) = (x.x & 0xFFu) | (x.y & 0xFFu) << 8 | (x.z & 0xFFu) << 16 | (x.w & 0xFFu) << 24;
+        if (o.var_observed) *(u32 *)(o.var_observed + j) = ((x.x >> 8) & 0xFFu) | ((x.y >> 8) & 0xFFu) << 8 | ((x.z >> 8) & 0xFFu) << 16 | ((x.w >> 8) & 0xFFu) << 24;
+        if (o.var_class) *(u32 *)(o.var_class + j) = ((x.x >> 16) & 0xFFu) | ((x.y >> 16) & 0xFFu) << 8 | ((x.z >> 16) & 0xFFu) << 16 | ((x.w >> 16) & 0xFFu) << 24;
+        if (o.var_zyg) *(u32 *)(o.var_zyg + j) = (x.x >> 24) | (x.y >> 24) << 8 | (x.z >> 24) << 16 | (x.w >> 24) << 24;
+        if (o.var_packed) *(u32 *)(o.var_packed + j) = dp_call_packed(x.x) | dp_call_packed(x.y) << 8 | dp_call_packed(x.z) << 16 | dp_call_packed(x.w) << 24;
+        return;
+    }
+    for (u64 hv = j; hv < n_calls; ++hv) {
+        const u32 x = o.var_out[hv];
+        if (o.var_expected) o.var_expected[hv] = (u8)(x & 0xFF);
+        if (o.var_observed) o.var_observed[hv] = (u8)((x >> 8) & 0xFF);
+        if (o.var_class) o.var_class[hv] = (u8)((x >> 16) & 0xFF);
+        if (o.var_zyg) o.var_zyg[hv] = (u8)(x >> 24);
+        if (o.var_packed) o.var_packed[hv] = (u8)dp_call_packed(x);
     }
 }
 

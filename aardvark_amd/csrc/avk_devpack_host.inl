@@ -360,14 +360,23 @@ __global__ void avk_dp_patch_ed_kernel(dpk::DpVarInfo *vinfo, const uint32_t *id
     }
 }
 
+/* A workgroup takes AVK_UNPACK_TILES tiles of 256 consecutive regions, lane t region t of every tile, and reserves the places of all their spilled groups with ONE
+ * atomic.  Every workgroup of a genome has a region that spills, so with a tile per workgroup 13,935 returning atomics met on one word, took most of the kernel's
+ * 187 us and kept it at that when the per-call outputs had left it (profiles/unpack_records_ab.txt); where the groups of a region lie in the list is the atomics'
+ * order either way, the region's word names the place. */
+enum { AVK_UNPACK_TILES = 8 };
 __global__ void __launch_bounds__(256) avk_dp_unpack_kernel(dpk::DpOut o, uint8_t *pair_exact) {
-    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    uint32_t word = 0, at = 0;
-    const uint32_t need = dpk::dp_unpack_bp_need(o, r, word);
-    if (o.bp_packed) { /* places in the spill list for the whole workgroup with one atomic: an exclusive scan of the lanes' needs */
+    const uint64_t r0 = (uint64_t)blockIdx.x * (256u * AVK_UNPACK_TILES) + threadIdx.x;
+    uint32_t word[AVK_UNPACK_TILES], need[AVK_UNPACK_TILES], mine = 0, at = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < AVK_UNPACK_TILES; ++k) {
+        need[k] = dpk::dp_unpack_bp_need(o, r0 + 256u * k, word[k]);
+        mine += need[k];
+    }
+    if (o.bp_packed) { /* an exclusive scan of the lanes' needs: a lane's regions lie one behind the other from `at` */
         __shared__ uint32_t wave_sum[4], base;
         const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-        uint32_t incl = need;
+        uint32_t incl = mine;
         for (uint32_t d = 1; d < 64; d <<= 1) {
             const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64);
             if (lane >= d) incl += y;
@@ -381,10 +390,20 @@ __global__ void __launch_bounds__(256) avk_dp_unpack_kernel(dpk::DpOut o, uint8_
         __syncthreads();
         uint32_t before = 0;
         for (uint32_t k = 0; k < wv; ++k) before += wave_sum[k];
-        at = base + before + incl - need;
+        at = base + before + incl - mine;
     }
-    dpk::dp_unpack(o, r, need, word, at);
-    if (pair_exact && r < o.n_regions) pair_exact[r] = (o.region_out[4 * r] == 0 && o.region_out[4 * r + 1] != 0) ? 1 : 0; /* all_opt_haps[0].is_exact_match() */
+#pragma unroll
+    for (uint32_t k = 0; k < AVK_UNPACK_TILES; ++k) {
+        const uint64_t r = r0 + 256u * k;
+        dpk::dp_unpack(o, r, need[k], word[k], at);
+        at += need[k];
+        if (pair_exact && r < o.n_regions) pair_exact[r] = (o.region_out[4 * r] == 0 && o.region_out[4 * r + 1] != 0) ? 1 : 0; /* all_opt_haps[0].is_exact_match() */
+    }
+}
+
+/* the per-call outputs of a dense batch read from its packed source: four consecutive calls per lane (dp_unpack_calls) */
+__global__ void __launch_bounds__(256) avk_dp_unpack_calls_kernel(dpk::DpOut o, uint64_t n_calls) {
+    dpk::dp_unpack_calls(o, n_calls, (uint64_t)blockIdx.x * 256u + threadIdx.x);
 }
 
 /* ---------------------------------------------------------------------------------- host threads */
@@ -1091,8 +1110,18 @@ static int download_device_packed(avk_ctx *ctx, const CallSpec &spec, avk_dev_ba
         rc = copy_in(ctx, pre, false);
         if (rc) return done(rc);
     }
+    /* A dense batch read from its packed source: word j of var_out is call v_lo + j (dp_unpack_calls), so the per-call outputs are made four calls per lane and the
+     * region kernel keeps the per-region words only.  The two launches share no output.  Every other batch — wide and compact sources, a slice that is not dense,
+     * DP_NOTE_OUTSIDE, the pair form — takes the region kernel alone, as before. */
+    const bool by_element = want_var && db->var_dense && db->d_pk_voff && db->last_mode == 0 && db->n_variants_dev == nvr;
+    dpk::DpOut o_regions = o;
+    if (by_element) o_regions.var_expected = o_regions.var_observed = o_regions.var_class = o_regions.var_zyg = o_regions.var_packed = nullptr;
+    if (e == hipSuccess && n && by_element) {
+        hipLaunchKernelGGL(avk_dp_unpack_calls_kernel, dim3((unsigned)((nvr + 1023) / 1024)), dim3(256), 0, s, o, nvr);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess && n) {
-        hipLaunchKernelGGL(avk_dp_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, o, d_exact);
+        hipLaunchKernelGGL(avk_dp_unpack_kernel, dim3((unsigned)((n + 256 * AVK_UNPACK_TILES - 1) / (256 * AVK_UNPACK_TILES))), dim3(256), 0, s, o_regions, d_exact);
         e = hipGetLastError();
     }
     if (e != hipSuccess) return done(fail(ctx, AVK_E_HIP, "result unpacking failed: %s", hipGetErrorString(e)));
