@@ -333,6 +333,28 @@ def declare_score(lib):
     lib.avk_score_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkScoreSpec), f32p, _p(AvkRegionLabels), C.c_uint32, u64p]
 
 
+N_KINDS, KIND_FIELDS = 9, 14
+# avk_kind_name for every kind (aardvark_amd/csrc/avk_callkind.h has the rule): kind = 3 * gt + sub
+KIND_NAMES = ["%s_%s" % (gt, sub) for gt in ("het", "hom", "nogt") for sub in ("ts", "tv", "other")]
+
+
+def declare_kind(lib):
+    """avk_kind_n, avk_kind_name, avk_kind_block, avk_kind_tallies, avk_compare_packed_kind, avk_kind_tallies_host (include/aardvark_amd.h)"""
+    vp, u64p = C.c_void_p, _p(C.c_uint64)
+    lib.avk_kind_n.restype = C.c_uint32
+    lib.avk_kind_n.argtypes = []
+    lib.avk_kind_name.restype = C.c_int
+    lib.avk_kind_name.argtypes = [C.c_uint32, C.c_char_p, C.c_size_t]
+    lib.avk_kind_block.restype = C.c_uint32
+    lib.avk_kind_block.argtypes = [vp]
+    lib.avk_kind_tallies.restype = C.c_int
+    lib.avk_kind_tallies.argtypes = [vp, vp, vp, u64p]
+    lib.avk_compare_packed_kind.restype = C.c_int
+    lib.avk_compare_packed_kind.argtypes = [vp, _p(AvkPackedBatch), _p(AvkPackedEscapes), vp, _p(AvkCompareConfig), _p(AvkResultBatch), u64p]
+    lib.avk_kind_tallies_host.restype = C.c_int
+    lib.avk_kind_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkRegionLabels), C.c_uint32, u64p]
+
+
 CONTEXT_PAD_MAX, CONTEXT_GC_EDGES_MAX, CONTEXT_HP_EDGES_MAX = 1024, 17, 16
 
 

@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
-                   PackedBatch, RegionBatch, ResultBatch, BootSpec, ContextSpec, SizeSpec, SIZE_FIELDS, ScoreSpec, SCORE_FIELDS, N_GROUPS, declare_boot, declare_size, declare_score, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
+                   PackedBatch, RegionBatch, ResultBatch, BootSpec, ContextSpec, SizeSpec, SIZE_FIELDS, ScoreSpec, SCORE_FIELDS, N_KINDS, KIND_FIELDS, N_GROUPS, declare_boot, declare_size, declare_score, declare_kind, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
                    region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -96,6 +96,8 @@ def load_library():
         declare_size(lib)
     if hasattr(lib, "avk_score_tallies"):  # the curve by query score (avk_score.inl); (AVK_LIB may name an older in-tree build: A/B runs)
         declare_score(lib)
+    if hasattr(lib, "avk_kind_tallies"):  # per-call tallies by call kind (avk_callkind.inl); (AVK_LIB may name an older in-tree build: A/B runs)
+        declare_kind(lib)
     if hasattr(lib, "avk_debug_ref_packed"):  # (AVK_LIB may name an older in-tree build: A/B runs)
         declare_debug_ref_packed(lib)
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
@@ -311,7 +313,7 @@ class Context:
         return PackedBatch(escapes=esc, **{f: pin(getattr(pbatch, f)) for f in PackedBatch.FIELDS})
 
     def solve_packed(self, pbatch, config=None, res=None, labels=None, label_tallies=None, strata=None, boot=None, boot_tallies=None, size=None, size_tallies=None, score=None, scores=None,
-                     score_tallies=None):
+                     score_tallies=None, kinds=False, kind_tallies=None):
         """avk_compare_packed: solve_compare_region for every region of a batch in the packed form -> ResultBatch (indexed like the packed arrays).
         labels=(n_labels, label_off, label_idx): avk_compare_packed_labels — the per-label sums come back as res.label_tallies, a [n_labels, TALLY_LEN] uint64
         array (label_tallies: an array of that shape the sums are added to instead).
@@ -322,10 +324,22 @@ class Context:
         array (scopes as above; size_tallies: an array of that shape the sums are added to instead); it returns no label sums: labels, label_tallies and boot raise ValueError.
         score=a ScoreSpec, scores=a float32 array of n_variants (indexed like the packed call arrays; query entries are read, NaN: missing): avk_compare_packed_score —
         the curve by query score comes back as res.score_tallies, a [1 + n_labels, n_points, N_GROUPS, 14] uint64 array (score_tallies: an array the sums are added
-        to instead); like size it excludes labels, label_tallies, boot and size"""
+        to instead); like size it excludes labels, label_tallies, boot and size.
+        kinds=True: avk_compare_packed_kind — the per-call tallies by call kind (het / hom x Ti / Tv, KIND_NAMES) come back as res.kind_tallies, a
+        [1 + n_labels, 9, N_GROUPS, 14] uint64 array (kind_tallies: an array of that shape the sums are added to instead); it excludes labels, label_tallies, boot,
+        size and score"""
         config = config or CompareConfig(enable_sequences=False)
         res = res if res is not None else ResultBatch(pbatch, sequences=False, group_metrics=False)
         pb, cfg, ro, esc = pbatch.c_struct(), config.c_struct(), res.c_struct(), pbatch.c_escapes()
+        if kinds:
+            if labels is not None or label_tallies is not None or (boot is not None and boot.replicates) or size is not None or score is not None:
+                raise ValueError("kinds takes strata, not label lists, returns no label sums (label_tallies) and excludes boot, size and score")
+            n_labels = 0 if strata is None else strata.n_labels
+            blocks = np.zeros((1 + n_labels, N_KINDS, N_GROUPS, KIND_FIELDS), np.uint64) if kind_tallies is None else kind_tallies
+            self._check(self.lib.avk_compare_packed_kind(self.handle, C.byref(pb), None if esc is None else C.byref(esc), None if strata is None else strata.handle, C.byref(cfg),
+                                                         C.byref(ro), blocks.ctypes.data_as(u64p)))
+            res.kind_tallies = blocks
+            return res
         if score is not None:
             if labels is not None or label_tallies is not None or (boot is not None and boot.replicates) or size is not None:
                 raise ValueError("score takes strata, not label lists, returns no label sums (label_tallies) and excludes boot and size")
@@ -573,6 +587,18 @@ class Context:
                                                None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
         return out
 
+    def kind_block(self):
+        """avk_kind_block: how many regions a workgroup of the call-kind kernel takes at a time (one lane each)"""
+        return int(self.lib.avk_kind_block(self.handle))
+
+    def kind_tallies(self, rb, strata=None, out=None):
+        """avk_kind_tallies: the per-call tallies by call kind of a solved resident batch (no option is needed); returns / adds to a
+        [1 + n_labels, 9, N_GROUPS, 14] uint64 array — scope 0: every region; scope 1 + l: label l of `strata`; the kinds are KIND_NAMES"""
+        n_labels = 0 if strata is None else strata.n_labels
+        out = np.zeros((1 + n_labels, N_KINDS, N_GROUPS, KIND_FIELDS), np.uint64) if out is None else out
+        self._check(self.lib.avk_kind_tallies(self.handle, rb.handle, None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
+        return out
+
     def synchronize(self):
         self._check(self.lib.avk_synchronize(self.handle))
 
@@ -721,4 +747,20 @@ def size_tallies_host(batch, res, spec, labels=None, threads=1, out=None):
     rc = lib.avk_size_tallies_host(C.byref(cb), C.byref(ro), C.byref(ss), None if lab is None else C.byref(lab), int(threads), out.ctypes.data_as(C.POINTER(C.c_uint64)))
     if rc:
         raise AardvarkAmdError("avk_size_tallies_host: %d: %s" % (rc, lib.avk_last_error(None).decode()))
+    return out
+
+
+def kind_tallies_host(batch, res, labels=None, threads=1, out=None):
+    """avk_kind_tallies_host: Context.kind_tallies' sums on the host from a wide RegionBatch and its ResultBatch (no GPU involved);
+    labels=(n_labels, label_off, label_idx) or None -> [1 + n_labels, 9, N_GROUPS, 14] uint64 (added to `out`)"""
+    lib = load_library()
+    n_labels = 0 if labels is None else int(labels[0])
+    out = np.zeros((1 + n_labels, N_KINDS, N_GROUPS, KIND_FIELDS), np.uint64) if out is None else out
+    cb, ro = batch.c_struct(), res.c_struct()
+    lab = None
+    if labels is not None:
+        lab, _keep = region_labels(*labels)
+    rc = lib.avk_kind_tallies_host(C.byref(cb), C.byref(ro), None if lab is None else C.byref(lab), int(threads), out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc:
+        raise AardvarkAmdError("avk_kind_tallies_host: %d: %s" % (rc, lib.avk_last_error(None).decode()))
     return out

@@ -3040,9 +3040,15 @@ struct ScoreStage {
     uint64_t *sums; /* the caller's [(1 + n_labels) * n_points * AVK_N_GROUPS * AVK_SCORE_FIELDS]: gains the sums */
 };
 static int score_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_score_spec *sp, const float *scores, const avk_strata *st, uint64_t *out);
+/* ... and the tallies by call kind (avk_compare_packed_kind), likewise */
+struct KindStage {
+    const avk_strata *st;
+    uint64_t *sums; /* the caller's [(1 + n_labels) * AVK_N_KINDS * AVK_N_GROUPS * AVK_SIZE_FIELDS]: gains the sums */
+};
+static int kind_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *st, uint64_t *out);
 static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_result_batch *out, uint64_t n, const char *timed_as,
                             const std::function<int(const CallSpec &, avk_dev_batch **)> &upload, const LabelStage *ls = nullptr, const BootStage *boot = nullptr,
-                            const SizeStage *size = nullptr, const ScoreStage *score = nullptr) {
+                            const SizeStage *size = nullptr, const ScoreStage *score = nullptr, const KindStage *kind = nullptr) {
     ctx->last_one_shot = 0;
     CallSpec spec = call_spec(ctx, out, ls != nullptr || boot != nullptr); /* (the groups are what the label kernel reads, whether the caller asked for them or not) */
     const uint32_t n_labels = !ls ? 0 : ls->st ? ls->st->n_labels : ls->lab->n_labels;
@@ -3088,6 +3094,7 @@ static int compare_one_call(avk_ctx *ctx, const avk_compare_config *cfg, avk_res
     if (!rc && boot) rc = boot_sums_run(ctx, db, boot->spec, job.st ? job.st->n_labels : 0, (const uint32_t *)L.d_mask, boot->sums);
     if (!rc && size) rc = size_resident_run(ctx, db, size->spec, size->st, size->sums);
     if (!rc && score) rc = score_resident_run(ctx, db, score->spec, score->scores, score->st, score->sums);
+    if (!rc && kind) rc = kind_resident_run(ctx, db, kind->st, kind->sums);
     strata_lists_release(ctx, L);
     pool_release(ctx, d_out);
     if (db) {
@@ -3636,6 +3643,168 @@ int avk_score_tallies_host(const avk_region_batch *b, const avk_result_batch *re
     /* the sums themselves: plain C++ in a header of its own, which the sanitizer program of the tests includes as well */
     if (avk_score_host_sum(b, res, sp, scores, lab && n_labels ? lab : nullptr, threads, avk::host_edit_distance, out))
         return fail(nullptr, AVK_E_ARG, "score curve: a region's calls lie outside the batch, or a label is not one of the labels");
+    return 0;
+}
+
+/* ---- per-call tallies by call kind: het / hom x Ti / Tv (avk_callkind.h, avk_callkind.inl) ---------------------------------------------------------------- */
+} /* extern "C" */
+#include "avk_callkind.inl"
+extern "C" {
+static_assert(AVK_ZYG_UNPHASED_HET == 2 && AVK_ZYG_PHASED_HET01 == 3 && AVK_ZYG_PHASED_HET10 == 4 && AVK_ZYG_HOM_ALT == 5, "avk_kind_gt_of reads these numbers");
+static_assert(AVK_N_KINDS == AVK_KIND_N_GT * AVK_KIND_N_SUB && AVK_N_KINDS <= 16, "a kind is a genotype and a substitution class, and a key holds it in four bits");
+static_assert(AVK_CK_SCOPES >= 1 && AVK_CK_SCOPES <= AVK_SZ_SCOPES_MAX && AVK_CK_THREADS % 64 == 0 && AVK_N_VARIANT_TYPES < 15,
+              "a workgroup of avk_kind_tally_kernel holds a scope's block, whole waves, and a key its type");
+uint32_t avk_kind_n(void) { return AVK_N_KINDS; }
+uint32_t avk_kind_block(const avk_ctx *ctx) { return ctx ? AVK_CK_THREADS : 0; }
+int avk_kind_name(uint32_t k, char *buf, size_t cap) {
+    const char *name = avk_kind_name_of(k);
+    if (!name || !buf || !cap) return fail(nullptr, AVK_E_ARG, "call kinds: invalid kind or buffer");
+    const int len = snprintf(buf, cap, "%s", name);
+    return len > 0 && (size_t)len < cap ? 0 : fail(nullptr, AVK_E_ARG, "call kinds: the name buffer is too small");
+}
+/* the kernel over blocks of scopes, on stream s behind whatever wrote the batch's results: d_out[(1 + n_labels) * AVK_CK_BLOCK_WORDS] gains the sums */
+static int kind_launch(avk_ctx *ctx, avk_dev_batch *db, uint32_t n_labels, const uint32_t *d_mask, uint64_t *d_out, hipStream_t s) {
+    const uint64_t n = db->n_regions;
+    if (!n) return 0;
+    avk::lb::LbView v;
+    memset(&v, 0, sizeof(v));
+    v.in = db->dp_args.in, v.vinfo = db->dp_args.vinfo, v.region_out = db->d_region_out, v.var_out = db->d_var_out, v.v_off = db->d_voff;
+    const uint32_t n_scopes = 1u + (d_mask ? n_labels : 0u);
+    /* four workgroups a CU (their LDS), and no more workgroups than tiles: each flushes its block once */
+    uint64_t blocks = (n + AVK_CK_THREADS - 1) / AVK_CK_THREADS;
+    if (blocks > (uint64_t)ctx->n_cus * 4u) blocks = (uint64_t)ctx->n_cus * 4u;
+    for (uint32_t lo = 0; lo < n_scopes; lo += AVK_CK_SCOPES) {
+        const uint32_t hi = n_scopes - lo > AVK_CK_SCOPES ? lo + AVK_CK_SCOPES : n_scopes;
+        hipLaunchKernelGGL(avk_kind_tally_kernel, dim3((unsigned)blocks), dim3(AVK_CK_THREADS), (size_t)(hi - lo) * AVK_CK_BLOCK_WORDS * 8u, s, v, d_mask, (uint32_t)n, lo, hi,
+                           (unsigned long long *)d_out);
+        AVK_HIP(ctx, hipGetLastError());
+    }
+    return 0;
+}
+/* sums cleared, kernels, copy back, wait, added to the caller's: on the context's stream */
+static int kind_sums_run(avk_ctx *ctx, avk_dev_batch *db, uint32_t n_labels, const uint32_t *d_mask, uint64_t *out) {
+    if (!d_mask) n_labels = 0;
+    const size_t words = ((size_t)n_labels + 1) * AVK_CK_BLOCK_WORDS;
+    std::vector<uint64_t> host(words, 0);
+    void *d_out = nullptr;
+    int rc = pool_alloc(ctx, &d_out, words * 8);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
+    if (!rc && e == hipSuccess) rc = kind_launch(ctx, db, n_labels, d_mask, (uint64_t *)d_out, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    pool_release(ctx, d_out);
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(ctx, AVK_E_HIP, "call-kind tallies failed: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    for (size_t k = 0; k < words; ++k) out[k] += host[k];
+    return 0;
+}
+/* a solved resident batch: the scopes' membership (the strata pass's masks, nothing else of the lists), then the sums */
+static int kind_resident_run(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *st, uint64_t *out) {
+    const uint64_t n = db->n_regions;
+    StrataLists L;
+    int rc = 0;
+    if (st && st->n_labels && n) {
+        rc = strata_lists_alloc(ctx, st, n, L);
+        if (!rc) {
+            const hipError_t e = strata_mask_launch(st, db->dp_args.in, n, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums, ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata masks failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (!rc) rc = kind_sums_run(ctx, db, L.d_mask ? st->n_labels : 0, (const uint32_t *)L.d_mask, out);
+    else (void)hipStreamSynchronize(ctx->stream);
+    strata_lists_release(ctx, L);
+    return rc;
+}
+
+int avk_kind_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *st, uint64_t *out) {
+    if (!ctx || !db) return AVK_E_ARG;
+    if (!out) return fail(ctx, AVK_E_ARG, "kind_tallies missing");
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    if (!db->dev_packed) return fail(ctx, AVK_E_STATE, "call-kind tallies on the device need a device-packed batch: the option device_pack was 0 at its upload (host route: avk_kind_tallies_host)");
+    if (!db->has_run || db->last_mode != 0) return fail(ctx, AVK_E_STATE, "call-kind tallies need a batch that avk_compare_resident has solved");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    return kind_resident_run(ctx, db, st, out);
+}
+
+int avk_compare_packed_kind(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg,
+                            avk_result_batch *out, uint64_t *kind_out) {
+    if (!batch) return AVK_E_ARG;
+    if (st && st->n_labels == 0) st = nullptr;
+    if (!kind_out) return fail(ctx, AVK_E_ARG, "kind_tallies missing");
+    if (!ctx || !cfg || !out || !(out->status || out->region_packed)) return AVK_E_ARG;
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG;
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->device_pack) return fail(ctx, AVK_E_STATE, "call-kind tallies on the device need the option device_pack (host route: avk_kind_tallies_host)");
+    if (!esc_present(esc)) esc = nullptr;
+    const KindStage kind{st, kind_out};
+    return compare_one_call(ctx, cfg, out, batch->n_regions, nullptr, [&](const CallSpec &spec, avk_dev_batch **db) { return upload_packed(ctx, spec, batch, esc, db); }, nullptr, nullptr,
+                            nullptr, nullptr, &kind);
+}
+
+int avk_kind_tallies_host(const avk_region_batch *b, const avk_result_batch *res, const avk_region_labels *lab, uint32_t threads, uint64_t *out) {
+    if (!b || !res) return fail(nullptr, AVK_E_ARG, "call kinds: batch or results missing");
+    const uint32_t n_labels = lab ? lab->n_labels : 0;
+    if (!out) return fail(nullptr, AVK_E_ARG, "kind_tallies missing");
+    if (lab && n_labels) {
+        const int rl = labels_check(nullptr, b->n_regions, lab, out);
+        if (rl) return rl;
+    }
+    if (!(res->status || res->region_packed)) return fail(nullptr, AVK_E_ARG, "call kinds: the results have neither status nor region_packed");
+    const bool wide_calls = res->var_expected && res->var_observed;
+    if (!wide_calls && !res->var_packed) return fail(nullptr, AVK_E_ARG, "call kinds: the results have no per-call outputs");
+    const uint64_t n = b->n_regions;
+    const size_t block = AVK_CK_BLOCK_WORDS, words = ((size_t)n_labels + 1) * block;
+    const uint32_t T = threads < 1 ? 1u : (threads > 64u ? 64u : threads); /* every thread sums into a block of its own */
+    std::vector<std::vector<uint64_t>> part(T);
+    std::vector<int> bad(T, 0);
+    auto work = [&](uint32_t t) {
+        std::vector<uint64_t> &acc = part[t];
+        acc.assign(words, 0);
+        for (uint64_t r = n * t / T; r < n * (t + 1) / T; ++r) {
+            const uint32_t status = res->status ? (uint32_t)res->status[r] : avk_rp_status(res->region_packed[r]);
+            if (status != 0) continue;
+            for (int side = 0; side < 2; ++side) {
+                const uint64_t off = side == 0 ? b->t_off[r] : b->q_off[r];
+                const uint32_t cnt = side == 0 ? b->t_cnt[r] : b->q_cnt[r];
+                if (off > b->n_variants || cnt > b->n_variants - off) {
+                    bad[t] = 1;
+                    return;
+                }
+                for (uint32_t i = 0; i < cnt; ++i) {
+                    const uint64_t v = off + i;
+                    const uint32_t vt = b->var_type[v], l0 = b->a0_len[v], l1 = b->a1_len[v];
+                    const uint64_t w = avk::host_edit_distance(b->allele_bytes + b->a0_off[v], l0, b->allele_bytes + b->a1_off[v], l1); /* Variant::alt_ed */
+                    const uint32_t ea = wide_calls ? res->var_expected[v] : avk_vp_expected(res->var_packed[v]), oa = wide_calls ? res->var_observed[v] : avk_vp_observed(res->var_packed[v]);
+                    /* one iteration of lb_side (avk_labels.inl): the query entries are stored toggled */
+                    const uint32_t exp = side == 0 ? ea : oa, obs = side == 0 ? oa : ea;
+                    const uint32_t val[AVK_SIZE_VALUES] = {exp == obs ? 1u : 0u, exp == obs ? 0u : 1u, (exp != obs && obs > 0) ? 1u : 0u, obs, exp - obs, (uint32_t)((uint64_t)obs * w),
+                                                           (uint32_t)((uint64_t)(uint32_t)(exp - obs) * w)};
+                    const bool bytes = l0 == 1u && l1 == 1u && b->a0_off[v] < b->allele_bytes_len && b->a1_off[v] < b->allele_bytes_len;
+                    const uint32_t sub = bytes ? avk_kind_sub_of(1u, 1u, b->allele_bytes[b->a0_off[v]], b->allele_bytes[b->a1_off[v]]) : (uint32_t)AVK_KIND_SUB_OTHER;
+                    const uint32_t kind = avk_kind_of(avk_kind_gt_of(b->var_zyg[v]), sub);
+                    auto add = [&](uint32_t scope) {
+                        for (uint32_t g : {0u, 1u + vt}) {
+                            if (g >= AVK_N_GROUPS) continue;
+                            uint64_t *dst = acc.data() + (size_t)scope * block + ((size_t)kind * AVK_N_GROUPS + g) * AVK_SIZE_FIELDS;
+                            for (uint32_t k = 0; k < AVK_SIZE_VALUES; ++k) dst[avk_size_field_of(k, side)] += val[k];
+                        }
+                    };
+                    add(0);
+                    if (n_labels)
+                        for (uint64_t q = lab->label_off[r]; q < lab->label_off[r + 1]; ++q) add(1u + lab->label_idx[q]);
+                }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < T; ++t) pool.emplace_back(work, t);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    for (uint32_t t = 0; t < T; ++t)
+        if (bad[t]) return fail(nullptr, AVK_E_ARG, "call kinds: a region's calls lie outside the batch");
+    for (uint32_t t = 0; t < T; ++t)
+        for (size_t k = 0; k < words; ++k) out[k] += part[t][k];
     return 0;
 }
 

@@ -48,7 +48,9 @@ void usage() {
             "  [--size-edges 1,6,16,50]  (1 to 15 ascending sizes, the first at least 1; default bins len_0 len_1_5 len_6_15 len_16_49 len_ge50)\n"
             "  [--roc QUAL|GQ]  (writes summary_roc.tsv: summary.tsv's GT, HAP and WEIGHTED_HAP rows once per threshold on the query calls' QUAL or FORMAT/GQ, the point's name\n"
             "   in the filter column, summed on the GPU from the ONE comparison of the job: an approximation of a filtered re-run per threshold, which could draw other regions)\n"
-            "  [--roc-thresholds 5,10,15,20,25,30,35,40,50,60]  (1 to 31 finite, strictly ascending numbers; points score_all, score_ge_5, ..)\n");
+            "  [--roc-thresholds 5,10,15,20,25,30,35,40,50,60]  (1 to 31 finite, strictly ascending numbers; points score_all, score_ge_5, ..)\n"
+            "  [--kind-strata]  (writes summary_kind.tsv: summary.tsv's GT, HAP and WEIGHTED_HAP rows per call kind — het / hom / nogt by the call's genotype x ts / tv / other by its\n"
+            "   two allele bases, the kind's name in the filter column — and kind_ratios.tsv: Ti/Tv and het/hom of the GT counts per region label, variant type and set; summed on the GPU)\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -106,6 +108,8 @@ int main(int argc, char **argv) {
     std::vector<uint32_t> size_edges = {1, 6, 16, 50};
     /* --roc: the precision-recall curve by the query calls' QUAL or GQ (avk_score_spec) for summary_roc.tsv */
     bool roc = false, roc_override = false;
+    /* --kind-strata: per-call tallies by call kind (het / hom x Ti / Tv) for summary_kind.tsv and kind_ratios.tsv */
+    bool kind = false;
     std::string roc_field, roc_list = "5,10,15,20,25,30,35,40,50,60";
     auto number_list = [](const std::string &opt, const std::string &list) {
         std::vector<uint32_t> out;
@@ -204,6 +208,7 @@ int main(int argc, char **argv) {
         else if (a == "--size-strata") size = true;
         else if (a == "--size-edges") size_edges = number_list(a, val()), size_override = true;
         else if (a == "--roc") roc_field = val(), roc = true;
+        else if (a == "--kind-strata") kind = true;
         else if (a == "--roc-thresholds") roc_list = val(), roc_override = true;
         else if (a == "-h" || a == "--help") {
             usage();
@@ -284,6 +289,13 @@ int main(int argc, char **argv) {
         if (!debug_dir.empty()) die(64, "--roc cannot be combined with --output-debug (the debug run writes per-region tables, not a curve)", "");
         if (!strat_tsv.empty() && strat_lists == "host" && want_packed)
             die(64, "--roc on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
+    }
+    /* The call kinds are summed like the size bins: by kernel on the packed feed (avk_compare_packed_kind, or avk_kind_tallies on the resident batch when other sums are
+     * wanted of the same batch), or on the host from the wide feed's results (avk_kind_tallies_host).  What neither route carries is refused here, by name. */
+    if (kind) {
+        if (!debug_dir.empty()) die(64, "--kind-strata cannot be combined with --output-debug (the debug run writes per-region tables, not call kinds)", "");
+        if (!strat_tsv.empty() && strat_lists == "host" && want_packed)
+            die(64, "--kind-strata on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
     }
     if (!devices.empty()) device = devices[0];
     if (mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create output folder", out_dir.c_str());
@@ -537,6 +549,34 @@ int main(int argc, char **argv) {
         if (db) avk_batch_free(c, db);
         return rc;
     };
+    /* --kind-strata on the packed feed, the same way: alone one call (avk_compare_packed_kind); with label sums, replicates, size bins or the curve of the same batch
+     * on the resident batch */
+    auto compare_part_kind = [&](avk_ctx *c, uint64_t at_abs, uint64_t n, const avk_compare_config &cfg, const avk_result_batch &out, const avk_strata *sets, uint64_t *sums,
+                                 uint64_t *reps, uint64_t *blocks, uint64_t *curve, uint64_t *kinds) -> int {
+        avk_packed_batch part;
+        avk_packed_escapes part_esc;
+        uint64_t v_first = 0;
+        if (avf_packed_slice_esc(feed, &packed_all, &esc_all, at_abs, n, &part, &part_esc, &v_first)) return AVK_E_ARG;
+        avk_result_batch shifted = out_for(out, v_first);
+        if (!sets && !boot && !size && !roc) return avk_compare_packed_kind(c, &part, &part_esc, nullptr, &cfg, &shifted, kinds);
+        avk_dev_batch *db = nullptr;
+        int rc = avk_batch_upload_packed_esc(c, &part, &part_esc, &db);
+        if (!rc) rc = avk_compare_resident(c, db, &cfg, nullptr);
+        if (!rc) rc = avk_results_download(c, db, &shifted);
+        if (!rc && sets) rc = avk_label_tallies_strata(c, db, sets, sums);
+        if (!rc && boot) rc = avk_boot_tallies(c, db, &boot_spec, sets, reps);
+        if (!rc && size) rc = avk_size_tallies(c, db, &size_spec, sets, blocks);
+        if (!rc && roc) rc = avk_score_tallies(c, db, &roc_spec, roc_scores.data() + v_first, sets, curve);
+        if (!rc) rc = avk_kind_tallies(c, db, sets, kinds);
+        if (db) avk_batch_free(c, db);
+        return rc;
+    };
+    /* --kind-strata on the wide feed: the part's blocks from its results on the host */
+    auto kind_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *kinds) -> int {
+        avk_region_labels lab;
+        lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
+        return avk_kind_tallies_host(&b, &out, n_labels ? &lab : nullptr, 16, kinds);
+    };
     /* --roc on the wide feed: the part's curve from its results on the host (the part's call offsets are the feed's) */
     auto roc_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *curve) -> int {
         avk_region_labels lab;
@@ -610,12 +650,22 @@ int main(int argc, char **argv) {
     const bool boot_host = boot && !packed; /* the wide feed: avk_boot_tallies_host on each part's results */
     if (size && packed && n_labels && !strata_route) die(70, "--size-strata on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
     const bool size_host = size && !packed;                            /* the wide feed: avk_size_tallies_host on each part's results */
-    const bool size_resident = size && packed && (strata_route || boot || roc); /* label sums, replicates or the score curve of the same batch: the kernels run on the resident batch */
+    const bool size_resident = size && packed && (strata_route || boot || roc || kind); /* label sums, replicates or the score curve of the same batch: the kernels run on the resident batch */
     if (roc && packed && n_labels && !strata_route) die(70, "--roc on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
     const bool roc_host = roc && !packed;                                   /* the wide feed: avk_score_tallies_host on each part's results */
-    const bool roc_resident = roc && packed && (strata_route || boot || size); /* other sums of the same batch: the kernels run on the resident batch */
+    const bool roc_resident = roc && packed && (strata_route || boot || size || kind); /* other sums of the same batch: the kernels run on the resident batch */
+    if (kind && packed && n_labels && !strata_route) die(70, "--kind-strata on the packed feed needs the stratification sets on the GPU, and they could not be put there", "");
+    const bool kind_host = kind && !packed;                                         /* the wide feed: avk_kind_tallies_host on each part's results */
+    const bool kind_resident = kind && packed && (strata_route || boot || size || roc); /* other sums of the same batch: the kernels run on the resident batch */
     (void)avk_ctx_set_option(ctx, "emit_group_metrics", (n_labels && !compact_labels) || debug ? 1 : 0);
-    if (boot_host || size_resident || roc_resident) (void)avk_ctx_set_option(ctx, "emit_bp_groups", 1);
+    if (boot_host || size_resident || roc_resident || kind_resident) (void)avk_ctx_set_option(ctx, "emit_bp_groups", 1);
+    std::vector<uint64_t> kind_total(kind ? ((size_t)n_labels + 1) * AVK_N_KINDS * AVK_N_GROUPS * AVK_SIZE_FIELDS : 0, 0);
+    if (verbosity && kind)
+        fprintf(stderr, "Call kinds: %u kinds in summary_kind.tsv (GT, HAP, WEIGHTED_HAP; no BASEPAIR rows) and their Ti/Tv and het/hom in kind_ratios.tsv; the kinds are summed %s.\n",
+                (unsigned)AVK_N_KINDS,
+                kind_host       ? "on the host from each batch's results (avk_kind_tallies_host, the wide feed)"
+                : kind_resident ? "on the GPU on each resident batch behind its solve and download (avk_kind_tallies)"
+                                : "on the GPU behind each batch's solve (avk_compare_packed_kind)");
     const uint32_t roc_points = roc ? roc_spec.n_thresholds + 1 : 0;
     std::vector<uint64_t> roc_total(roc ? ((size_t)n_labels + 1) * roc_points * AVK_N_GROUPS * AVK_SCORE_FIELDS : 0, 0);
     if (verbosity && roc)
@@ -684,7 +734,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "Size bins: the hash-sharded route does not carry the blocks; --size-strata selects the route on which the contexts share the region batches.\n");
     if (verbosity && roc && n_workers > 1 && packed && !n_labels)
         fprintf(stderr, "Score curve: the hash-sharded route does not carry the blocks; --roc selects the route on which the contexts share the region batches.\n");
-    if (n_workers > 1 && packed && !n_labels && !boot && !size && !roc) {
+    if (verbosity && kind && n_workers > 1 && packed && !n_labels)
+        fprintf(stderr, "Call kinds: the hash-sharded route does not carry the blocks; --kind-strata selects the route on which the contexts share the region batches.\n");
+    if (n_workers > 1 && packed && !n_labels && !boot && !size && !roc && !kind) {
         sharded = true;
         avk_packed_batch sel;
         avk_packed_escapes sel_esc;
@@ -808,7 +860,8 @@ int main(int argc, char **argv) {
         std::vector<std::string> worker_err(n_workers);
         std::vector<std::vector<uint64_t>> w_total(n_workers, std::vector<uint64_t>(AVK_TALLY_LEN, 0)),
             w_strat(n_workers, std::vector<uint64_t>((size_t)n_labels * AVK_TALLY_LEN, 0)), w_boot(n_workers, std::vector<uint64_t>(boot_total.size(), 0)),
-            w_size(n_workers, std::vector<uint64_t>(size_total.size(), 0)), w_roc(n_workers, std::vector<uint64_t>(roc_total.size(), 0));
+            w_size(n_workers, std::vector<uint64_t>(size_total.size(), 0)), w_roc(n_workers, std::vector<uint64_t>(roc_total.size(), 0)),
+            w_kind(n_workers, std::vector<uint64_t>(kind_total.size(), 0));
         std::mutex log_mutex;
         auto worker = [&](size_t w) {
             avk_ctx *my = ctx;
@@ -831,7 +884,7 @@ int main(int argc, char **argv) {
                     return;
                 }
                 (void)avk_ctx_set_option(my, "emit_group_metrics", n_labels && !compact_labels ? 1 : 0);
-                if (boot_host || size_resident || roc_resident) (void)avk_ctx_set_option(my, "emit_bp_groups", 1);
+                if (boot_host || size_resident || roc_resident || kind_resident) (void)avk_ctx_set_option(my, "emit_bp_groups", 1);
             }
             avk_strata *my_sets = w > 0 ? nullptr : strata;
             if (w > 0 && strata_route && cx_given && strata_upload(my, &my_sets)) { /* (context labels: no host route) */
@@ -843,10 +896,11 @@ int main(int argc, char **argv) {
                 std::lock_guard<std::mutex> lock(log_mutex);
                 fprintf(stderr, "Warning: cannot upload the stratification sets to context %zu: %s; its region labels are listed on the host.\n", w, avk_last_error(my));
                 my_sets = nullptr;
-                if (boot || size || roc) { /* (the replicates', the size bins' and the curve's scopes are read from the sets on the GPU) */
+                if (boot || size || roc || kind) { /* (the replicates', the size bins', the curve's and the kinds' scopes are read from the sets on the GPU) */
                     worker_err[w] = boot   ? "--bootstrap: cannot upload the stratification sets to every context"
                                     : size ? "--size-strata: cannot upload the stratification sets to every context"
-                                           : "--roc: cannot upload the stratification sets to every context";
+                                    : roc  ? "--roc: cannot upload the stratification sets to every context"
+                                           : "--kind-strata: cannot upload the stratification sets to every context";
                     avk_ctx_destroy(my);
                     return;
                 }
@@ -875,7 +929,10 @@ int main(int argc, char **argv) {
                 int rc = 0;
                 HostGroups hg;
                 if (boot_host) host_groups(n, out, hg);
-                if (roc && packed)
+                if (kind && packed)
+                    rc = compare_part_kind(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data(), w_size[w].data(), w_roc[w].data(),
+                                           w_kind[w].data());
+                else if (roc && packed)
                     rc = compare_part_roc(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data(), w_size[w].data(), w_roc[w].data());
                 else if (size && packed) rc = compare_part_size(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data(), w_size[w].data());
                 else if (boot && packed) rc = compare_part_boot(my, first + at, n, cfg, out, strata_route ? my_sets : nullptr, w_strat[w].data(), w_boot[w].data());
@@ -914,6 +971,10 @@ int main(int argc, char **argv) {
                             worker_err[w] = std::string("score curve failed: ") + avk_last_error(nullptr);
                             break;
                         }
+                        if (!rc && kind_host && kind_part_host(b, out, label_off.data(), label_idx.data(), w_kind[w].data())) {
+                            worker_err[w] = std::string("call-kind tallies failed: ") + avk_last_error(nullptr);
+                            break;
+                        }
                     }
                 } else {
                     rc = compare_part(my, b, first + at, n, cfg, out);
@@ -927,6 +988,10 @@ int main(int argc, char **argv) {
                     }
                     if (!rc && roc_host && roc_part_host(b, out, nullptr, nullptr, w_roc[w].data())) {
                         worker_err[w] = std::string("score curve failed: ") + avk_last_error(nullptr);
+                        break;
+                    }
+                    if (!rc && kind_host && kind_part_host(b, out, nullptr, nullptr, w_kind[w].data())) {
+                        worker_err[w] = std::string("call-kind tallies failed: ") + avk_last_error(nullptr);
                         break;
                     }
                 }
@@ -958,6 +1023,7 @@ int main(int argc, char **argv) {
             for (size_t k = 0; k < boot_total.size(); ++k) boot_total[k] += w_boot[w][k]; /* the contexts' blocks, added on the host */
             for (size_t k = 0; k < size_total.size(); ++k) size_total[k] += w_size[w][k];
             for (size_t k = 0; k < roc_total.size(); ++k) roc_total[k] += w_roc[w][k];
+            for (size_t k = 0; k < kind_total.size(); ++k) kind_total[k] += w_kind[w][k];
         }
     }
     for (uint64_t at = 0; n_workers == 1 && at < count; at += batch_regions) {
@@ -1001,7 +1067,11 @@ int main(int argc, char **argv) {
         }
         HostGroups hg;
         if (boot_host) host_groups(n, out, hg);
-        if (roc && packed) { /* the curve with the results (and, on the resident batch, the labels' sums, the replicates and the size blocks) */
+        if (kind && packed) { /* the kinds with the results (and, on the resident batch, every other sum asked for) */
+            if (compare_part_kind(ctx, first + at, n, cfg, out, strata_route ? strata : nullptr, strat_total.data(), boot_total.data(), size_total.data(), roc_total.data(),
+                                  kind_total.data()))
+                die(70, "compare failed", avk_last_error(ctx));
+        } else if (roc && packed) { /* the curve with the results (and, on the resident batch, the labels' sums, the replicates and the size blocks) */
             if (compare_part_roc(ctx, first + at, n, cfg, out, strata_route ? strata : nullptr, strat_total.data(), boot_total.data(), size_total.data(), roc_total.data()))
                 die(70, "compare failed", avk_last_error(ctx));
         } else if (size && packed) { /* the size blocks with the results (and, on the resident batch, the labels' sums and the replicates) */
@@ -1046,11 +1116,13 @@ int main(int argc, char **argv) {
             if (boot_host && boot_part_host(b, out, label_off.data(), label_idx.data(), boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
             if (size_host && size_part_host(b, out, label_off.data(), label_idx.data(), size_total.data())) die(70, "size-bin tallies failed", avk_last_error(nullptr));
             if (roc_host && roc_part_host(b, out, label_off.data(), label_idx.data(), roc_total.data())) die(70, "score curve failed", avk_last_error(nullptr));
+            if (kind_host && kind_part_host(b, out, label_off.data(), label_idx.data(), kind_total.data())) die(70, "call-kind tallies failed", avk_last_error(nullptr));
         } else {
             if (compare_part(ctx, b, first + at, n, cfg, out)) die(70, "compare failed", avk_last_error(ctx));
             if (boot_host && boot_part_host(b, out, nullptr, nullptr, boot_total.data())) die(70, "bootstrap tallies failed", avk_last_error(nullptr));
             if (size_host && size_part_host(b, out, nullptr, nullptr, size_total.data())) die(70, "size-bin tallies failed", avk_last_error(nullptr));
             if (roc_host && roc_part_host(b, out, nullptr, nullptr, roc_total.data())) die(70, "score curve failed", avk_last_error(nullptr));
+            if (kind_host && kind_part_host(b, out, nullptr, nullptr, kind_total.data())) die(70, "call-kind tallies failed", avk_last_error(nullptr));
         }
         for (size_t k = 0; k < (size_t)AVK_TALLY_LEN; ++k) total[k] += tally[k];
         if (debug && (avf_region_summary_rows(region_table, genome, all, first + at, n, out.status, gm.data()) ||
@@ -1120,6 +1192,21 @@ int main(int argc, char **argv) {
         for (const std::string &n : bin_names) bin_ptrs.push_back(n.c_str());
         if (avf_write_summary_size((out_dir + "/summary_size.tsv").c_str(), label.c_str(), size_bins, bin_ptrs.data(), n_labels, sz_ptrs.data(), size_total.data(), mask))
             die(74, "Error while saving summary_size.tsv", avf_last_error());
+    }
+    if (kind) { /* summary_kind.tsv: summary.tsv's GT / HAP / WEIGHTED_HAP rows per scope and call kind; kind_ratios.tsv: their Ti/Tv and het/hom */
+        std::vector<std::string> kd_names;
+        for (uint32_t l = 0; l < n_bed_labels; ++l) kd_names.push_back(avf_strat_label(strat, l));
+        for (uint32_t j = 0; j < n_ctx_labels; ++j) {
+            char name[64];
+            if (avk_context_label_name(&cx_spec, j, name, sizeof(name))) die(70, "context label name", avk_last_error(nullptr));
+            kd_names.push_back(name);
+        }
+        std::vector<const char *> kd_ptrs;
+        for (const std::string &n : kd_names) kd_ptrs.push_back(n.c_str());
+        if (avf_write_summary_kind((out_dir + "/summary_kind.tsv").c_str(), label.c_str(), n_labels, kd_ptrs.data(), kind_total.data(), mask))
+            die(74, "Error while saving summary_kind.tsv", avf_last_error());
+        if (avf_write_kind_ratios((out_dir + "/kind_ratios.tsv").c_str(), label.c_str(), n_labels, kd_ptrs.data(), kind_total.data()))
+            die(74, "Error while saving kind_ratios.tsv", avf_last_error());
     }
     if (roc) { /* summary_roc.tsv: summary.tsv's GT / HAP / WEIGHTED_HAP rows per scope and point of the curve */
         std::vector<std::string> sc_names, point_names;

@@ -2043,6 +2043,87 @@ int avf_write_summary_roc(const char *path, const char *compare_label, uint32_t 
     return avf_write_summary_size(path, compare_label, n_points, point_names, n_labels, label_names, score_blocks, metrics_mask);
 }
 
+/* summary_kind.tsv: the same file keyed by the call KINDS (avk_kind_tallies' layout, [1 + n_labels][AVK_N_KINDS][AVK_N_GROUPS][14]): the kind's name
+ * (avk_kind_name) in `filter`.  One layout, one writer. */
+int avf_write_summary_kind(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks, uint32_t metrics_mask) {
+    if (!path || !kind_blocks || (n_labels && !label_names)) return fail(AVK_E_ARG, "null argument");
+    const char *names[AVK_N_KINDS];
+    for (uint32_t k = 0; k < AVK_N_KINDS; ++k) names[k] = avk_kind_name_of(k);
+    return avf_write_summary_size(path, compare_label, AVK_N_KINDS, names, n_labels, label_names, kind_blocks, metrics_mask);
+}
+
+/* kind_ratios.tsv: Ti/Tv and het/hom of the GT counts.  One row per scope (ALL, then the labels in order) x variant_type x set: the variant types are the rows
+ * summary.tsv prints for GT from the scope's tally — the block summed over its kinds: ALL, the call types that occur, the joint rows that occur — and the sets are
+ * truth_total truth_tp truth_fn query_total query_tp query_fp.  ti / tv: the set's count summed over the kinds with sub ts / tv; het / hom_alt: over the kinds
+ * with gt het / hom; the ratios as summary.tsv formats its metrics, empty where the denominator is 0. */
+int avf_write_kind_ratios(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks) {
+    if (!path || !kind_blocks || (n_labels && !label_names)) return fail(AVK_E_ARG, "null argument");
+    for (uint32_t l = 0; l < n_labels; ++l)
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+    const std::string p(path);
+    const char delim = p.size() >= 4 && p.compare(p.size() - 4, 4, ".csv") == 0 ? ',' : '\t';
+    FILE *fp = fopen(path, "w");
+    if (!fp) return fail(AVK_E_ARG, "cannot create %s", path);
+    const std::string label = csv_field(compare_label ? compare_label : "", delim);
+    static const char *const header[10] = {"compare_label", "region_label", "variant_type", "set", "ti", "tv", "titv_ratio", "het", "hom_alt", "het_hom_ratio"};
+    for (int k = 0; k < 10; ++k) fprintf(fp, "%s%c", header[k], k == 9 ? '\n' : delim);
+    static const char *const type_name[12] = {"Snv", "Insertion", "Deletion", "Indel", "SvInsertion", "SvDeletion", "SvDuplication", "SvInversion",
+                                              "SvBreakend", "TrContraction", "TrExpansion", "Unknown"};
+    struct Joint {
+        const char *label;
+        std::vector<int> types;
+    };
+    const Joint joints[3] = {{"JointIndel", {AVK_VT_INSERTION, AVK_VT_DELETION, AVK_VT_INDEL}},
+                             {"JointStructuralVariant", {AVK_VT_SV_INSERTION, AVK_VT_SV_DELETION, AVK_VT_SV_DUPLICATION, AVK_VT_SV_INVERSION, AVK_VT_SV_BREAKEND}},
+                             {"JointTandemRepeat", {AVK_VT_TR_EXPANSION, AVK_VT_TR_CONTRACTION}}};
+    static const char *const set_name[6] = {"truth_total", "truth_tp", "truth_fn", "query_total", "query_tp", "query_fp"};
+    const int size_fields = AVK_F_WHAP_QUERY_FP + 1;
+    for (uint32_t sc = 0; sc <= n_labels; ++sc) {
+        const std::string region_label = csv_field(sc ? label_names[sc - 1] : "ALL", delim);
+        const uint64_t *block = kind_blocks + (size_t)sc * AVK_N_KINDS * AVK_N_GROUPS * size_fields;
+        /* the six sets of kind k over the groups gs */
+        auto sets_of = [&](uint32_t k, const std::vector<int> &gs, uint64_t s[6]) {
+            uint64_t m[4] = {0, 0, 0, 0};
+            for (int g : gs) {
+                const uint64_t *gp = block + ((size_t)k * AVK_N_GROUPS + g) * size_fields;
+                for (int q = 0; q < 4; ++q) m[q] += gp[AVK_F_GT_TRUTH_TP + q]; /* truth_tp, truth_fn, query_tp, query_fp */
+            }
+            s[0] = m[0] + m[1], s[1] = m[0], s[2] = m[1], s[3] = m[2] + m[3], s[4] = m[2], s[5] = m[3];
+        };
+        auto rows = [&](const char *vtype, const std::vector<int> &gs, bool always) {
+            uint64_t by_kind[AVK_N_KINDS][6], any = 0;
+            for (uint32_t k = 0; k < AVK_N_KINDS; ++k) {
+                sets_of(k, gs, by_kind[k]);
+                any += by_kind[k][0] + by_kind[k][3];
+            }
+            if (!always && !any) return; /* is_empty: no row in summary.tsv */
+            for (int s = 0; s < 6; ++s) {
+                uint64_t ti = 0, tv = 0, het = 0, hom = 0;
+                for (uint32_t k = 0; k < AVK_N_KINDS; ++k) {
+                    const uint32_t gt = k / AVK_KIND_N_SUB, sub = k % AVK_KIND_N_SUB;
+                    if (sub == AVK_KIND_SUB_TS) ti += by_kind[k][s];
+                    if (sub == AVK_KIND_SUB_TV) tv += by_kind[k][s];
+                    if (gt == AVK_KIND_GT_HET) het += by_kind[k][s];
+                    if (gt == AVK_KIND_GT_HOM) hom += by_kind[k][s];
+                }
+                const std::string titv = tv ? fmt_f64((double)ti / (double)tv) : std::string(), hethom = hom ? fmt_f64((double)het / (double)hom) : std::string();
+                fprintf(fp, "%s%c%s%c%s%c%s%c%llu%c%llu%c%s%c%llu%c%llu%c%s\n", label.c_str(), delim, region_label.c_str(), delim, vtype, delim, set_name[s], delim,
+                        (unsigned long long)ti, delim, (unsigned long long)tv, delim, titv.c_str(), delim, (unsigned long long)het, delim, (unsigned long long)hom, delim, hethom.c_str());
+            }
+        };
+        rows("ALL", {0}, true);
+        for (int t = 0; t < AVK_N_VARIANT_TYPES; ++t) rows(type_name[t], {1 + t}, false);
+        for (const Joint &jt : joints) {
+            std::vector<int> gs;
+            for (int t : jt.types) gs.push_back(1 + t);
+            rows(jt.label, gs, false);
+        }
+    }
+    const bool bad = ferror(fp) != 0;
+    if (fclose(fp) != 0 || bad) return fail(AVK_E_ARG, "write error on %s", path);
+    return 0;
+}
+
 /* ---- scores of a VCF's records for the curve by query score ----------------------------------------------------------------------------------------- */
 namespace {
 /* a VCF number -> float; ".", an empty field and anything strtof does not take whole are missing (NaN) */

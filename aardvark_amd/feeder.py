@@ -460,6 +460,33 @@ def write_summary_roc(path, point_names, names, score_blocks, compare_label="com
     _check(lib, lib.avf_write_summary_roc(os.fsencode(path), compare_label.encode(), len(point_names), points, len(names), arr, sb.reshape(-1).ctypes.data_as(u64p), metrics))
 
 
+def _kind_blocks(names, kind_blocks):
+    kb = np.ascontiguousarray(kind_blocks, dtype=np.uint64)
+    if kb.ndim != 4 or kb.shape[0] != 1 + len(names) or kb.shape[1] != 9 or kb.shape[3] != 14:
+        raise ValueError("kind_blocks is [1 + labels, 9, N_GROUPS, 14]")
+    return kb, (C.c_char_p * len(names))(*[n.encode() for n in names]) if names else None
+
+
+def write_summary_kind(path, names, kind_blocks, compare_label="compare", metrics=METRIC_GT | METRIC_HAP | METRIC_WEIGHTED_HAP):
+    """avf_write_summary_kind: summary_kind.tsv — the rows of write_summary_named per scope (ALL, then `names`) and call kind (het / hom x Ti / Tv), the kind's name in
+    the `filter` column; kind_blocks is [1 + len(names), 9, N_GROUPS, 14] (Context.kind_tallies' layout).  BASEPAIR and RECORD_BP bits of `metrics` are ignored"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    kb, arr = _kind_blocks(names, kind_blocks)
+    lib.avf_write_summary_kind.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32]
+    _check(lib, lib.avf_write_summary_kind(os.fsencode(path), compare_label.encode(), len(names), arr, kb.reshape(-1).ctypes.data_as(u64p), metrics))
+
+
+def write_kind_ratios(path, names, kind_blocks, compare_label="compare"):
+    """avf_write_kind_ratios: kind_ratios.tsv — Ti/Tv and het/hom of the GT counts per scope (ALL, then `names`), variant type and set (truth_total .. query_fp);
+    kind_blocks as for write_summary_kind"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    kb, arr = _kind_blocks(names, kind_blocks)
+    lib.avf_write_kind_ratios.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), u64p]
+    _check(lib, lib.avf_write_kind_ratios(os.fsencode(path), compare_label.encode(), len(names), arr, kb.reshape(-1).ctypes.data_as(u64p)))
+
+
 def write_summary_ci(path, tally, names, strat_tallies, boot_blocks, level=95, compare_label="compare", metrics=METRIC_GT | METRIC_BASEPAIR):
     """avf_write_summary_ci: the rows of write_summary_named with percentile intervals of recall, precision and F1 over the bootstrap replicates `boot_blocks`
     ([1 + len(names), replicates, TALLY_LEN], Context.boot_tallies' layout); level: 90, 95 or 99"""

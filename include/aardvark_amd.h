@@ -697,6 +697,37 @@ int  avk_compare_packed_score(avk_ctx *ctx, const avk_packed_batch *batch, const
 int  avk_score_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_score_spec *spec, const float *scores,
                             const avk_region_labels *labels, uint32_t threads, uint64_t *out);
 
+/* PER-CALL TALLIES BY CALL KIND (avk_callkind.inl; the rule is this project's own, stated in aardvark_amd/csrc/avk_callkind.h and DESIGN.md section 5): what kind
+ * of call the errors are — the het/hom and Ti/Tv figures every small-variant benchmark carries.
+ *   kind     kind(call) = 3 * gt + sub, AVK_N_KINDS = 9: het_ts het_tv het_other hom_ts hom_tv hom_other nogt_ts nogt_tv nogt_other (avk_kind_name)
+ *   gt       from the call's INPUT zygosity (var_zyg / var_type_zyg, not the resolved zygosity of the per-call word): 0 het for AVK_ZYG_UNPHASED_HET,
+ *            _PHASED_HET01 and _PHASED_HET10; 1 hom for AVK_ZYG_HOM_ALT; 2 nogt for anything else
+ *   sub      from the two alleles as the batch holds them (escaped lengths resolved), whatever the call's type: if a0_len == 1 and a1_len == 1, the two bytes
+ *            folded to upper case (b & 0xDF) are both one of A C G T and they differ: 0 ts for {A,G} and {C,T}, 1 tv otherwise.  Every other call is 2 other:
+ *            longer or empty alleles, equal bases, N, IUPAC codes, an allele offset outside the allele array
+ *   call     the size rule's contribution (above): the seven values of a call of a SOLVED region, to the truth fields of a truth call or the query fields of a
+ *            query call, of group 0 and group 1 + type, in kind(call), in scope 0 and in scope 1 + l for every label l of the strata handle that holds the
+ *            call's region; unsolved regions and regions whose call ranges lie outside the batch add nothing
+ *   block    out[((scope * AVK_N_KINDS + kind) * AVK_N_GROUPS + g) * AVK_SIZE_FIELDS + f], 64-bit; sums are ADDED; additive over batches, slices, shards, ranks
+ *   law      for every scope, group and f < 14 the sum over the kinds equals the size block summed over its bins: word g * AVK_N_FIELDS + f of that scope's tally
+ * The submit / wait forms and the merge take no kinds. */
+#include "../aardvark_amd/csrc/avk_callkind.h"
+uint32_t avk_kind_n(void);                                      /* AVK_N_KINDS */
+int  avk_kind_name(uint32_t k, char *buf, size_t cap);          /* the name of kind k; AVK_E_ARG for k >= AVK_N_KINDS or a buffer that is too small */
+uint32_t avk_kind_block(const avk_ctx *ctx);                    /* regions a workgroup of the kernel takes at a time */
+/* resident form: a device-packed batch (wide, compact or packed upload, with or without escapes) after avk_compare_resident, otherwise AVK_E_STATE; out == NULL is
+ * AVK_E_ARG; both leave out untouched.  A handle of another context is AVK_E_ARG.  strata == NULL: scope 0 only.  Called after avk_results_download it also counts
+ * the regions the capacity retry repaired. */
+int  avk_kind_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_strata *strata, uint64_t *out);
+/* avk_compare_packed_esc that also returns the block (ADDED to kind_out): results and tally are bit for bit those of the plain call; regions the capacity retry
+ * repairs are counted.  strata == NULL or zero labels: scope 0 only.  The option device_pack 0 is AVK_E_STATE (host route: avk_kind_tallies_host). */
+int  avk_compare_packed_kind(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *strata, const avk_compare_config *cfg,
+                             avk_result_batch *out, uint64_t *kind_out);
+/* host only (no GPU involved): the same sums from the wide batch and its results (status or region_packed; var_expected and var_observed, or var_packed), alt_ed
+ * by avk_edit_distance's rule, scopes from labels (NULL: scope 0 only; a label named twice in a region's list counts twice).  threads: host threads (0: one); the
+ * sums do not depend on the cut. */
+int  avk_kind_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_region_labels *labels, uint32_t threads, uint64_t *out);
+
 /* SEQUENCE-CONTEXT labels (avk_context.inl): labels that are functions of the reference sequence alone, made by kernel from the reference avk_ref_upload left in
  * HBM — a stratified job needs no BED set for them.  The rule is this project's own (the reference has no such labels):
  *   window   a region's query is the one the interval sets get, [first, last] on its contig; a family's window is [first - pad, last + 1 + pad), clamped to the

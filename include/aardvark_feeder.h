@@ -168,6 +168,15 @@ int avf_write_summary_size(const char *path, const char *compare_label, uint32_t
  * and point; a metric whose denominator is 0 at a point is written as summary.tsv writes such a metric. */
 int avf_write_summary_roc(const char *path, const char *compare_label, uint32_t n_points, const char *const *point_names, uint32_t n_labels, const char *const *label_names,
                           const uint64_t *score_blocks, uint32_t metrics_mask);
+/* summary_kind.tsv: the same file keyed by the call kinds (het / hom x Ti / Tv): kind_blocks is avk_kind_tallies' block, [1 + n_labels][AVK_N_KINDS][AVK_N_GROUPS][14],
+ * the kind's name (avk_kind_name) in `filter`; rows and mask bits as avf_write_summary_size. */
+int avf_write_summary_kind(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks, uint32_t metrics_mask);
+/* kind_ratios.tsv from the same block: columns compare_label region_label variant_type set ti tv titv_ratio het hom_alt het_hom_ratio.  One row per region label
+ * (ALL first, then the labels in order) x variant_type (the rows summary.tsv prints for GT from the block summed over its kinds: ALL, the call types that occur, the
+ * joint rows that occur) x set (truth_total truth_tp truth_fn query_total query_tp query_fp, from the GT fields), in this order.  ti and tv are the set's count summed
+ * over the kinds *_ts and *_tv, het and hom_alt over the kinds het_* and hom_*; titv_ratio = ti / tv and het_hom_ratio = het / hom_alt are formatted as summary.tsv's
+ * metrics and are empty where the denominator is 0. */
+int avf_write_kind_ratios(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks);
 /* The scores of a VCF's records for that curve, in one pass over its data lines: out[rec] for the first n_records data lines (the index avf_feed_var_record
  * speaks of), NaN where the file has fewer.  field: "QUAL" (column 6) or "GQ" (FORMAT/GQ of `sample`; NULL or "": the first sample); ".", an absent key or a value
  * that is no number gives NaN.  The record parser is not involved. */
