@@ -17,7 +17,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 
 from ._abi import (CLASSES, FIELDS, KIND_NAMES, N_FIELDS, N_GROUPS, ST_NAMES, TALLY_LEN, VARIANT_TYPES, ZYGOSITIES, BootSpec, SizeSpec, ScoreSpec, CompactBatch, ContextSpec, PackedBatch, PackedEscapes, RegionBatch,
                    ResultBatch)
-from .api import AardvarkAmdError, CompareConfig, Context, library_path, load_library, kind_tallies_host, score_tallies_host, size_tallies_host
+from .api import AardvarkAmdError, CompareConfig, Context, library_path, load_library, kind_tallies_host, kind_boot_tallies_host, size_boot_tallies_host, score_tallies_host, size_tallies_host
 
-__all__ = ["Context", "CompareConfig", "ContextSpec", "BootSpec", "SizeSpec", "size_tallies_host", "ScoreSpec", "score_tallies_host", "KIND_NAMES", "kind_tallies_host", "RegionBatch", "CompactBatch", "PackedBatch", "PackedEscapes", "ResultBatch", "AardvarkAmdError", "load_library", "library_path",
+__all__ = ["Context", "CompareConfig", "ContextSpec", "BootSpec", "SizeSpec", "size_tallies_host", "ScoreSpec", "score_tallies_host", "KIND_NAMES", "kind_tallies_host", "size_boot_tallies_host", "kind_boot_tallies_host", "RegionBatch", "CompactBatch", "PackedBatch", "PackedEscapes", "ResultBatch", "AardvarkAmdError", "load_library", "library_path",
            "VARIANT_TYPES", "ZYGOSITIES", "CLASSES", "FIELDS", "N_GROUPS", "N_FIELDS", "TALLY_LEN", "ST_NAMES"]

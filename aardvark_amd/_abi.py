@@ -355,6 +355,24 @@ def declare_kind(lib):
     lib.avk_kind_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkRegionLabels), C.c_uint32, u64p]
 
 
+CALLBOOT_MAX_BLOCKS = 262144  # AVK_CALLBOOT_MAX_BLOCKS of aardvark_amd/csrc/avk_callboot.h: (1 + labels) * replicates * keys
+
+
+def declare_callboot(lib):
+    """avk_callboot_block, avk_size_boot_tallies, avk_kind_boot_tallies and their host routes (include/aardvark_amd.h)"""
+    vp, u64p = C.c_void_p, _p(C.c_uint64)
+    lib.avk_callboot_block.restype = C.c_uint32
+    lib.avk_callboot_block.argtypes = [vp, C.c_uint32]
+    lib.avk_size_boot_tallies.restype = C.c_int
+    lib.avk_size_boot_tallies.argtypes = [vp, vp, _p(AvkSizeSpec), _p(AvkBootSpec), vp, u64p]
+    lib.avk_kind_boot_tallies.restype = C.c_int
+    lib.avk_kind_boot_tallies.argtypes = [vp, vp, _p(AvkBootSpec), vp, u64p]
+    lib.avk_size_boot_tallies_host.restype = C.c_int
+    lib.avk_size_boot_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkSizeSpec), _p(AvkBootSpec), _p(AvkRegionLabels), C.c_uint32, u64p]
+    lib.avk_kind_boot_tallies_host.restype = C.c_int
+    lib.avk_kind_boot_tallies_host.argtypes = [_p(AvkRegionBatch), _p(AvkResultBatch), _p(AvkBootSpec), _p(AvkRegionLabels), C.c_uint32, u64p]
+
+
 CONTEXT_PAD_MAX, CONTEXT_GC_EDGES_MAX, CONTEXT_HP_EDGES_MAX = 1024, 17, 16
 
 

@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from ._abi import (TALLY_LEN, AvkCompactBatch, AvkCompareConfig, AvkPackedBatch, AvkPackedEscapes, AvkRegionBatch, AvkRegionLabels, AvkResultBatch, CompactBatch,
-                   PackedBatch, RegionBatch, ResultBatch, BootSpec, ContextSpec, SizeSpec, SIZE_FIELDS, ScoreSpec, SCORE_FIELDS, N_KINDS, KIND_FIELDS, N_GROUPS, declare_boot, declare_size, declare_score, declare_kind, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
+                   PackedBatch, RegionBatch, ResultBatch, BootSpec, ContextSpec, SizeSpec, SIZE_FIELDS, ScoreSpec, SCORE_FIELDS, N_KINDS, KIND_FIELDS, N_GROUPS, declare_boot, declare_size, declare_score, declare_kind, declare_callboot, declare_context_strata, declare_debug_ref_packed, declare_submit_strata, ref_packed_sizes,
                    region_labels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -98,6 +98,8 @@ def load_library():
         declare_score(lib)
     if hasattr(lib, "avk_kind_tallies"):  # per-call tallies by call kind (avk_callkind.inl); (AVK_LIB may name an older in-tree build: A/B runs)
         declare_kind(lib)
+    if hasattr(lib, "avk_kind_boot_tallies"):  # bootstrap replicates of the per-call blocks (avk_callboot.inl); (AVK_LIB may name an older in-tree build: A/B runs)
+        declare_callboot(lib)
     if hasattr(lib, "avk_debug_ref_packed"):  # (AVK_LIB may name an older in-tree build: A/B runs)
         declare_debug_ref_packed(lib)
     lib.avk_compare_resident.argtypes = [vp, vp, C.POINTER(AvkCompareConfig), vp]
@@ -599,6 +601,28 @@ class Context:
         self._check(self.lib.avk_kind_tallies(self.handle, rb.handle, None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
         return out
 
+    def callboot_block(self, n_keys):
+        """avk_callboot_block: how many replicates of one scope a launch of the per-call bootstrap kernel holds for n_keys keys (9 kinds, or a SizeSpec's n_bins)"""
+        return int(self.lib.avk_callboot_block(self.handle, int(n_keys)))
+
+    def size_boot_tallies(self, rb, spec, boot, strata=None, out=None):
+        """avk_size_boot_tallies: the bootstrap replicates of size_tallies' block of a solved resident batch; returns / adds to a
+        [1 + n_labels, replicates, n_bins, N_GROUPS, 14] uint64 array — replicate b weighs every region as replicate b of boot_tallies does for the same seed"""
+        n_labels = 0 if strata is None else strata.n_labels
+        out = np.zeros((1 + n_labels, max(boot.replicates, 0), spec.n_bins, N_GROUPS, SIZE_FIELDS), np.uint64) if out is None else out
+        ss, bs = spec.c_struct(), boot.c_struct()
+        self._check(self.lib.avk_size_boot_tallies(self.handle, rb.handle, C.byref(ss), C.byref(bs), None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
+        return out
+
+    def kind_boot_tallies(self, rb, boot, strata=None, out=None):
+        """avk_kind_boot_tallies: the bootstrap replicates of kind_tallies' block of a solved resident batch; returns / adds to a
+        [1 + n_labels, replicates, 9, N_GROUPS, 14] uint64 array"""
+        n_labels = 0 if strata is None else strata.n_labels
+        out = np.zeros((1 + n_labels, max(boot.replicates, 0), N_KINDS, N_GROUPS, KIND_FIELDS), np.uint64) if out is None else out
+        bs = boot.c_struct()
+        self._check(self.lib.avk_kind_boot_tallies(self.handle, rb.handle, C.byref(bs), None if strata is None else strata.handle, out.ctypes.data_as(u64p)))
+        return out
+
     def synchronize(self):
         self._check(self.lib.avk_synchronize(self.handle))
 
@@ -764,3 +788,30 @@ def kind_tallies_host(batch, res, labels=None, threads=1, out=None):
     if rc:
         raise AardvarkAmdError("avk_kind_tallies_host: %d: %s" % (rc, lib.avk_last_error(None).decode()))
     return out
+
+
+def _callboot_host(name, batch, res, spec, boot, labels, threads, out, n_keys):
+    lib = load_library()
+    n_labels = 0 if labels is None else int(labels[0])
+    out = np.zeros((1 + n_labels, max(boot.replicates, 0), n_keys, N_GROUPS, SIZE_FIELDS), np.uint64) if out is None else out
+    cb, ro, bs = batch.c_struct(), res.c_struct(), boot.c_struct()
+    lab = None
+    if labels is not None:
+        lab, _keep = region_labels(*labels)
+    args = [C.byref(cb), C.byref(ro)] + ([] if spec is None else [C.byref(spec)]) + [C.byref(bs), None if lab is None else C.byref(lab), int(threads),
+                                                                                     out.ctypes.data_as(C.POINTER(C.c_uint64))]
+    rc = getattr(lib, name)(*args)
+    if rc:
+        raise AardvarkAmdError("%s: %d: %s" % (name, rc, lib.avk_last_error(None).decode()))
+    return out
+
+
+def size_boot_tallies_host(batch, res, spec, boot, labels=None, threads=1, out=None):
+    """avk_size_boot_tallies_host: Context.size_boot_tallies' sums on the host from a wide RegionBatch and its ResultBatch (no GPU involved);
+    labels=(n_labels, label_off, label_idx) or None -> [1 + n_labels, replicates, n_bins, N_GROUPS, 14] uint64 (added to `out`)"""
+    return _callboot_host("avk_size_boot_tallies_host", batch, res, spec.c_struct(), boot, labels, threads, out, spec.n_bins)
+
+
+def kind_boot_tallies_host(batch, res, boot, labels=None, threads=1, out=None):
+    """avk_kind_boot_tallies_host: Context.kind_boot_tallies' sums on the host -> [1 + n_labels, replicates, 9, N_GROUPS, 14] uint64 (added to `out`)"""
+    return _callboot_host("avk_kind_boot_tallies_host", batch, res, None, boot, labels, threads, out, N_KINDS)

@@ -45,6 +45,7 @@
 #include "avk_strata.inl"
 #include "avk_context.inl"
 #include "avk_boot.inl"
+#include "avk_callboot_host.h"
 #include "avk_mergecount.inl"
 #include "avk_mergesweep.inl"
 static_assert((int)avk::ms::MS_KMAX == (int)avk::dp::DP_MERGE_KMAX, "the sweep kernel decides what the classification kernel decides");
@@ -375,6 +376,7 @@ struct avk_ctx {
     } stage[4];
     hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr; /* AVK_TIMING: around the label kernels */
     int64_t label_lds_bytes = 0;       /* LDS a launch of avk_label_tally_compact_kernel gets (0: not asked yet) */
+    int64_t callboot_lds_bytes = 0;    /* LDS a launch of avk_callboot_tally_kernel gets (0: not asked yet) */
     int64_t mergecount_lds_bytes = 0;  /* ... and a launch of avk_merge_count_kernel */
     int last_merge_counts_on_device = 0; /* the last avk_merge_packed_counts with counters made them by kernel */
     /* options */
@@ -3329,6 +3331,7 @@ extern "C" {
 static_assert(AVK_SIZE_FIELDS == AVK_F_WHAP_QUERY_FP + 1 && AVK_F_GT_TRUTH_TP == 0, "the size block's fields are the first fourteen of a group");
 static_assert(AVK_SZ_BLOCK_WORDS(AVK_SIZE_EDGES_MAX + 1) * 8 <= AVK_SZ_LDS_BYTES && AVK_SZ_THREADS % 64 == 0 && AVK_N_VARIANT_TYPES < 15,
               "a workgroup of avk_size_tally_kernel holds one scope's block of the widest spec, whole waves, and a key its type");
+using avk::cbh::host_call_values; /* (avk_callboot_host.h: the per-call contribution every per-call host route shares) */
 /* the refusals of every entry point with a spec, before anything is queued (no device involved) */
 static int size_spec_check(avk_ctx *ctx, const avk_size_spec *sp, const uint64_t *out) {
     if (!sp) return fail(ctx, AVK_E_ARG, "size bins: spec missing");
@@ -3470,11 +3473,8 @@ int avk_size_tallies_host(const avk_region_batch *b, const avk_result_batch *res
                     const uint64_t v = off + i;
                     const uint32_t vt = b->var_type[v];
                     const uint64_t w = avk::host_edit_distance(b->allele_bytes + b->a0_off[v], b->a0_len[v], b->allele_bytes + b->a1_off[v], b->a1_len[v]); /* Variant::alt_ed */
-                    const uint32_t ea = wide_calls ? res->var_expected[v] : avk_vp_expected(res->var_packed[v]), oa = wide_calls ? res->var_observed[v] : avk_vp_observed(res->var_packed[v]);
-                    /* one iteration of lb_side (avk_labels.inl): the query entries are stored toggled */
-                    const uint32_t exp = side == 0 ? ea : oa, obs = side == 0 ? oa : ea;
-                    const uint32_t val[AVK_SIZE_VALUES] = {exp == obs ? 1u : 0u, exp == obs ? 0u : 1u, (exp != obs && obs > 0) ? 1u : 0u, obs, exp - obs, (uint32_t)((uint64_t)obs * w),
-                                                           (uint32_t)((uint64_t)(uint32_t)(exp - obs) * w)};
+                    uint32_t val[AVK_SIZE_VALUES];
+                    host_call_values(res, wide_calls, v, side, w, val);
                     const uint32_t bin = avk_size_bin_of(sp, avk_size_of(b->a0_len[v], b->a1_len[v]));
                     auto add = [&](uint32_t scope) {
                         for (uint32_t g : {0u, 1u + vt}) {
@@ -3775,11 +3775,8 @@ int avk_kind_tallies_host(const avk_region_batch *b, const avk_result_batch *res
                     const uint64_t v = off + i;
                     const uint32_t vt = b->var_type[v], l0 = b->a0_len[v], l1 = b->a1_len[v];
                     const uint64_t w = avk::host_edit_distance(b->allele_bytes + b->a0_off[v], l0, b->allele_bytes + b->a1_off[v], l1); /* Variant::alt_ed */
-                    const uint32_t ea = wide_calls ? res->var_expected[v] : avk_vp_expected(res->var_packed[v]), oa = wide_calls ? res->var_observed[v] : avk_vp_observed(res->var_packed[v]);
-                    /* one iteration of lb_side (avk_labels.inl): the query entries are stored toggled */
-                    const uint32_t exp = side == 0 ? ea : oa, obs = side == 0 ? oa : ea;
-                    const uint32_t val[AVK_SIZE_VALUES] = {exp == obs ? 1u : 0u, exp == obs ? 0u : 1u, (exp != obs && obs > 0) ? 1u : 0u, obs, exp - obs, (uint32_t)((uint64_t)obs * w),
-                                                           (uint32_t)((uint64_t)(uint32_t)(exp - obs) * w)};
+                    uint32_t val[AVK_SIZE_VALUES];
+                    host_call_values(res, wide_calls, v, side, w, val);
                     const bool bytes = l0 == 1u && l1 == 1u && b->a0_off[v] < b->allele_bytes_len && b->a1_off[v] < b->allele_bytes_len;
                     const uint32_t sub = bytes ? avk_kind_sub_of(1u, 1u, b->allele_bytes[b->a0_off[v]], b->allele_bytes[b->a1_off[v]]) : (uint32_t)AVK_KIND_SUB_OTHER;
                     const uint32_t kind = avk_kind_of(avk_kind_gt_of(b->var_zyg[v]), sub);
@@ -3806,6 +3803,159 @@ int avk_kind_tallies_host(const avk_region_batch *b, const avk_result_batch *res
     for (uint32_t t = 0; t < T; ++t)
         for (size_t k = 0; k < words; ++k) out[k] += part[t][k];
     return 0;
+}
+
+/* ---- bootstrap replicates of the per-call blocks: size bins and call kinds (avk_callboot.h, avk_callboot.inl) ------------------------------------------------ */
+} /* extern "C" */
+#include "avk_callboot.inl"
+extern "C" {
+static_assert(AVK_CALLBOOT_KEY_WORDS * 8 == 1456 && AVK_CB_SLOTS * AVK_CB_REPS_MAX <= AVK_CB_THREADS && AVK_CB_TILE <= AVK_CB_THREADS && AVK_CB_RECS <= AVK_CB_THREADS,
+              "a workgroup of avk_callboot_tally_kernel holds its lane teams, a staging lane per region and one per record");
+static_assert(AVK_CB_LDS_BYTES(AVK_SIZE_EDGES_MAX + 1, 1) <= 64 * 1024 && AVK_N_KINDS <= 16 && AVK_SIZE_EDGES_MAX + 1 <= 16,
+              "one replicate of the widest family fits the LDS every device grants; a key fits four bits");
+static_assert((uint64_t)1000 * AVK_N_KINDS * 17 <= AVK_CALLBOOT_MAX_BLOCKS, "the cap admits 1000 replicates of the kinds in 17 scopes");
+static int64_t callboot_lds(avk_ctx *ctx) { /* the LDS a launch really gets: the whole CU's where the runtime grants it */
+    if (!ctx->callboot_lds_bytes) {
+        int64_t b = 64 * 1024;
+        if (hipFuncSetAttribute((const void *)avk_callboot_tally_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AVK_CB_LDS_MAX) == hipSuccess) b = AVK_CB_LDS_MAX;
+        else {
+            (void)hipGetLastError();
+            int attr = 0;
+            if (hipDeviceGetAttribute(&attr, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) == hipSuccess && attr > 0 && attr < b) b = attr;
+            else (void)hipGetLastError();
+        }
+        ctx->callboot_lds_bytes = b - 1024; /* (the kernel's static words, the barrier's among them, lie beside the dynamic part: 256 bytes by the compiler's count) */
+    }
+    return ctx->callboot_lds_bytes;
+}
+/* the refusals of every entry point, before anything is queued (no device involved): the family's spec, the replicates, the cap, out */
+static int callboot_check(avk_ctx *ctx, int family, const avk_size_spec *sp, const avk_boot_spec *bs, uint32_t n_labels, const uint64_t *out, const char *out_name) {
+    if (family == AVK_CALLBOOT_SIZE) {
+        if (!sp) return fail(ctx, AVK_E_ARG, "size bins: spec missing");
+        if (!avk_size_spec_ok(sp)) return fail(ctx, AVK_E_ARG, "size bins: 1 to %d edges, the first at least 1, strictly ascending", AVK_SIZE_EDGES_MAX);
+    }
+    if (bs->replicates < 1 || bs->replicates > AVK_BOOT_MAX_REPLICATES) return fail(ctx, AVK_E_ARG, "bootstrap: %u replicates, 1 to %u are possible", bs->replicates, AVK_BOOT_MAX_REPLICATES);
+    const uint32_t n_keys = avk_callboot_n_keys(family, sp);
+    if (!avk_callboot_blocks_ok((uint64_t)n_labels + 1, bs->replicates, n_keys))
+        return fail(ctx, AVK_E_ARG, "per-call bootstrap: %u replicates of 1 + %u scopes and %u keys are more than %u blocks", bs->replicates, n_labels, n_keys, AVK_CALLBOOT_MAX_BLOCKS);
+    if (!out) return fail(ctx, AVK_E_ARG, "%s missing", out_name);
+    return 0;
+}
+uint32_t avk_callboot_block(avk_ctx *ctx, uint32_t n_keys) {
+    if (!ctx || n_keys < 1 || n_keys > 16) return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) return 0;
+    return avk::cb::cb_reps(n_keys, (uint64_t)callboot_lds(ctx));
+}
+/* the kernel over the scopes and the blocks of replicates, on stream s behind whatever wrote the batch's results: d_out[(1 + n_labels) * B * n_keys * 182] gains the sums */
+static int callboot_launch(avk_ctx *ctx, avk_dev_batch *db, int family, const avk_size_spec *sp, const avk_boot_spec *bs, uint32_t n_labels, const uint32_t *d_mask,
+                           uint64_t *d_out, hipStream_t s) {
+    const uint64_t n = db->n_regions;
+    if (!n) return 0;
+    avk::lb::LbView v;
+    memset(&v, 0, sizeof(v));
+    v.in = db->dp_args.in, v.vinfo = db->dp_args.vinfo, v.region_out = db->d_region_out, v.var_out = db->d_var_out, v.v_off = db->d_voff;
+    avk_size_spec spec;
+    memset(&spec, 0, sizeof(spec));
+    if (family == AVK_CALLBOOT_SIZE) spec = *sp;
+    const uint32_t n_keys = avk_callboot_n_keys(family, sp), B = bs->replicates;
+    const uint32_t R = avk::cb::cb_reps(n_keys, (uint64_t)callboot_lds(ctx));
+    const size_t lds = AVK_CB_LDS_BYTES(n_keys, R);
+    if ((int64_t)lds > callboot_lds(ctx)) return fail(ctx, AVK_E_HIP, "per-call bootstrap: a launch needs %zu bytes of LDS, the device grants %lld", lds, (long long)callboot_lds(ctx));
+    /* one workgroup a CU (its LDS), and no more workgroups than tiles: each flushes its accumulators once */
+    uint64_t blocks = (n + AVK_CB_TILE - 1) / AVK_CB_TILE;
+    if (blocks > (uint64_t)ctx->n_cus) blocks = (uint64_t)ctx->n_cus;
+    const unsigned long long seed_mix = avk_boot_mix(bs->seed);
+    for (uint32_t scope = 0; scope <= (d_mask ? n_labels : 0u); ++scope)
+        for (uint32_t lo = 0; lo < B; lo += R) {
+            const uint32_t hi = B - lo > R ? lo + R : B;
+            hipLaunchKernelGGL(avk_callboot_tally_kernel, dim3((unsigned)blocks), dim3(AVK_CB_THREADS), lds, s, v, d_mask, (uint32_t)n, family, spec, n_keys, scope, seed_mix, B, lo, hi,
+                               R, (unsigned long long *)d_out);
+            AVK_HIP(ctx, hipGetLastError());
+        }
+    return 0;
+}
+/* a solved resident batch: the scopes' membership (the strata pass's masks), sums cleared, kernels, copy back, wait, added to the caller's: on the context's stream */
+static int callboot_resident_run(avk_ctx *ctx, avk_dev_batch *db, int family, const avk_size_spec *sp, const avk_boot_spec *bs, const avk_strata *st, uint64_t *out) {
+    const uint64_t n = db->n_regions;
+    StrataLists L;
+    int rc = 0;
+    if (st && st->n_labels && n) {
+        rc = strata_lists_alloc(ctx, st, n, L);
+        if (!rc) {
+            const hipError_t e = strata_mask_launch(st, db->dp_args.in, n, (uint32_t *)L.d_mask, (uint64_t *)L.d_sums, ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, AVK_E_HIP, "strata masks failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        strata_lists_release(ctx, L);
+        return rc;
+    }
+    const uint32_t n_labels = L.d_mask ? st->n_labels : 0;
+    const size_t words = ((size_t)n_labels + 1) * bs->replicates * avk_callboot_n_keys(family, sp) * AVK_CALLBOOT_KEY_WORDS;
+    std::vector<uint64_t> host(words, 0);
+    void *d_out = nullptr;
+    rc = pool_alloc(ctx, &d_out, words * 8);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_out, 0, words * 8, ctx->stream);
+    if (!rc && e == hipSuccess) rc = callboot_launch(ctx, db, family, sp, bs, n_labels, (const uint32_t *)L.d_mask, (uint64_t *)d_out, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    pool_release(ctx, d_out);
+    strata_lists_release(ctx, L);
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(ctx, AVK_E_HIP, "per-call bootstrap tallies failed: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    for (size_t k = 0; k < words; ++k) out[k] += host[k];
+    return 0;
+}
+static int callboot_tallies(avk_ctx *ctx, avk_dev_batch *db, int family, const avk_size_spec *sp, const avk_boot_spec *bs, const avk_strata *st, uint64_t *out, const char *out_name) {
+    if (!ctx || !db || !bs) return AVK_E_ARG;
+    if (st && strata_handle_check(ctx, st)) return AVK_E_ARG; /* (before anything of the handle is read) */
+    {
+        const int rb = callboot_check(ctx, family, sp, bs, st ? st->n_labels : 0, out, out_name);
+        if (rb) return rb;
+    }
+    if (!db->dev_packed)
+        return fail(ctx, AVK_E_STATE, "per-call bootstrap tallies on the device need a device-packed batch: the option device_pack was 0 at its upload (host route: avk_%s_boot_tallies_host)",
+                    family == AVK_CALLBOOT_KIND ? "kind" : "size");
+    if (!db->has_run || db->last_mode != 0) return fail(ctx, AVK_E_STATE, "per-call bootstrap tallies need a batch that avk_compare_resident has solved");
+    AVK_HIP(ctx, hipSetDevice(ctx->device));
+    return callboot_resident_run(ctx, db, family, sp, bs, st, out);
+}
+int avk_size_boot_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *sp, const avk_boot_spec *bs, const avk_strata *st, uint64_t *out) {
+    return callboot_tallies(ctx, db, AVK_CALLBOOT_SIZE, sp, bs, st, out, "size_boot_tallies");
+}
+int avk_kind_boot_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *bs, const avk_strata *st, uint64_t *out) {
+    return callboot_tallies(ctx, db, AVK_CALLBOOT_KIND, nullptr, bs, st, out, "kind_boot_tallies");
+}
+
+/* host only: the checks here, the sums in avk_callboot_host.h (X_r from the wide batch and its results, weighted with avk_boot.h's rule) */
+static int callboot_tallies_host(const avk_region_batch *b, const avk_result_batch *res, int family, const avk_size_spec *sp, const avk_boot_spec *bs, const avk_region_labels *lab,
+                                 uint32_t threads, uint64_t *out, const char *out_name) {
+    if (!b || !res || !bs) return fail(nullptr, AVK_E_ARG, "per-call bootstrap: batch, results or spec missing");
+    const uint32_t n_labels = lab ? lab->n_labels : 0;
+    {
+        const int rb = callboot_check(nullptr, family, sp, bs, n_labels, out, out_name);
+        if (rb) return rb;
+        if (lab && n_labels) {
+            const int rl = labels_check(nullptr, b->n_regions, lab, out);
+            if (rl) return rl;
+        }
+    }
+    if (!(res->status || res->region_packed)) return fail(nullptr, AVK_E_ARG, "per-call bootstrap: the results have neither status nor region_packed");
+    const bool wide_calls = res->var_expected && res->var_observed;
+    if (!wide_calls && !res->var_packed) return fail(nullptr, AVK_E_ARG, "per-call bootstrap: the results have no per-call outputs");
+    if (b->n_regions && !b->start) return fail(nullptr, AVK_E_ARG, "per-call bootstrap: the batch has no start array");
+    if (avk::cbh::callboot_host_sum(b, res, family, sp, bs, lab && n_labels ? lab : nullptr, threads, out, avk::host_edit_distance))
+        return fail(nullptr, AVK_E_ARG, "per-call bootstrap: a region's calls lie outside the batch");
+    return 0;
+}
+int avk_size_boot_tallies_host(const avk_region_batch *b, const avk_result_batch *res, const avk_size_spec *sp, const avk_boot_spec *bs, const avk_region_labels *lab, uint32_t threads,
+                               uint64_t *out) {
+    return callboot_tallies_host(b, res, AVK_CALLBOOT_SIZE, sp, bs, lab, threads, out, "size_boot_tallies");
+}
+int avk_kind_boot_tallies_host(const avk_region_batch *b, const avk_result_batch *res, const avk_boot_spec *bs, const avk_region_labels *lab, uint32_t threads, uint64_t *out) {
+    return callboot_tallies_host(b, res, AVK_CALLBOOT_KIND, nullptr, bs, lab, threads, out, "kind_boot_tallies");
 }
 
 int avk_compare_packed_submit_strata(avk_ctx *ctx, const avk_packed_batch *batch, const avk_packed_escapes *esc, const avk_strata *st, const avk_compare_config *cfg,

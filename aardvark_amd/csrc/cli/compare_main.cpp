@@ -8,6 +8,7 @@
 #include <dlfcn.h>
 #include <algorithm>
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <cerrno>
 #include <chrono>
@@ -50,7 +51,9 @@ void usage() {
             "   in the filter column, summed on the GPU from the ONE comparison of the job: an approximation of a filtered re-run per threshold, which could draw other regions)\n"
             "  [--roc-thresholds 5,10,15,20,25,30,35,40,50,60]  (1 to 31 finite, strictly ascending numbers; points score_all, score_ge_5, ..)\n"
             "  [--kind-strata]  (writes summary_kind.tsv: summary.tsv's GT, HAP and WEIGHTED_HAP rows per call kind — het / hom / nogt by the call's genotype x ts / tv / other by its\n"
-            "   two allele bases, the kind's name in the filter column — and kind_ratios.tsv: Ti/Tv and het/hom of the GT counts per region label, variant type and set; summed on the GPU)\n");
+            "   two allele bases, the kind's name in the filter column — and kind_ratios.tsv: Ti/Tv and het/hom of the GT counts per region label, variant type and set; summed on the GPU)\n"
+            "  [--bootstrap-per-call]  (with --bootstrap B and --size-strata and / or --kind-strata: the replicates of the size-bin and call-kind blocks as well; writes\n"
+            "   summary_size_ci.tsv, summary_kind_ci.tsv and kind_ratios_ci.tsv: the rows of the plain files with --bootstrap-level percentile intervals)\n");
 }
 
 std::string json_string(const std::string &s) {
@@ -110,6 +113,7 @@ int main(int argc, char **argv) {
     bool roc = false, roc_override = false;
     /* --kind-strata: per-call tallies by call kind (het / hom x Ti / Tv) for summary_kind.tsv and kind_ratios.tsv */
     bool kind = false;
+    bool pcb = false; /* --bootstrap-per-call: replicates of the size-bin and call-kind blocks (avk_callboot.h) */
     std::string roc_field, roc_list = "5,10,15,20,25,30,35,40,50,60";
     auto number_list = [](const std::string &opt, const std::string &list) {
         std::vector<uint32_t> out;
@@ -209,6 +213,7 @@ int main(int argc, char **argv) {
         else if (a == "--size-edges") size_edges = number_list(a, val()), size_override = true;
         else if (a == "--roc") roc_field = val(), roc = true;
         else if (a == "--kind-strata") kind = true;
+        else if (a == "--bootstrap-per-call") pcb = true;
         else if (a == "--roc-thresholds") roc_list = val(), roc_override = true;
         else if (a == "-h" || a == "--help") {
             usage();
@@ -248,6 +253,16 @@ int main(int argc, char **argv) {
     /* The replicates are summed where the blocks are: by kernel behind the packed call (avk_compare_packed_boot; labels from the sets resident on the GPU), or on the
      * host from the wide feed's results (avk_boot_tallies_host).  What neither route carries is refused here, by name. */
     const bool boot = boot_spec.replicates != 0;
+    /* --bootstrap-per-call: the replicates of the size-bin and call-kind blocks are summed where those blocks are — on the resident batch by kernel on the packed feed
+     * (avk_size_boot_tallies, avk_kind_boot_tallies: --bootstrap keeps the batch resident beside --size-strata / --kind-strata), on the host from the wide feed's
+     * results (avk_size_boot_tallies_host, avk_kind_boot_tallies_host).  What neither route carries is refused here, by name, before anything is loaded. */
+    if (pcb) {
+        if (!boot) die(64, "--bootstrap-per-call needs --bootstrap B (the replicates' count, seed and level are --bootstrap's)", "");
+        if (!size && !kind) die(64, "--bootstrap-per-call needs --size-strata or --kind-strata (the blocks whose replicates it sums)", "");
+        if (!debug_dir.empty()) die(64, "--bootstrap-per-call cannot be combined with --output-debug (the debug run writes per-region tables, not replicates)", "");
+        if (!strat_tsv.empty() && strat_lists == "host" && want_packed)
+            die(64, "--bootstrap-per-call on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
+    }
     if (boot_override && !boot) die(64, "--bootstrap-seed and --bootstrap-level need --bootstrap", "");
     if (boot && !debug_dir.empty()) die(64, "--bootstrap cannot be combined with --output-debug (the debug run writes per-region tables, not replicates)", "");
     if (boot && !strat_tsv.empty() && strat_lists == "host" && want_packed)
@@ -297,6 +312,14 @@ int main(int argc, char **argv) {
         if (!strat_tsv.empty() && strat_lists == "host" && want_packed)
             die(64, "--kind-strata on the packed feed reads the labels from the sets on the GPU: it cannot be combined with --strat-lists host", "");
     }
+    /* the cap of avk_callboot.h, as soon as the labels are counted: the context labels are known here, the sets' once the table of sets is read */
+    auto pcb_cap_check = [&](uint32_t labels) {
+        if (!pcb) return;
+        const uint64_t keys = (size ? size_spec.n_edges + 1u : 0u) > (kind ? (uint32_t)AVK_N_KINDS : 0u) ? size_spec.n_edges + 1u : (uint32_t)AVK_N_KINDS;
+        if (!avk_callboot_blocks_ok((uint64_t)labels + 1, boot_spec.replicates, keys))
+            die(64, "--bootstrap-per-call: replicates x (1 + region labels) x keys (size bins, or the 9 kinds) may not exceed 262144 blocks", "");
+    };
+    pcb_cap_check(n_ctx_labels);
     if (!devices.empty()) device = devices[0];
     if (mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create output folder", out_dir.c_str());
     if (!debug_dir.empty() && mkdir(debug_dir.c_str(), 0777) != 0 && errno != EEXIST) die(74, "cannot create debug folder", debug_dir.c_str());
@@ -385,6 +408,7 @@ int main(int argc, char **argv) {
     const uint32_t n_bed_labels = avf_strat_n_labels(strat), n_labels = n_bed_labels + n_ctx_labels; /* the sets' labels, then the context labels */
     if (boot && ((uint64_t)n_labels + 1) * boot_spec.replicates > AVK_BOOT_MAX_BLOCKS)
         die(64, "--bootstrap: replicates x (1 + region labels) may not exceed 16384 blocks", "");
+    pcb_cap_check(n_labels);
 
     /* the reference goes to the GPU (upload + 2-bit packing) while the regions are walked */
     t0 = std::chrono::steady_clock::now();
@@ -506,6 +530,21 @@ int main(int argc, char **argv) {
         lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
         return avk_boot_tallies_host(&b, &out, &boot_spec, n_labels ? &lab : nullptr, 16, reps);
     };
+    /* --bootstrap-per-call: a context's (or, on the wide feed, a worker's) replicates of the two blocks, found by a key of its own — the context on the packed
+     * feed, the worker's block of plain sums on the wide feed — and added on the host at the end, as the contexts' other blocks are */
+    struct PerCall {
+        std::vector<uint64_t> size_reps, kind_reps;
+    };
+    std::map<const void *, PerCall> pcb_bufs;
+    std::mutex pcb_mutex;
+    auto pcb_of = [&](const void *key) -> PerCall & {
+        std::lock_guard<std::mutex> lock(pcb_mutex);
+        PerCall &pc = pcb_bufs[key];
+        const size_t scopes = (size_t)(avf_strat_n_labels(strat) + n_ctx_labels) + 1;
+        if (size && pc.size_reps.empty()) pc.size_reps.assign(scopes * boot_spec.replicates * (size_spec.n_edges + 1u) * AVK_CALLBOOT_KEY_WORDS, 0);
+        if (kind && pc.kind_reps.empty()) pc.kind_reps.assign(scopes * boot_spec.replicates * AVK_N_KINDS * AVK_CALLBOOT_KEY_WORDS, 0);
+        return pc;
+    };
     /* --size-strata on the packed feed: the part's results and its size blocks.  Alone it is one call (avk_compare_packed_size); when the labels' sums or the
      * replicates are wanted of the same batch the batch stays resident: solve, download (the capacity retry patches the device view), then the label, bootstrap and
      * size kernels on it — the sums the one-call forms return */
@@ -524,6 +563,7 @@ int main(int argc, char **argv) {
         if (!rc && sets) rc = avk_label_tallies_strata(c, db, sets, sums);
         if (!rc && boot) rc = avk_boot_tallies(c, db, &boot_spec, sets, reps);
         if (!rc) rc = avk_size_tallies(c, db, &size_spec, sets, blocks);
+        if (!rc && pcb) rc = avk_size_boot_tallies(c, db, &size_spec, &boot_spec, sets, pcb_of(c).size_reps.data());
         if (db) avk_batch_free(c, db);
         return rc;
     };
@@ -545,6 +585,7 @@ int main(int argc, char **argv) {
         if (!rc && sets) rc = avk_label_tallies_strata(c, db, sets, sums);
         if (!rc && boot) rc = avk_boot_tallies(c, db, &boot_spec, sets, reps);
         if (!rc && size) rc = avk_size_tallies(c, db, &size_spec, sets, blocks);
+        if (!rc && size && pcb) rc = avk_size_boot_tallies(c, db, &size_spec, &boot_spec, sets, pcb_of(c).size_reps.data());
         if (!rc) rc = avk_score_tallies(c, db, &roc_spec, sc, sets, curve);
         if (db) avk_batch_free(c, db);
         return rc;
@@ -566,8 +607,10 @@ int main(int argc, char **argv) {
         if (!rc && sets) rc = avk_label_tallies_strata(c, db, sets, sums);
         if (!rc && boot) rc = avk_boot_tallies(c, db, &boot_spec, sets, reps);
         if (!rc && size) rc = avk_size_tallies(c, db, &size_spec, sets, blocks);
+        if (!rc && size && pcb) rc = avk_size_boot_tallies(c, db, &size_spec, &boot_spec, sets, pcb_of(c).size_reps.data());
         if (!rc && roc) rc = avk_score_tallies(c, db, &roc_spec, roc_scores.data() + v_first, sets, curve);
         if (!rc) rc = avk_kind_tallies(c, db, sets, kinds);
+        if (!rc && pcb) rc = avk_kind_boot_tallies(c, db, &boot_spec, sets, pcb_of(c).kind_reps.data());
         if (db) avk_batch_free(c, db);
         return rc;
     };
@@ -575,7 +618,8 @@ int main(int argc, char **argv) {
     auto kind_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *kinds) -> int {
         avk_region_labels lab;
         lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
-        return avk_kind_tallies_host(&b, &out, n_labels ? &lab : nullptr, 16, kinds);
+        const int rc = avk_kind_tallies_host(&b, &out, n_labels ? &lab : nullptr, 16, kinds);
+        return rc || !pcb ? rc : avk_kind_boot_tallies_host(&b, &out, &boot_spec, n_labels ? &lab : nullptr, 16, pcb_of(kinds).kind_reps.data());
     };
     /* --roc on the wide feed: the part's curve from its results on the host (the part's call offsets are the feed's) */
     auto roc_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *curve) -> int {
@@ -587,7 +631,8 @@ int main(int argc, char **argv) {
     auto size_part_host = [&](const avk_region_batch &b, const avk_result_batch &out, const uint64_t *label_off, const uint32_t *label_idx, uint64_t *blocks) -> int {
         avk_region_labels lab;
         lab.n_labels = n_labels, lab.label_off = label_off, lab.label_idx = label_idx;
-        return avk_size_tallies_host(&b, &out, &size_spec, n_labels ? &lab : nullptr, 16, blocks);
+        const int rc = avk_size_tallies_host(&b, &out, &size_spec, n_labels ? &lab : nullptr, 16, blocks);
+        return rc || !pcb ? rc : avk_size_boot_tallies_host(&b, &out, &size_spec, &boot_spec, n_labels ? &lab : nullptr, 16, pcb_of(blocks).size_reps.data());
     };
     auto upload_part = [&](avk_ctx *c, const avk_region_batch &b, uint64_t at_abs, uint64_t n, avk_dev_batch **db, uint64_t *v_first) -> int {
         *v_first = 0;
@@ -686,6 +731,12 @@ int main(int argc, char **argv) {
         fprintf(stderr, "Bootstrap: %u replicates, seed %llu, %u %% intervals in summary_ci.tsv; the replicates are summed %s.\n", boot_spec.replicates,
                 (unsigned long long)boot_spec.seed, boot_level,
                 boot_host ? "on the host from each batch's results (avk_boot_tallies_host, the wide feed)" : "on the GPU behind each batch's solve (avk_compare_packed_boot)");
+    if (verbosity && pcb)
+        fprintf(stderr, "Per-call bootstrap: %u replicates of the %s%s%s in %s%s%s, %u %% intervals; the replicates are summed %s.\n", boot_spec.replicates, size ? "size bins" : "",
+                size && kind ? " and the " : "", kind ? "call kinds" : "", size ? "summary_size_ci.tsv" : "", size && kind ? ", " : "", kind ? "summary_kind_ci.tsv and kind_ratios_ci.tsv" : "",
+                boot_level,
+                !packed ? "on the host from each batch's results (avk_size_boot_tallies_host / avk_kind_boot_tallies_host, the wide feed)"
+                        : "on the GPU on each resident batch behind its solve and download (avk_size_boot_tallies / avk_kind_boot_tallies)");
     if (verbosity && compact_labels) {
         if (strata_route)
             fprintf(stderr, "Region labels: listed on the GPU (--strat-lists device, avk_compare_packed_strata): %llu intervals of %u labels uploaded once per context.\n",
@@ -1192,6 +1243,14 @@ int main(int argc, char **argv) {
         for (const std::string &n : bin_names) bin_ptrs.push_back(n.c_str());
         if (avf_write_summary_size((out_dir + "/summary_size.tsv").c_str(), label.c_str(), size_bins, bin_ptrs.data(), n_labels, sz_ptrs.data(), size_total.data(), mask))
             die(74, "Error while saving summary_size.tsv", avf_last_error());
+        if (pcb) { /* summary_size_ci.tsv: the same rows with the replicates' percentile intervals; the contexts' (workers') blocks are added here, on the host */
+            std::vector<uint64_t> reps(((size_t)n_labels + 1) * boot_spec.replicates * size_bins * AVK_CALLBOOT_KEY_WORDS, 0);
+            for (const auto &kv : pcb_bufs)
+                for (size_t k = 0; k < kv.second.size_reps.size(); ++k) reps[k] += kv.second.size_reps[k];
+            if (avf_write_summary_size_ci((out_dir + "/summary_size_ci.tsv").c_str(), label.c_str(), size_bins, bin_ptrs.data(), n_labels, sz_ptrs.data(), size_total.data(), mask,
+                                          boot_spec.replicates, reps.data(), boot_level))
+                die(74, "Error while saving summary_size_ci.tsv", avf_last_error());
+        }
     }
     if (kind) { /* summary_kind.tsv: summary.tsv's GT / HAP / WEIGHTED_HAP rows per scope and call kind; kind_ratios.tsv: their Ti/Tv and het/hom */
         std::vector<std::string> kd_names;
@@ -1207,6 +1266,16 @@ int main(int argc, char **argv) {
             die(74, "Error while saving summary_kind.tsv", avf_last_error());
         if (avf_write_kind_ratios((out_dir + "/kind_ratios.tsv").c_str(), label.c_str(), n_labels, kd_ptrs.data(), kind_total.data()))
             die(74, "Error while saving kind_ratios.tsv", avf_last_error());
+        if (pcb) { /* summary_kind_ci.tsv and kind_ratios_ci.tsv, likewise */
+            std::vector<uint64_t> reps(((size_t)n_labels + 1) * boot_spec.replicates * AVK_N_KINDS * AVK_CALLBOOT_KEY_WORDS, 0);
+            for (const auto &kv : pcb_bufs)
+                for (size_t k = 0; k < kv.second.kind_reps.size(); ++k) reps[k] += kv.second.kind_reps[k];
+            if (avf_write_summary_kind_ci((out_dir + "/summary_kind_ci.tsv").c_str(), label.c_str(), n_labels, kd_ptrs.data(), kind_total.data(), mask, boot_spec.replicates, reps.data(),
+                                          boot_level))
+                die(74, "Error while saving summary_kind_ci.tsv", avf_last_error());
+            if (avf_write_kind_ratios_ci((out_dir + "/kind_ratios_ci.tsv").c_str(), label.c_str(), n_labels, kd_ptrs.data(), kind_total.data(), boot_spec.replicates, reps.data(), boot_level))
+                die(74, "Error while saving kind_ratios_ci.tsv", avf_last_error());
+        }
     }
     if (roc) { /* summary_roc.tsv: summary.tsv's GT / HAP / WEIGHTED_HAP rows per scope and point of the curve */
         std::vector<std::string> sc_names, point_names;

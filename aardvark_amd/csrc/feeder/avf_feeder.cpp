@@ -2204,12 +2204,33 @@ int avf_write_summary(const char *path, const char *compare_label, const uint64_
  * A metric's interval is taken over the m replicates in which it is defined (its denominator is not 0), sorted ascending: with a = 100 - level_percent,
  * lo = x[floor(a m / 200)], hi = x[ceil((200 - a) m / 200) - 1], both in integer arithmetic and clamped to [0, m - 1]; m = 0: empty cells.  The column
  * `replicates` is the m of F1 (recall and precision both defined and not both 0), the smallest of the three.  Joint rows are summed per replicate before the ratio is taken. */
-int avf_write_summary_ci(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names, const uint64_t *strat_tallies,
-                         uint32_t metrics_mask, uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent) {
-    if (!path || !tally || (n_labels && (!strat_tallies || !label_names)) || !replicates || !boot_blocks) return fail(AVK_E_ARG, "null argument, or no replicates");
-    if (level_percent != 90 && level_percent != 95 && level_percent != 99) return fail(AVK_E_ARG, "the interval's level is 90, 95 or 99, not %u", level_percent);
-    for (uint32_t l = 0; l < n_labels; ++l)
-        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+/* the percentile rule, ONE statement for every _ci file: xs (sorted here) -> the cells lo and hi, empty for m = 0 */
+static void ci_bounds(std::vector<double> &xs, uint32_t level_percent, std::string &lo, std::string &hi) {
+    std::sort(xs.begin(), xs.end());
+    const uint64_t a = 100 - level_percent, mq = xs.size();
+    lo.clear(), hi.clear();
+    if (!mq) return;
+    uint64_t il = a * mq / 200, ih = ((200 - a) * mq + 199) / 200;
+    ih = ih ? ih - 1 : 0;
+    if (il > mq - 1) il = mq - 1;
+    if (ih > mq - 1) ih = mq - 1;
+    lo = fmt_f64(xs[il]), hi = fmt_f64(xs[ih]);
+}
+static const char *const ci_type_name[12] = {"Snv", "Insertion", "Deletion", "Indel", "SvInsertion", "SvDeletion", "SvDuplication", "SvInversion",
+                                             "SvBreakend", "TrContraction", "TrExpansion", "Unknown"};
+static const char *const ci_joint_name[3] = {"JointIndel", "JointStructuralVariant", "JointTandemRepeat"};
+static const std::vector<int> &ci_joint_types(int j) {
+    static const std::vector<int> types[3] = {{AVK_VT_INSERTION, AVK_VT_DELETION, AVK_VT_INDEL},
+                                              {AVK_VT_SV_INSERTION, AVK_VT_SV_DELETION, AVK_VT_SV_DUPLICATION, AVK_VT_SV_INVERSION, AVK_VT_SV_BREAKEND},
+                                              {AVK_VT_TR_EXPANSION, AVK_VT_TR_CONTRACTION}};
+    return types[j];
+}
+/* The rows of a _ci file, ONE statement for summary_ci.tsv, summary_size_ci.tsv and summary_kind_ci.tsv: for each scope and each filter the rows write_summary_rows
+ * writes for the point block points[scope * n_filters + filter], each with the intervals over the replicates reps[scope * n_filters + filter] + b * rep_stride.  A
+ * block holds group_stride words a group, the counters of a metric kind at the same index in either layout (22 words: a tally; 14: a keyed block). */
+static int write_ci_rows(const char *path, const char *compare_label, uint32_t n_scopes, const char *const *scope_names, uint32_t n_filters, const char *const *filter_names,
+                         const uint64_t *const *points, const uint64_t *const *reps, size_t rep_stride, size_t group_stride, uint32_t metrics_mask, uint32_t replicates,
+                         uint32_t level_percent) {
     const std::string p(path);
     const char delim = p.size() >= 4 && p.compare(p.size() - 4, 4, ".csv") == 0 ? ',' : '\t';
     FILE *fp = fopen(path, "w");
@@ -2218,12 +2239,6 @@ int avf_write_summary_ci(const char *path, const char *compare_label, const uint
     static const char *const header[15] = {"compare_label", "comparison", "region_label", "filter", "variant_type", "metric_recall", "recall_lo", "recall_hi",
                                            "metric_precision", "precision_lo", "precision_hi", "metric_f1", "f1_lo", "f1_hi", "replicates"};
     for (int k = 0; k < 15; ++k) fprintf(fp, "%s%c", header[k], k == 14 ? '\n' : delim);
-    static const char *const type_name[12] = {"Snv", "Insertion", "Deletion", "Indel", "SvInsertion", "SvDeletion", "SvDuplication", "SvInversion",
-                                              "SvBreakend", "TrContraction", "TrExpansion", "Unknown"};
-    const std::vector<int> joint_types[3] = {{AVK_VT_INSERTION, AVK_VT_DELETION, AVK_VT_INDEL},
-                                             {AVK_VT_SV_INSERTION, AVK_VT_SV_DELETION, AVK_VT_SV_DUPLICATION, AVK_VT_SV_INVERSION, AVK_VT_SV_BREAKEND},
-                                             {AVK_VT_TR_EXPANSION, AVK_VT_TR_CONTRACTION}};
-    static const char *const joint_name[3] = {"JointIndel", "JointStructuralVariant", "JointTandemRepeat"};
     const struct {
         uint32_t bit;
         const char *name;
@@ -2238,16 +2253,15 @@ int avf_write_summary_ci(const char *path, const char *compare_label, const uint
         v[1] = ok[1] ? (double)m[2] / (double)qtot : 0.0;
         v[2] = ok[2] ? 2.0 * v[0] * v[1] / (v[0] + v[1]) : 0.0;
     };
-    const uint64_t a = 100 - level_percent;
     std::vector<double> xs[3];
-    auto write_group = [&](const uint64_t *point, const uint64_t *reps, const std::string &region_label) {
+    auto write_group = [&](const uint64_t *point, const uint64_t *rep0, const std::string &region_label, const std::string &filter) {
         for (const auto &kd : kinds) {
             if (!(metrics_mask & kd.bit)) continue;
             /* the four sums of the groups `groups` of a block, added */
             auto sums = [&](const uint64_t *block, const std::vector<int> &groups, uint64_t m[4]) {
                 m[0] = m[1] = m[2] = m[3] = 0;
                 for (int g : groups)
-                    for (int k = 0; k < 4; ++k) m[k] += block[(size_t)g * AVK_N_FIELDS + kd.base + k];
+                    for (int k = 0; k < 4; ++k) m[k] += block[(size_t)g * group_stride + kd.base + k];
             };
             auto row = [&](const char *vtype, const std::vector<int> &groups, bool always) {
                 uint64_t m[4];
@@ -2261,39 +2275,157 @@ int avf_write_summary_ci(const char *path, const char *compare_label, const uint
                     uint64_t mb[4];
                     double vb[3];
                     bool okb[3];
-                    sums(reps + (size_t)b * AVK_TALLY_LEN, groups, mb);
+                    sums(rep0 + (size_t)b * rep_stride, groups, mb);
                     ratios(mb, vb, okb);
                     for (int q = 0; q < 3; ++q)
                         if (okb[q] && vb[q] == vb[q]) xs[q].push_back(vb[q]); /* (F1 of recall = precision = 0 is 0 / 0: not defined in that replicate) */
                 }
-                fprintf(fp, "%s%c%s%c%s%cALL%c%s", label.c_str(), delim, kd.name, delim, region_label.c_str(), delim, delim, vtype);
+                fprintf(fp, "%s%c%s%c%s%c%s%c%s", label.c_str(), delim, kd.name, delim, region_label.c_str(), delim, filter.c_str(), delim, vtype);
                 for (int q = 0; q < 3; ++q) {
-                    std::sort(xs[q].begin(), xs[q].end());
-                    const uint64_t mq = xs[q].size();
                     std::string lo, hi;
-                    if (mq) {
-                        uint64_t il = a * mq / 200, ih = ((200 - a) * mq + 199) / 200;
-                        ih = ih ? ih - 1 : 0;
-                        if (il > mq - 1) il = mq - 1;
-                        if (ih > mq - 1) ih = mq - 1;
-                        lo = fmt_f64(xs[q][il]), hi = fmt_f64(xs[q][ih]);
-                    }
+                    ci_bounds(xs[q], level_percent, lo, hi);
                     fprintf(fp, "%c%s%c%s%c%s", delim, ok[q] ? fmt_f64(v[q]).c_str() : "", delim, lo.c_str(), delim, hi.c_str());
                 }
                 fprintf(fp, "%c%llu\n", delim, (unsigned long long)xs[2].size());
             };
             row("ALL", {0}, true);
-            for (int t = 0; t < AVK_N_VARIANT_TYPES; ++t) row(type_name[t], {1 + t}, false);
+            for (int t = 0; t < AVK_N_VARIANT_TYPES; ++t) row(ci_type_name[t], {1 + t}, false);
             for (int j = 0; j < 3; ++j) {
                 std::vector<int> groups;
-                for (int t : joint_types[j]) groups.push_back(1 + t);
-                row(joint_name[j], groups, false);
+                for (int t : ci_joint_types(j)) groups.push_back(1 + t);
+                row(ci_joint_name[j], groups, false);
             }
         }
     };
-    write_group(tally, boot_blocks, "ALL");
+    for (uint32_t sc = 0; sc < n_scopes; ++sc)
+        for (uint32_t fl = 0; fl < n_filters; ++fl)
+            write_group(points[(size_t)sc * n_filters + fl], reps[(size_t)sc * n_filters + fl], csv_field(scope_names[sc], delim), csv_field(filter_names[fl], delim));
+    const bool bad = ferror(fp) != 0;
+    if (fclose(fp) != 0 || bad) return fail(AVK_E_ARG, "write error on %s", path);
+    return 0;
+}
+
+int avf_write_summary_ci(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names, const uint64_t *strat_tallies,
+                         uint32_t metrics_mask, uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent) {
+    if (!path || !tally || (n_labels && (!strat_tallies || !label_names)) || !replicates || !boot_blocks) return fail(AVK_E_ARG, "null argument, or no replicates");
+    if (level_percent != 90 && level_percent != 95 && level_percent != 99) return fail(AVK_E_ARG, "the interval's level is 90, 95 or 99, not %u", level_percent);
     for (uint32_t l = 0; l < n_labels; ++l)
-        write_group(strat_tallies + (size_t)l * AVK_TALLY_LEN, boot_blocks + (size_t)(1 + l) * replicates * AVK_TALLY_LEN, csv_field(label_names[l], delim));
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+    std::vector<const char *> scopes = {"ALL"};
+    std::vector<const uint64_t *> points = {tally}, reps = {boot_blocks};
+    for (uint32_t l = 0; l < n_labels; ++l)
+        scopes.push_back(label_names[l]), points.push_back(strat_tallies + (size_t)l * AVK_TALLY_LEN), reps.push_back(boot_blocks + (size_t)(1 + l) * replicates * AVK_TALLY_LEN);
+    static const char *const all = "ALL";
+    return write_ci_rows(path, compare_label, 1 + n_labels, scopes.data(), 1, &all, points.data(), reps.data(), AVK_TALLY_LEN, AVK_N_FIELDS, metrics_mask, replicates, level_percent);
+}
+
+/* summary_size_ci.tsv: summary_size.tsv's rows — same order, same rows left out, the bin's name in `filter` — each with summary_ci.tsv's ten interval columns, by
+ * avf_write_summary_ci's percentile rule.  size_blocks: the point block, avk_size_tallies' layout; boot_blocks: avk_size_boot_tallies' layout,
+ * [1 + n_labels][replicates][n_bins][AVK_N_GROUPS][14].  BASEPAIR and RECORD_BP bits of the mask are ignored, as in summary_size.tsv. */
+int avf_write_summary_size_ci(const char *path, const char *compare_label, uint32_t n_bins, const char *const *bin_names, uint32_t n_labels, const char *const *label_names,
+                              const uint64_t *size_blocks, uint32_t metrics_mask, uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent) {
+    if (!path || !n_bins || !bin_names || !size_blocks || (n_labels && !label_names) || !replicates || !boot_blocks) return fail(AVK_E_ARG, "null argument, no bins, or no replicates");
+    if (level_percent != 90 && level_percent != 95 && level_percent != 99) return fail(AVK_E_ARG, "the interval's level is 90, 95 or 99, not %u", level_percent);
+    for (uint32_t b = 0; b < n_bins; ++b)
+        if (!bin_names[b]) return fail(AVK_E_ARG, "null argument");
+    for (uint32_t l = 0; l < n_labels; ++l)
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+    const size_t key_words = (size_t)AVK_N_GROUPS * (AVK_F_WHAP_QUERY_FP + 1);
+    std::vector<const char *> scopes = {"ALL"};
+    for (uint32_t l = 0; l < n_labels; ++l) scopes.push_back(label_names[l]);
+    std::vector<const uint64_t *> points, reps;
+    for (uint32_t sc = 0; sc <= n_labels; ++sc)
+        for (uint32_t k = 0; k < n_bins; ++k)
+            points.push_back(size_blocks + ((size_t)sc * n_bins + k) * key_words), reps.push_back(boot_blocks + ((size_t)sc * replicates * n_bins + k) * key_words);
+    return write_ci_rows(path, compare_label, 1 + n_labels, scopes.data(), n_bins, bin_names, points.data(), reps.data(), (size_t)n_bins * key_words, AVK_F_WHAP_QUERY_FP + 1,
+                         metrics_mask & ~(uint32_t)(AVF_METRIC_BASEPAIR | AVF_METRIC_RECORD_BP), replicates, level_percent);
+}
+
+/* summary_kind_ci.tsv: the same file keyed by the call kinds (avk_kind_tallies' and avk_kind_boot_tallies' layouts).  One layout, one writer. */
+int avf_write_summary_kind_ci(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks, uint32_t metrics_mask,
+                              uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent) {
+    if (!path || !kind_blocks || (n_labels && !label_names)) return fail(AVK_E_ARG, "null argument");
+    const char *names[AVK_N_KINDS];
+    for (uint32_t k = 0; k < AVK_N_KINDS; ++k) names[k] = avk_kind_name_of(k);
+    return avf_write_summary_size_ci(path, compare_label, AVK_N_KINDS, names, n_labels, label_names, kind_blocks, metrics_mask, replicates, boot_blocks, level_percent);
+}
+
+/* kind_ratios_ci.tsv: kind_ratios.tsv's rows — same order, same rows left out, the same ten columns — followed by titv_lo titv_hi hethom_lo hethom_hi replicates: each
+ * ratio's interval by the percentile rule over the replicates in which its denominator is not 0; `replicates` is the smaller of the two counts. */
+int avf_write_kind_ratios_ci(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks, uint32_t replicates,
+                             const uint64_t *boot_blocks, uint32_t level_percent) {
+    if (!path || !kind_blocks || (n_labels && !label_names) || !replicates || !boot_blocks) return fail(AVK_E_ARG, "null argument, or no replicates");
+    if (level_percent != 90 && level_percent != 95 && level_percent != 99) return fail(AVK_E_ARG, "the interval's level is 90, 95 or 99, not %u", level_percent);
+    for (uint32_t l = 0; l < n_labels; ++l)
+        if (!label_names[l]) return fail(AVK_E_ARG, "null argument");
+    const std::string p(path);
+    const char delim = p.size() >= 4 && p.compare(p.size() - 4, 4, ".csv") == 0 ? ',' : '\t';
+    FILE *fp = fopen(path, "w");
+    if (!fp) return fail(AVK_E_ARG, "cannot create %s", path);
+    const std::string label = csv_field(compare_label ? compare_label : "", delim);
+    static const char *const header[15] = {"compare_label", "region_label", "variant_type", "set", "ti", "tv", "titv_ratio", "het", "hom_alt", "het_hom_ratio",
+                                           "titv_lo", "titv_hi", "hethom_lo", "hethom_hi", "replicates"};
+    for (int k = 0; k < 15; ++k) fprintf(fp, "%s%c", header[k], k == 14 ? '\n' : delim);
+    static const char *const set_name[6] = {"truth_total", "truth_tp", "truth_fn", "query_total", "query_tp", "query_fp"};
+    const int size_fields = AVK_F_WHAP_QUERY_FP + 1;
+    const size_t block_words = (size_t)AVK_N_KINDS * AVK_N_GROUPS * size_fields;
+    /* ti, tv, het, hom of set s of a block over the groups gs; `any`: the block holds a GT count in these groups */
+    auto counts = [&](const uint64_t *block, const std::vector<int> &gs, uint64_t c[6][4], uint64_t &any) {
+        any = 0;
+        for (int s = 0; s < 6; ++s) c[s][0] = c[s][1] = c[s][2] = c[s][3] = 0;
+        for (uint32_t k = 0; k < AVK_N_KINDS; ++k) {
+            uint64_t m[4] = {0, 0, 0, 0};
+            for (int g : gs) {
+                const uint64_t *gp = block + ((size_t)k * AVK_N_GROUPS + g) * size_fields;
+                for (int q = 0; q < 4; ++q) m[q] += gp[AVK_F_GT_TRUTH_TP + q];
+            }
+            const uint64_t set[6] = {m[0] + m[1], m[0], m[1], m[2] + m[3], m[2], m[3]};
+            any += set[0] + set[3];
+            const uint32_t gt = k / AVK_KIND_N_SUB, sub = k % AVK_KIND_N_SUB;
+            for (int s = 0; s < 6; ++s) {
+                if (sub == AVK_KIND_SUB_TS) c[s][0] += set[s];
+                if (sub == AVK_KIND_SUB_TV) c[s][1] += set[s];
+                if (gt == AVK_KIND_GT_HET) c[s][2] += set[s];
+                if (gt == AVK_KIND_GT_HOM) c[s][3] += set[s];
+            }
+        }
+    };
+    std::vector<std::vector<double>> xs(12); /* [set][titv | hethom] */
+    for (uint32_t sc = 0; sc <= n_labels; ++sc) {
+        const std::string region_label = csv_field(sc ? label_names[sc - 1] : "ALL", delim);
+        const uint64_t *block = kind_blocks + (size_t)sc * block_words, *rep0 = boot_blocks + (size_t)sc * replicates * block_words;
+        auto rows = [&](const char *vtype, const std::vector<int> &gs, bool always) {
+            uint64_t c[6][4], any;
+            counts(block, gs, c, any);
+            if (!always && !any) return; /* is_empty: no row in summary.tsv, kind_ratios.tsv or here */
+            for (auto &x : xs) x.clear();
+            for (uint32_t b = 0; b < replicates; ++b) {
+                uint64_t cb[6][4], anyb;
+                counts(rep0 + (size_t)b * block_words, gs, cb, anyb);
+                for (int s = 0; s < 6; ++s) {
+                    if (cb[s][1]) xs[2 * s].push_back((double)cb[s][0] / (double)cb[s][1]);
+                    if (cb[s][3]) xs[2 * s + 1].push_back((double)cb[s][2] / (double)cb[s][3]);
+                }
+            }
+            for (int s = 0; s < 6; ++s) {
+                const std::string titv = c[s][1] ? fmt_f64((double)c[s][0] / (double)c[s][1]) : std::string(), hethom = c[s][3] ? fmt_f64((double)c[s][2] / (double)c[s][3]) : std::string();
+                const size_t m = std::min(xs[2 * s].size(), xs[2 * s + 1].size());
+                std::string lo[2], hi[2];
+                ci_bounds(xs[2 * s], level_percent, lo[0], hi[0]);
+                ci_bounds(xs[2 * s + 1], level_percent, lo[1], hi[1]);
+                fprintf(fp, "%s%c%s%c%s%c%s%c%llu%c%llu%c%s%c%llu%c%llu%c%s%c%s%c%s%c%s%c%s%c%llu\n", label.c_str(), delim, region_label.c_str(), delim, vtype, delim, set_name[s], delim,
+                        (unsigned long long)c[s][0], delim, (unsigned long long)c[s][1], delim, titv.c_str(), delim, (unsigned long long)c[s][2], delim, (unsigned long long)c[s][3], delim,
+                        hethom.c_str(), delim, lo[0].c_str(), delim, hi[0].c_str(), delim, lo[1].c_str(), delim, hi[1].c_str(), delim, (unsigned long long)m);
+            }
+        };
+        rows("ALL", {0}, true);
+        for (int t = 0; t < AVK_N_VARIANT_TYPES; ++t) rows(ci_type_name[t], {1 + t}, false);
+        for (int j = 0; j < 3; ++j) {
+            std::vector<int> gs;
+            for (int t : ci_joint_types(j)) gs.push_back(1 + t);
+            rows(ci_joint_name[j], gs, false);
+        }
+    }
     const bool bad = ferror(fp) != 0;
     if (fclose(fp) != 0 || bad) return fail(AVK_E_ARG, "write error on %s", path);
     return 0;

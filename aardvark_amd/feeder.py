@@ -503,6 +503,51 @@ def write_summary_ci(path, tally, names, strat_tallies, boot_blocks, level=95, c
                                          bb.reshape(-1).ctypes.data_as(u64p), int(level)))
 
 
+def _boot_blocks(names, keys, boot_blocks):
+    bb = np.ascontiguousarray(boot_blocks, dtype=np.uint64)
+    if bb.ndim != 5 or bb.shape[0] != 1 + len(names) or bb.shape[2] != keys or bb.shape[4] != 14 or bb.shape[1] < 1:
+        raise ValueError("boot_blocks is [1 + labels, replicates, %d, N_GROUPS, 14]" % keys)
+    return bb
+
+
+def write_summary_size_ci(path, bin_names, names, size_blocks, boot_blocks, level=95, compare_label="compare", metrics=METRIC_GT | METRIC_HAP | METRIC_WEIGHTED_HAP):
+    """avf_write_summary_size_ci: summary_size_ci.tsv — write_summary_size's rows with write_summary_ci's ten interval columns over the replicates `boot_blocks`
+    ([1 + len(names), replicates, len(bin_names), N_GROUPS, 14], Context.size_boot_tallies' layout); level: 90, 95 or 99"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    sb = np.ascontiguousarray(size_blocks, dtype=np.uint64)
+    if sb.ndim != 4 or sb.shape[0] != 1 + len(names) or sb.shape[1] != len(bin_names) or sb.shape[3] != 14:
+        raise ValueError("size_blocks is [1 + labels, bins, N_GROUPS, 14]")
+    bb = _boot_blocks(names, len(bin_names), boot_blocks)
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names]) if names else None
+    bins = (C.c_char_p * len(bin_names))(*[b.encode() for b in bin_names])
+    lib.avf_write_summary_size_ci.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32, C.c_uint32, u64p, C.c_uint32]
+    _check(lib, lib.avf_write_summary_size_ci(os.fsencode(path), compare_label.encode(), len(bin_names), bins, len(names), arr, sb.reshape(-1).ctypes.data_as(u64p), metrics, bb.shape[1],
+                                              bb.reshape(-1).ctypes.data_as(u64p), int(level)))
+
+
+def write_summary_kind_ci(path, names, kind_blocks, boot_blocks, level=95, compare_label="compare", metrics=METRIC_GT | METRIC_HAP | METRIC_WEIGHTED_HAP):
+    """avf_write_summary_kind_ci: summary_kind_ci.tsv — write_summary_kind's rows with the interval columns; boot_blocks is Context.kind_boot_tallies' layout"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    kb, arr = _kind_blocks(names, kind_blocks)
+    bb = _boot_blocks(names, 9, boot_blocks)
+    lib.avf_write_summary_kind_ci.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32, C.c_uint32, u64p, C.c_uint32]
+    _check(lib, lib.avf_write_summary_kind_ci(os.fsencode(path), compare_label.encode(), len(names), arr, kb.reshape(-1).ctypes.data_as(u64p), metrics, bb.shape[1],
+                                              bb.reshape(-1).ctypes.data_as(u64p), int(level)))
+
+
+def write_kind_ratios_ci(path, names, kind_blocks, boot_blocks, level=95, compare_label="compare"):
+    """avf_write_kind_ratios_ci: kind_ratios_ci.tsv — write_kind_ratios' rows followed by titv_lo titv_hi hethom_lo hethom_hi replicates"""
+    lib = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    kb, arr = _kind_blocks(names, kind_blocks)
+    bb = _boot_blocks(names, 9, boot_blocks)
+    lib.avf_write_kind_ratios_ci.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), u64p, C.c_uint32, u64p, C.c_uint32]
+    _check(lib, lib.avf_write_kind_ratios_ci(os.fsencode(path), compare_label.encode(), len(names), arr, kb.reshape(-1).ctypes.data_as(u64p), bb.shape[1],
+                                             bb.reshape(-1).ctypes.data_as(u64p), int(level)))
+
+
 def write_debug_tables(summary_path, sequences_path, genome, batch, result, metrics=METRIC_GT | METRIC_BASEPAIR):
     """region_summary.tsv.gz and region_sequences.tsv.gz of --output-debug for one batch and its ResultBatch (with sequences)."""
     lib = load_library()

@@ -728,6 +728,29 @@ int  avk_compare_packed_kind(avk_ctx *ctx, const avk_packed_batch *batch, const 
  * sums do not depend on the cut. */
 int  avk_kind_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_region_labels *labels, uint32_t threads, uint64_t *out);
 
+/* BOOTSTRAP REPLICATES OF THE PER-CALL BLOCKS (avk_callboot.inl; the rule is stated in aardvark_amd/csrc/avk_callboot.h and DESIGN.md section 5): the replicates
+ * avk_boot_tallies gives the tallies, for the size-bin block and the call-kind block — what an interval on the recall of len_ge50, on het_tv precision or on a
+ * Ti/Tv ratio is made from.  No new randomness:
+ *   rule     out[scope][b][key][g][f] = sum over the scope's solved regions r of w(r, b) * X_r[key][g][f]; w = avk_boot_weight (the same seed gives a region the
+ *            same weight as in avk_boot_tallies); X_r = region r's contribution to avk_size_tallies' block (key = bin) or avk_kind_tallies' block (key = kind),
+ *            with every refusal of those stages
+ *   block    out[AVK_CALLBOOT_AT(scope, B, b, n_keys, key, g, f)] = out[(((scope * B + b) * n_keys + key) * AVK_N_GROUPS + g) * AVK_SIZE_FIELDS + f], 64-bit; sums
+ *            are ADDED; additive over batches, slices, shards and contexts
+ *   cap      1 <= replicates <= AVK_BOOT_MAX_REPLICATES and (1 + labels) * replicates * n_keys <= AVK_CALLBOOT_MAX_BLOCKS, otherwise AVK_E_ARG
+ *   law      replicate b summed over its keys is words g * AVK_N_FIELDS + f (f < 14) of replicate b of avk_boot_tallies, for the same seed
+ * There is no one-call avk_compare_packed_* form and no submit / wait form: a caller that wants these replicates keeps the batch resident. */
+#include "../aardvark_amd/csrc/avk_callboot.h"
+uint32_t avk_callboot_block(avk_ctx *ctx, uint32_t n_keys);     /* replicates of one scope a launch holds for n_keys keys (1 .. 16; 0 otherwise): more are more launches */
+/* resident forms: the preconditions and refusals of avk_size_tallies / avk_kind_tallies, the replicate count's and the cap's; every refusal leaves out untouched */
+int  avk_size_boot_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_size_spec *size_spec, const avk_boot_spec *boot_spec, const avk_strata *strata, uint64_t *out);
+int  avk_kind_boot_tallies(avk_ctx *ctx, avk_dev_batch *db, const avk_boot_spec *boot_spec, const avk_strata *strata, uint64_t *out);
+/* host only (no GPU involved): the same sums, bit for bit, from the wide batch (with its start array) and its results, as avk_size_tallies_host / avk_kind_tallies_host
+ * read them; a label named twice in a region's list counts twice.  threads: host threads (0: one); the sums do not depend on the cut. */
+int  avk_size_boot_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_size_spec *size_spec, const avk_boot_spec *boot_spec,
+                                const avk_region_labels *labels, uint32_t threads, uint64_t *out);
+int  avk_kind_boot_tallies_host(const avk_region_batch *batch, const avk_result_batch *res, const avk_boot_spec *boot_spec, const avk_region_labels *labels, uint32_t threads,
+                                uint64_t *out);
+
 /* SEQUENCE-CONTEXT labels (avk_context.inl): labels that are functions of the reference sequence alone, made by kernel from the reference avk_ref_upload left in
  * HBM — a stratified job needs no BED set for them.  The rule is this project's own (the reference has no such labels):
  *   window   a region's query is the one the interval sets get, [first, last] on its contig; a family's window is [first - pad, last + 1 + pad), clamped to the

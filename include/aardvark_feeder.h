@@ -192,6 +192,18 @@ int avf_feed_scores(const avf_feed *f, const float *per_record, uint64_t n_recor
  * denominators non-zero and recall + precision > 0), the smallest of the three.  Joint rows are summed per replicate before the ratio is taken.  level_percent: 90, 95 or 99. */
 int avf_write_summary_ci(const char *path, const char *compare_label, const uint64_t *tally, uint32_t n_labels, const char *const *label_names, const uint64_t *strat_tallies,
                          uint32_t metrics_mask, uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent);
+/* summary_size_ci.tsv / summary_kind_ci.tsv: the rows of summary_size.tsv / summary_kind.tsv for the same point blocks — same order, same key columns (the bin's or
+ * kind's name in `filter`), rows they leave out left out — each followed by summary_ci.tsv's ten interval columns, by the same percentile rule (one statement in the
+ * source).  size_blocks / kind_blocks: avk_size_tallies' / avk_kind_tallies' layout; boot_blocks: avk_size_boot_tallies' / avk_kind_boot_tallies' layout,
+ * [1 + n_labels][replicates][keys][AVK_N_GROUPS][14].  BASEPAIR and RECORD_BP bits of the mask are ignored. */
+int avf_write_summary_size_ci(const char *path, const char *compare_label, uint32_t n_bins, const char *const *bin_names, uint32_t n_labels, const char *const *label_names,
+                              const uint64_t *size_blocks, uint32_t metrics_mask, uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent);
+int avf_write_summary_kind_ci(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks, uint32_t metrics_mask,
+                              uint32_t replicates, const uint64_t *boot_blocks, uint32_t level_percent);
+/* kind_ratios_ci.tsv: kind_ratios.tsv's rows and columns followed by titv_lo titv_hi hethom_lo hethom_hi replicates.  Each ratio's interval is taken, by the same rule,
+ * over the replicates in which its denominator is not 0; `replicates` is the smaller of the two counts. */
+int avf_write_kind_ratios_ci(const char *path, const char *compare_label, uint32_t n_labels, const char *const *label_names, const uint64_t *kind_blocks, uint32_t replicates,
+                             const uint64_t *boot_blocks, uint32_t level_percent);
 
 /* One of the two annotated VCFs of `compare` (VariantCategorizer, src/writers/variant_categorizer.rs:41-230; source 0 =
  * truth.vcf.gz, 1 = query.vcf.gz): the meta lines of input_vcf, the aardvark_version / aardvark_command lines and the
